@@ -10,9 +10,14 @@ Workload = BASELINE.json configs[1] ("CMU-MOSEI features, batch=64 ... 1xMI355X 
 N > 1 shards the batch (weak scaling: 64 samples per GPU, global batch 64*N) with ONE RCCL all-reduce
 of the flat gradient bucket per step plus the two exactness exchanges (sdumc_amd/trainer.py).
 
-Output: ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel,
-HIP events on the launch stream) and `cpu_baseline` (the CPU oracle = port of the reference's torch-eager
-path, timed on this box's host cores; rank 0, N=1 only).
+Output: ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets up, warms up,
+times the K steps and prints that line, nothing else.  `--full` adds everything that takes runs of its own: `roofline` (dominant
+kernel, HIP events on the launch stream), `cpu_baseline` (the CPU oracle = port of the reference's torch-eager path, timed on the
+host cores; rank 0, N=1 only), the `side` legs of the default workload and the all-reduce probe of the data-parallel line.
+
+`--dump-outputs DIR` writes what the timed path handed its caller after its last step (rank 0): DIR/losses.npy (the 8 loss
+slots), DIR/params.npy (the flat parameter buffer after Adam) and DIR/grads.npy (the gradient bucket), float32, every element.
+The inputs (parameters, batches, dropout seed) are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import ctypes as C
@@ -37,8 +42,8 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0          # same guide: dense bf16 matrix peak (th
 PEAK_F32_ON_BF16_PIPE_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 6.0
 F32_ARITHMETIC = ("f32 in, out and accumulation; GEMM products on the bf16 matrix pipe from operands split exactly into three bf16 "
                   "parts each (six of the nine part products, each exact in f32; error per product < 2^-23, as close to f64 as the "
-                  "v_mfma_f32_32x32x2_f32 path: tools/gg_split_check.py, tests/test_gpu_split.py); side.c2_f32_mfma is the same step "
-                  "with every product on the f32 MFMAs")
+                  "v_mfma_f32_32x32x2_f32 path: tools/gg_split_check.py, tests/test_gpu_split.py); side.c2_f32_mfma of a --full run is "
+                  "the same step with every product on the f32 MFMAs")
 PEAK_HBM_GBS = 8000.0                  # same guide: HBM3E peak (6.3 TB/s achievable with a streaming copy)
 # The default is the configuration the metric is quoted on (configs[1]); the others are the parity-test shapes of
 # SURVEY §8, selectable for side measurements (`--workload c1|c5`), never what the driver's default run reports.
@@ -459,6 +464,14 @@ def cpu_baseline_leg(steps=3):
             "sec_per_step": round(best, 4)}
 
 
+def dump_outputs(path, losses, params, grads):
+    """--dump-outputs: the timed path's results after its last step as float32 .npy files (~34 MB at the default workload)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("losses", losses), ("params", params), ("grads", grads)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def epoch_leg(args, engine, flat, lay, dev, bf16=None, nb=None, warmup=None):
     """One epoch of REAL loader behaviour -- every batch has its own padded shape and is assembled from the resident store inside the
     clock -- against the static-shape step on one resident batch at the same mean padded frame counts."""
@@ -539,7 +552,13 @@ def main():
     ap.add_argument("--resident", type=int, default=N_RESIDENT, help="distinct resident batches the timed loop rotates through (single GPU)")
     ap.add_argument("--epoch-batches", type=int, default=200, help="batches of the ragged-epoch side legs")
     ap.add_argument("--stream-priority", type=int, default=None, help="experiment: run the timed loop on a torch stream of this priority (-1 = high)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: roofline, CPU baseline, the side legs of the default workload, the all-reduce probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's losses, parameters and gradients after its last step to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "epoch":
+        ap.error("--dump-outputs writes the outputs of the train step the headline times; --workload epoch times a ragged epoch")
     global B_PER_GPU, T_MOSEI, DIMS, TRAIN_FLOPS_PER_SAMPLE, WORKLOAD_TEXT
     epoch = args.workload == "epoch"
     B_PER_GPU, T_MOSEI, DIMS, TRAIN_FLOPS_PER_SAMPLE, WORKLOAD_TEXT = WORKLOADS["c2" if epoch else args.workload]
@@ -635,6 +654,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # (before the all-reduce probe below, which overwrites the gradient bucket, and before the roofline leg's extra steps)
+    losses = (step.losses if (world == 1 and not force_dp) else step.be.losses).cpu()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, flat, step.grads if (world == 1 and not force_dp) else step.be.grads)
     dp_extra = None
     if world > 1 or force_dp:
         mine = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -642,21 +665,21 @@ def main():
         dist.all_gather(every, mine)
         per_rank = [float(t.item()) for t in every]
         dt = max(per_rank)                                   # MAX over ranks, as the contract says
-        # the gradient all-reduce on its own (the flat 15.4 MB bucket, same call the step makes), outside the timed region
-        bucket = step.be.grads
-        torch.cuda.synchronize()
-        dist.barrier()
-        t1 = time.perf_counter()
-        for _ in range(20):
-            dist.all_reduce(bucket)
-        torch.cuda.synchronize()
-        ar_ms = 1e3 * (time.perf_counter() - t1) / 20
-        bucket.zero_()
         dp_extra = {"per_rank_ms_per_step": [round(1e3 * t / args.steps, 4) for t in per_rank],
-                    "allreduce_ms": round(ar_ms, 4), "allreduce_bytes": bucket.numel() * 4,
                     "backend": dist.get_backend(), "overlap": bool(step.overlap)}
+        if args.full:
+            # the gradient all-reduce on its own (the flat 15.4 MB bucket, same call the step makes), outside the timed region
+            bucket = step.be.grads
+            torch.cuda.synchronize()
+            dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(20):
+                dist.all_reduce(bucket)
+            torch.cuda.synchronize()
+            ar_ms = 1e3 * (time.perf_counter() - t1) / 20
+            bucket.zero_()
+            dp_extra.update({"allreduce_ms": round(ar_ms, 4), "allreduce_bytes": bucket.numel() * 4})
 
-    losses = (step.losses if (world == 1 and not force_dp) else step.be.losses).cpu()
     if not torch.isfinite(losses).all():
         raise SystemExit(f"non-finite loss: {losses.tolist()}")
 
@@ -683,7 +706,7 @@ def main():
     }
     if dp_extra is not None:
         out["data_parallel"] = dp_extra
-    if rotate and args.workload == "c2" and not args.bf16 and not args.serial_lanes and not args.no_side:
+    if args.full and rotate and args.workload == "c2" and not args.bf16 and not args.serial_lanes and not args.no_side:
         out["side"] = {"c3_bf16": c3_bf16_side_leg(engine, flat0, batches, args),
                        "c2_f32_mfma": c2_f32_mfma_side_leg(engine, _lib, flat0, batches, args, losses),
                        "set_batch_loop": set_batch_loop_side_leg(engine, flat0, batches, args)}
@@ -694,13 +717,13 @@ def main():
                                                    "static_shape_at_mean_T", "epoch_over_static")}
             out["side"][name]["workload"] = e["config"]["workload"]
             out["side"][name]["config"] = {k: e["config"][k] for k in ("distinct_batch_shapes", "mean_padded_T", "store_utterances", "store_gb")}
-    if not args.no_roofline:     # every rank runs it (the DP step has collectives); rank 0 reports
+    if args.full and not args.no_roofline:     # every rank runs it (the DP step has collectives); rank 0 reports
         roof = roofline_leg(_lib, run if single else step.step, max(3, min(10, args.steps)),
                             traffic_ok=(args.workload == "c2" and not args.bf16))
         if rank == 0:
             out["roofline"] = hbm_roofline_bf16(out["ms_per_step"], roof) if (args.bf16 and args.workload == "c2" and world == 1) else roof
     if rank == 0 and world == 1:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_leg()
             out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
     if world > 1 or force_dp:
