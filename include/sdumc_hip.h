@@ -579,6 +579,26 @@ int sdumc_distill_fwd_bwd(int32_t B, float denom, const float* vals, const float
                           const float* ct, const float* z, const float* weights5, const float* ssd_global,
                           float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
                           void* stream);
+/* Row-wise criteria for the drop-in loss modules: value and gradient in ONE launch, one wavefront per row, fixed
+ * summation order (rows in index order per wavefront, wavefronts in index order: bitwise reproducible).
+ * a, b: [rows, groups, width] contiguous (groups = 1 for 2-D inputs), width <= 1024; denom = size(0) of the GLOBAL
+ * batch; loss_out (device scalar) is WRITTEN with the unweighted value; da / db ([rows, groups, width], overwritten
+ * with weight * dLoss/da, weight * dLoss/db) may be NULL.  Identical inputs give value 0 and gradient 0.
+ *
+ * CosineSimilarityLoss4Seq (loss.py:100-119): sum over the groups of the mean over rows of 1 - cos(a_row, b_row)
+ *   = sum over all rows*groups / denom.  cos as torch.cosine_similarity: every norm is clamped from below to
+ *   eps = 1e-8 on its own, a clamped norm passes no gradient (all-zero rows: cos = 0, gradient = other / (eps * norm)). */
+int sdumc_cosine_fwd_bwd(const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                         float weight, float* loss_out, float* da, float* db, void* stream);
+/* KLLoss (loss.py:74-97): (KL(softmax b || softmax a) + KL(softmax a || softmax b)) / 2, softmax over the last axis,
+ * reduction 'batchmean' = sum over everything / denom.  Log-softmax with the row maximum subtracted, fp32. */
+int sdumc_kl_fwd_bwd(const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                     float weight, float* loss_out, float* da, float* db, void* stream);
+/* CELoss (loss.py:6-16): log_softmax(a, 1) + NLLLoss(reduction='sum') / denom.  a [rows, width] logits, b [rows] the
+ * class indices held as floats (truncated like target.long(); an index outside [0, width) makes the value NaN).
+ * groups must be 1 and db NULL (else SDUMC_EINVAL): the targets take no gradient. */
+int sdumc_ce_fwd_bwd(const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                     float weight, float* loss_out, float* da, float* db, void* stream);
 /* gradient rows [row0, row0+rows) from the workspace a previous sdumc_rnc_fwd_bwd call filled
  * (a data-parallel rank owns two row ranges of the gathered matrix: its stream-0 and stream-1 rows) */
 int sdumc_rnc_dfeat_rows(const float* feats, int32_t n, int32_t dim, float temperature, float weight, int32_t row0,
@@ -1005,7 +1025,16 @@ typedef struct sdumc_step_cfg {
   const float* rnc_feats_global;  /* [2*B_global, 64] = cat(r_stream0 of all ranks, r_stream1 of all ranks) */
   const float* rnc_labels_global; /* [2*B_global] */
   int32_t rnc_row0[2];   /* rows of this rank's stream-0 / stream-1 features in the gathered matrix */
+  /* The criterion of the three distillation pairs text_hidden, cross_text, fused (main :148 and its commented-out tail):
+   * SDUMC_DISTILL_RMSE (0 = a zeroed struct) RMSELoss, _COSINE CosineSimilarityLoss4Seq, _KL KLLoss; anything else:
+   * SDUMC_EINVAL before a launch.  losses[3..5] hold the chosen criterion's values.  Cosine and KL are sums over rows
+   * divided by B_global: like the MSE entries, a data-parallel rank writes its LOCAL sum / B_global and ssd_global is
+   * not read. */
+  int32_t distill;
 } sdumc_step_cfg;
+#define SDUMC_DISTILL_RMSE 0
+#define SDUMC_DISTILL_COSINE 1
+#define SDUMC_DISTILL_KL 2
 
 size_t sdumc_loss_workspace_bytes(const sdumc_net_dims* d, int32_t B_global);
 /* local sums of squared differences of the three RMSE pairs -> ssd_out float[3] (for the all-reduce) */

@@ -154,7 +154,17 @@ class StepCfg(C.Structure):
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
                 ("losses", C.c_void_p),
                 ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
-                ("rnc_labels_global", C.c_void_p), ("rnc_row0", C.c_int32 * 2)]
+                ("rnc_labels_global", C.c_void_p), ("rnc_row0", C.c_int32 * 2), ("distill", C.c_int32)]
+
+
+# sdumc_step_cfg.distill: the criterion of the three distillation pairs (SDUMC_DISTILL_* of include/sdumc_hip.h)
+DISTILL = {"rmse": 0, "cosine": 1, "kl": 2}
+
+
+def distill_code(name):
+    if not isinstance(name, str) or name not in DISTILL:
+        raise SdumcError(f"distill must be one of {sorted(DISTILL)}, not {name!r}")
+    return DISTILL[name]
 
 
 GATHER_MAX_SEGS = 8
@@ -260,6 +270,12 @@ _SIGS = {
     "sdumc_ssd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdumc_rmse_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_float, C.c_void_p,
                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "sdumc_cosine_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdumc_kl_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdumc_ce_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdumc_rnc_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "sdumc_rnc_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -2833,6 +2833,7 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   if (!io->vals || !io->fused || !io->rnc || !io->text_hidden || !io->cross_text) return SDUMC_EINVAL;
   if (!g->d_vals || !g->d_fused || !g->d_rnc || !g->d_text_hidden || !g->d_cross_text) return SDUMC_EINVAL;
   if (!cfg->labels || !cfg->losses) return SDUMC_EINVAL;
+  if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;
   hipStream_t st = as_stream(stream);
   const int B = d->B, Bg = cfg->B_global > 0 ? cfg->B_global : B;
   const LossScratch ls = loss_scratch(*d, cfg->B_global, static_cast<float*>(scratch));
@@ -2849,7 +2850,8 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   if (!cfg->rnc_feats_global && !cfg->ssd_global && Bg == B) {
     const int rc = sdumc_losses_fused_(B, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, io->rnc, RD,
                                        cfg->temperature, w, dv, dth, dct, df, dr, L, ls.ssd_ws, ls.rnc_ws,
-                                       total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2, stream);
+                                       total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2, cfg->distill,
+                                       stream);
     if (rc < 0) return rc;
     done = rc == 0;
     if (done && total_pending && hyper) {
@@ -2858,10 +2860,10 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
     }
   }
   if (!done) {
-  // MSELoss x2 (main :137-138) + RMSELoss x3 (main :148; teacher side detached for text_feat / text_query_feat,
-  // not for features): value and gradients in two launches
-  RET(sdumc_distill_fwd_bwd(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
-                            cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, stream));
+  // MSELoss x2 (main :137-138) + the distillation criterion x3 (main :148; teacher side detached for text_feat /
+  // text_query_feat, not for features): value and gradients in two launches
+  RET(sdumc_distill_crit_(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
+                          cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, cfg->distill, stream));
   // RnCLoss over cat(r_stream0, r_stream1) with labels repeated (main :134,:140; loss.py:282-283)
   if (cfg->rnc_feats_global) {
     if (!cfg->rnc_labels_global) return SDUMC_EINVAL;
@@ -2924,6 +2926,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
                                 void* stream) {
   RET(check_io(d, io));
   if (!cfg || d->streams != 2 || !cfg->adam_m || !cfg->adam_v || !cfg->hyper) return SDUMC_EINVAL;
+  if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;   // before anything is launched
   const StepLayout sl = step_layout(*d);
   if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   char* base = static_cast<char*>(io->workspace);

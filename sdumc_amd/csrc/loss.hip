@@ -3,6 +3,9 @@
 //   RMSELoss  toolkit/utils/loss.py:37-51   sqrt(mean((a-b)^2))   (split: ssd, then sqrt -> DP-exact)
 //   RnCLoss   toolkit/utils/loss.py:271-315 Rank-N-Contrast; the boolean neg_mask (loss.py:303) is
 //             evaluated with the same fp32 operations as the reference, so membership is bit-exact.
+//   CosineSimilarityLoss4Seq  toolkit/utils/loss.py:100-119   sum over groups of mean over rows of 1 - cos
+//   KLLoss    toolkit/utils/loss.py:74-97   (KL(softmax b || softmax a) + KL(softmax a || softmax b)) / 2, batchmean
+//   CELoss    toolkit/utils/loss.py:6-16    log_softmax + NLL, summed, / len
 // All sums run in a fixed order (no float atomics): results are bitwise reproducible.
 #include "common.h"
 
@@ -431,6 +434,164 @@ __global__ void rnc_mask_kernel(const float* y, int n, uint8_t* mask) {
 }
 
 
+// ---- row-wise criteria: one wavefront per row of W <= 1024 elements, the row held in registers (16 per lane) ----------
+// Every row's value and gradient depend on that row alone and the loss is a plain sum of row values / denom, so -- unlike
+// RMSE, the square root of a GLOBAL mean -- the gradient needs no first pass and shards of a batch add up exactly.
+constexpr int ROW_MAXW = 1024;
+constexpr int ROW_K = ROW_MAXW / 64;
+constexpr int CRIT_COSINE = SDUMC_DISTILL_COSINE, CRIT_KL = SDUMC_DISTILL_KL, CRIT_CE = 3;
+
+// 1 - cos(x, y) as torch.cosine_similarity (ATen Distance.cpp): x / max(|x|, eps) . y / max(|y|, eps), eps = 1e-8, each norm
+// clamped on its own; clamp_min passes the gradient where norm >= eps only, so a clamped norm is a constant.
+// gx / gy (may be null): scale * d(1 - cos)/dx, /dy.  Returns the row's value in every lane.
+template <bool GRAD>
+__device__ __forceinline__ float cosine_row(const float* xr, const float* yr, int W, int lane, float scale, float* gx, float* gy) {
+  float x[ROW_K], y[ROW_K];
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    const int c = lane + 64 * k;
+    x[k] = c < W ? xr[c] : 0.f;
+    y[k] = c < W ? yr[c] : 0.f;
+  }
+  float sx = 0.f, sy = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    sx += x[k] * x[k];
+    sy += y[k] * y[k];
+  }
+  const float nx = sqrtf(wave_sum(sx)), ny = sqrtf(wave_sum(sy));
+  const float eps = 1e-8f;
+  const float cx = fmaxf(nx, eps), cy = fmaxf(ny, eps);
+  float dot = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    x[k] = x[k] / cx;
+    y[k] = y[k] / cy;
+    dot += x[k] * y[k];
+  }
+  const float cs = wave_sum(dot);
+  if (GRAD) {
+    const float kx = nx >= eps ? cs : 0.f, ky = ny >= eps ? cs : 0.f;
+#pragma unroll
+    for (int k = 0; k < ROW_K; ++k) {
+      const int c = lane + 64 * k;
+      if (c < W) {
+        if (gx) gx[c] = -scale * (y[k] - kx * x[k]) / cx;
+        if (gy) gy[c] = -scale * (x[k] - ky * y[k]) / cy;
+      }
+    }
+  }
+  return 1.f - cs;
+}
+
+// stable softmax / log-softmax of one row held in registers: e[k] <- softmax, l[k] <- log-softmax (row maximum subtracted)
+__device__ __forceinline__ void softmax_row(const float (&v)[ROW_K], int W, int lane, float (&e)[ROW_K], float (&l)[ROW_K]) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k)
+    if (lane + 64 * k < W) mx = fmaxf(mx, v[k]);
+  mx = wave_max(mx);
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    e[k] = lane + 64 * k < W ? expf(v[k] - mx) : 0.f;
+    s += e[k];
+  }
+  s = wave_sum(s);
+  const float ls = logf(s);
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    e[k] = e[k] / s;
+    l[k] = lane + 64 * k < W ? (v[k] - mx) - ls : 0.f;
+  }
+}
+
+// S = sum_i (Q_i - P_i)(log Q_i - log P_i) = KL(Q || P) + KL(P || Q), P = softmax(x), Q = softmax(y); the loss is S / 2 per row.
+// With d = log Q - log P:  dS/dx_j = P_j (E_P[d] - d_j) + P_j - Q_j,   dS/dy_j = Q_j (d_j - E_Q[d]) + Q_j - P_j.
+// scale already holds the 1/2.  Equal rows: d = 0 and P = Q exactly -> value 0, gradient 0.
+template <bool GRAD>
+__device__ __forceinline__ float kl_row(const float* xr, const float* yr, int W, int lane, float scale, float* gx, float* gy) {
+  float x[ROW_K], y[ROW_K], P[ROW_K], Q[ROW_K], d[ROW_K];
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    const int c = lane + 64 * k;
+    x[k] = c < W ? xr[c] : 0.f;
+    y[k] = c < W ? yr[c] : 0.f;
+  }
+  softmax_row(x, W, lane, P, x);   // x <- log P
+  softmax_row(y, W, lane, Q, y);   // y <- log Q
+  float S = 0.f, ep = 0.f, eq = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    d[k] = y[k] - x[k];            // (0 beyond the row)
+    S += (Q[k] - P[k]) * d[k];
+    ep += P[k] * d[k];
+    eq += Q[k] * d[k];
+  }
+  S = wave_sum(S);
+  if (GRAD) {
+    ep = wave_sum(ep);
+    eq = wave_sum(eq);
+#pragma unroll
+    for (int k = 0; k < ROW_K; ++k) {
+      const int c = lane + 64 * k;
+      if (c < W) {
+        if (gx) gx[c] = scale * (P[k] * (ep - d[k]) + (P[k] - Q[k]));
+        if (gy) gy[c] = scale * (Q[k] * (d[k] - eq) + (Q[k] - P[k]));
+      }
+    }
+  }
+  return S;
+}
+
+// -log_softmax(x)[t]; gx = scale * (softmax(x) - onehot(t)).  t outside [0, W): NaN (torch raises there; a kernel cannot).
+__device__ __forceinline__ float ce_row(const float* xr, float target, int W, int lane, float scale, float* gx) {
+  float x[ROW_K], P[ROW_K];
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) x[k] = lane + 64 * k < W ? xr[lane + 64 * k] : 0.f;
+  softmax_row(x, W, lane, P, x);
+  const int t = (int)target;       // target.long(): truncation
+  float pick = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_K; ++k) {
+    const int c = lane + 64 * k;
+    if (c == t && c < W) pick = x[k];
+    if (gx && c < W) gx[c] = scale * (P[k] - (c == t ? 1.f : 0.f));
+  }
+  pick = wave_sum(pick);
+  return (t >= 0 && t < W) ? -pick : NAN;
+}
+
+template <bool GRAD>
+__device__ __forceinline__ float crit_row(int crit, const float* xr, const float* yr, int W, int lane, float scale, float* gx,
+                                          float* gy) {
+  return crit == CRIT_COSINE ? cosine_row<GRAD>(xr, yr, W, lane, scale, gx, gy) : kl_row<GRAD>(xr, yr, W, lane, scale, gx, gy);
+}
+
+// The modules' standalone call: ONE workgroup of 16 wavefronts, wavefront w takes rows w, w + 16, ... in order, then the 16
+// partial sums are added in index order.  (No workspace in the call's signature, and the module loop is not the fast path:
+// the fused step runs the same row bodies across many workgroups, below.)
+__global__ __launch_bounds__(1024) void row_crit_kernel(int crit, const float* a, const float* b, int R, int W, float gscale,
+                                                        float vscale, float* loss_out, float* da, float* db) {
+  __shared__ float red[16];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float acc = 0.f;
+  for (int r = wave; r < R; r += 16) {
+    const size_t o = (size_t)r * W;
+    if (crit == CRIT_CE)
+      acc += ce_row(a + o, b[r], W, lane, gscale, da ? da + o : nullptr);
+    else
+      acc += crit_row<true>(crit, a + o, b + o, W, lane, gscale, da ? da + o : nullptr, db ? db + o : nullptr);
+  }
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int w = 0; w < 16; ++w) s += red[w];
+    *loss_out = s * vscale;
+  }
+}
+
 // ---- the five "small" distillation terms of main :137-148 in two launches -------------------------------
 // pass 1: per-block partial sums of squared differences of the three RMSE pairs (+ both MSE terms, block 0)
 // pass 2: every block re-reduces the (few) partials in a fixed order, then writes the gradients of its chunk
@@ -444,8 +605,11 @@ struct DistillArgs {
   float* losses;    // [8]: writes 1..5
   float* part;      // [3][nblk]
   int nblk[3];
+  int crit;         // SDUMC_DISTILL_*: uniform per launch
 };
 constexpr int DCH = 4096;   // elements per block
+static_assert(DCH % SDUMC_D == 0 && DCH % SDUMC_H == 0 && SDUMC_D <= ROW_MAXW && SDUMC_H <= ROW_MAXW,
+              "a block's chunk is a whole number of rows of every distillation pair");
 __device__ __forceinline__ void distill_pair(const DistillArgs& a, int p, const float*& s1, const float*& s0, float*& g,
                                              int64_t& n) {
   const int64_t per = p == 0 ? SDUMC_D : (p == 1 ? SDUMC_NQ * SDUMC_H : SDUMC_H);
@@ -455,9 +619,58 @@ __device__ __forceinline__ void distill_pair(const DistillArgs& a, int p, const 
   s1 = base + n;
   g = p == 0 ? a.d_th : (p == 1 ? a.d_ct : a.d_z);
 }
+// cosine / KL: the rows of a pair are its last axis (text_hidden [B,256], cross_text [B*7,128], fused [B,128]); a block's chunk
+// of DCH elements is 16 or 32 whole rows.  Pass 1: wavefront w adds the values of rows w, w + 4, ... of the chunk, the four sums
+// are added in order -> one partial per block, in the slots the sums of squares take.
+__device__ __forceinline__ void distill_rows_partials(const DistillArgs& a, const int bx, const int p, float* red) {
+  const float *s1, *s0;
+  float* g;
+  int64_t n;
+  distill_pair(a, p, s1, s0, g, n);
+  const int W = p == 0 ? SDUMC_D : SDUMC_H;
+  const int rpb = DCH / W, rows = (int)(n / W);
+  const int r1 = min(rows, (bx + 1) * rpb);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  float acc = 0.f;
+  for (int r = bx * rpb + wave; r < r1; r += 4)
+    acc += crit_row<false>(a.crit, s1 + (size_t)r * W, s0 + (size_t)r * W, W, lane, 0.f, nullptr, nullptr);
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) a.part[p * a.nblk[1] + bx] = red[0] + red[1] + red[2] + red[3];
+}
+// Pass 2: block 0 of a pair adds the partials in index order (the value); every block writes the gradients of its rows, which
+// need nothing from other rows.  Stream 1 is the first argument (main :148: loss(x_1, x_0.detach())).
+__device__ __forceinline__ void distill_rows_apply(const DistillArgs& a, const int bx, const int p, float* red) {
+  const float *s1, *s0;
+  float* g;
+  int64_t n;
+  distill_pair(a, p, s1, s0, g, n);
+  const float half = a.crit == CRIT_KL ? 0.5f : 1.f;
+  if (bx == 0) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < a.nblk[p]; i += 256) acc += a.part[p * a.nblk[1] + i];
+    const float s = block_sum_256(acc, red);
+    if (threadIdx.x == 0) a.losses[3 + p] = s * half / a.denom;
+  }
+  const int W = p == 0 ? SDUMC_D : SDUMC_H;
+  const int rpb = DCH / W, rows = (int)(n / W);
+  const int r1 = min(rows, (bx + 1) * rpb);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float scale = a.w[2 + p] * half / a.denom;
+  for (int r = bx * rpb + wave; r < r1; r += 4) {
+    const size_t o = (size_t)r * W;
+    crit_row<true>(a.crit, s1 + o, s0 + o, W, lane, scale, g + n + o, p == 2 ? g + o : nullptr);
+    if (p != 2)      // stream 0 detached for text_feat / text_query_feat: its gradient buffer is written with zeros
+      for (int c = lane; c < W; c += 64) g[o + c] = 0.f;
+  }
+}
 __device__ __forceinline__ void distill_partials_body(const DistillArgs a, const int bx, const int p) {
   __shared__ float red[4];
   if (bx >= a.nblk[p]) return;
+  if (a.crit != SDUMC_DISTILL_RMSE) {
+    distill_rows_partials(a, bx, p, red);
+    return;
+  }
   const float *s1, *s0;
   float* g;
   int64_t n;
@@ -489,6 +702,10 @@ __device__ __forceinline__ void distill_apply_body(const DistillArgs a, const in
     return;
   }
   if (bx >= a.nblk[p]) return;
+  if (a.crit != SDUMC_DISTILL_RMSE) {
+    distill_rows_apply(a, bx, p, red);
+    return;
+  }
   const float *s1, *s0;
   float* g;
   int64_t n;
@@ -737,15 +954,18 @@ extern "C" size_t sdumc_distill_workspace_bytes(int32_t B) {
   return (size_t)(3 * nb + 64) * sizeof(float);
 }
 
-// MSE x2 + RMSE x3 of main :137-148 (value + gradients w.r.t. the network outputs) in two launches
-extern "C" int sdumc_distill_fwd_bwd(int32_t B, float denom, const float* vals, const float* labels, const float* th,
-                                     const float* ct, const float* z, const float* weights5, const float* ssd_global,
-                                     float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses,
-                                     float* workspace, void* stream) {
+// MSE x2 + the chosen criterion x3 of main :137-148 (value + gradients w.r.t. the network outputs) in two launches.
+// distill != RMSE: ssd_global is not read (the value is a sum over local rows / denom) and pass 1 always runs.
+extern "C" int sdumc_distill_crit_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                   const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                   float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                   int32_t distill, void* stream) {
   if (B <= 0 || denom <= 0.f || !vals || !labels || !th || !ct || !z || !weights5 || !d_vals || !d_th || !d_ct || !d_z ||
-      !losses || !workspace)
+      !losses || !workspace || distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL)
     return SDUMC_EINVAL;
+  if (distill != SDUMC_DISTILL_RMSE) ssd_global = nullptr;
   DistillArgs a;
+  a.crit = distill;
   a.B = B;
   a.denom = denom;
   a.vals = vals; a.labels = labels; a.th = th; a.ct = ct; a.z = z;
@@ -770,14 +990,47 @@ extern "C" int sdumc_distill_fwd_bwd(int32_t B, float denom, const float* vals, 
   return SDUMC_OK;
 }
 
-// MSE x2 + RMSE x3 + RnC over cat(stream 0, stream 1) with the labels repeated (main :134-148): values and every gradient
+extern "C" int sdumc_distill_fwd_bwd(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                     const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                     float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses,
+                                     float* workspace, void* stream) {
+  return sdumc_distill_crit_(B, denom, vals, labels, th, ct, z, weights5, ssd_global, d_vals, d_th, d_ct, d_z, losses,
+                             workspace, SDUMC_DISTILL_RMSE, stream);
+}
+
+static int row_crit_launch(int crit, const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                           float weight, float* loss_out, float* da, float* db, void* stream) {
+  if (!a || !b || !loss_out || rows <= 0 || groups <= 0 || width <= 0 || width > ROW_MAXW || !(denom > 0.f)) return SDUMC_EINVAL;
+  if ((int64_t)rows * groups > INT32_MAX / ROW_MAXW) return SDUMC_EINVAL;
+  if (crit == CRIT_CE && (groups != 1 || db)) return SDUMC_EINVAL;
+  const float half = crit == CRIT_KL ? 0.5f : 1.f;
+  hipLaunchKernelGGL(row_crit_kernel, dim3(1), dim3(1024), 0, as_stream(stream), crit, a, b, rows * groups, width,
+                     weight * half / denom, half / denom, loss_out, da, db);
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
+}
+extern "C" int sdumc_cosine_fwd_bwd(const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                                    float weight, float* loss_out, float* da, float* db, void* stream) {
+  return row_crit_launch(CRIT_COSINE, a, b, rows, groups, width, denom, weight, loss_out, da, db, stream);
+}
+extern "C" int sdumc_kl_fwd_bwd(const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                                float weight, float* loss_out, float* da, float* db, void* stream) {
+  return row_crit_launch(CRIT_KL, a, b, rows, groups, width, denom, weight, loss_out, da, db, stream);
+}
+extern "C" int sdumc_ce_fwd_bwd(const float* a, const float* b, int32_t rows, int32_t groups, int32_t width, float denom,
+                                float weight, float* loss_out, float* da, float* db, void* stream) {
+  return row_crit_launch(CRIT_CE, a, b, rows, groups, width, denom, weight, loss_out, da, db, stream);
+}
+
+// MSE x2 + the distillation criterion x3 + RnC over cat(stream 0, stream 1) with the labels repeated (main :134-148): values and every gradient
 // w.r.t. the network outputs in two launches.  Returns 1 when the shape is not one it takes (n = 2B > 256: the sorted RnC form).
 extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
                                    const float* z, const float* rnc_feats, int32_t rd, float temperature, const float* weights6,
                                    float* d_vals, float* d_th, float* d_ct, float* d_z, float* d_rnc, float* losses,
                                    float* distill_ws, float* rnc_workspace, float* hyper, double beta1, double beta2,
-                                   void* stream) {
+                                   int32_t distill, void* stream) {
   const int n = 2 * B;
+  if (distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;
   if (B <= 0 || n > 256 || rd <= 0 || temperature <= 0.f) return 1;
   const size_t lds1 = (((size_t)rd + 3) & ~(size_t)3) * sizeof(float) + 5 * (size_t)n * sizeof(float);
   const size_t lds2 = ((size_t)n + 256) * sizeof(float);
@@ -788,6 +1041,7 @@ extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* la
   a.vals = vals; a.labels = labels; a.th = th; a.ct = ct; a.z = z;
   for (int i = 0; i < 5; ++i) a.w[i] = weights6[i];
   a.ssd_global = nullptr;
+  a.crit = distill;
   a.d_vals = d_vals; a.d_th = d_th; a.d_ct = d_ct; a.d_z = d_z;
   a.losses = losses;
   a.part = distill_ws;

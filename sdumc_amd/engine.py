@@ -335,8 +335,10 @@ class TrainStep(_OptStateMixin):
 
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
-                 bits_next=True):
-        """share: an object with .params .rng .adam_m .adam_v .hyper .losses (another TrainStep over the SAME flat_params, or
+                 bits_next=True, distill='rmse'):
+        """distill: the criterion of the three distillation pairs (text_hidden, cross_text, fused; main :148): 'rmse' (the
+        reference's line as it stands), 'cosine' (CosineSimilarityLoss4Seq) or 'kl' (KLLoss); losses[3:6] hold its values.
+        share: an object with .params .rng .adam_m .adam_v .hyper .losses (another TrainStep over the SAME flat_params, or
         FusedTrainer's run state) whose optimiser state this step uses instead of allocating its own -- steps of different
         (B, T) shapes then continue one training run.
         arena: a _StepArena sized for the largest batch of the run: workspace, input and output buffers are views into it
@@ -344,6 +346,8 @@ class TrainStep(_OptStateMixin):
         decides about planes and owns the keep-bits buffer (its shapes change from step to step: use_set / launch(next_step=)).
         planes=True: the batch installed by set_batch is RESIDENT (run many times): its bf16 planes are split once, there (planes_wanted)."""
         Ta, Tt, Tv, T4 = T
+        distill_code = _lib.distill_code(distill)
+        self.distill = distill
         self.layout = ParamLayout.get(dims[0], dims[1], dims[2])
         dev = flat_params.device
         _require_cuda(flat_params)
@@ -435,6 +439,7 @@ class TrainStep(_OptStateMixin):
         cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay = betas[0], betas[1], eps, weight_decay
         cfg.adam_m, cfg.adam_v = ptr(self.adam_m), ptr(self.adam_v)
         cfg.hyper, cfg.losses = ptr(self.hyper), ptr(self.losses)
+        cfg.distill = distill_code
         self.graph = None
         goff = lib.sdumc_step_grads_offset(C.byref(self.dims))      # the same for every shape: the bucket leads the workspace
         self.grads = self.workspace[goff:goff + 4 * self.layout.live].view(torch.float32)
@@ -749,17 +754,20 @@ class FusedTrainer:
     (sdumc_net_io.prefetch) -- and every step tells the engine the next batch's shape, so that the next keep-bits are laid out for it."""
 
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
-                 inplace=True, **step_kwargs):
-        """capacity = (B_max, (T_audio, T_text, T_video, T_feat4) maxima) of the run: ONE arena then backs every batch shape
+                 inplace=True, distill='rmse', **step_kwargs):
+        """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        capacity = (B_max, (T_audio, T_text, T_video, T_feat4) maxima) of the run: ONE arena then backs every batch shape
         (no per-shape workspace, the per-shape step is a few ctypes structs and tensor views: cache as many as you like) and
         `step_from_store` / `run_epoch` assemble batches straight into it.  Without it every cached shape owns its workspace.
         planes (arena only): None (default) = follow the store -- batches assembled from a DeviceFeatureStore(planes=True) bring their
         P3 planes along (the same gather as the fp32 rows) and the step's frame projections read them; False = never.
         inplace (default True): with such a store the batches are not gathered at all -- the step reads the store's packed tensors
         through per-batch row maps (4 bytes per frame; sdumc_net_io.row_map)."""
+        _lib.distill_code(distill)
+        self.distill = distill
         _require_cuda(flat_params)
         self.params, self.dims, self.max_cached = flat_params, tuple(dims), max(1, int(max_cached))
-        self.kw = dict(step_kwargs, lr=lr, seed=seed)
+        self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         self.state = _RunState(flat_params, lay.live, lr, seed)     # (params, rng, adam_m, adam_v, hyper, losses)
         self._steps = {}          # shape -> TrainStep, insertion order = recency
@@ -779,7 +787,7 @@ class FusedTrainer:
             self.kw.update(planes=False, bits_next=False)
 
     def _get(self, B, T):
-        key = (B,) + tuple(T)
+        key = (B,) + tuple(T) + (self.distill,)      # the criterion is part of the key: one cache never mixes criteria
         ts = self._steps.pop(key, None)
         if ts is None:
             while len(self._steps) >= self.max_cached:

@@ -1,11 +1,14 @@
-"""Drop-in replacements of the loss callables the training step uses (toolkit/utils/loss.py):
-MSELoss (:19-33), RMSELoss (:37-51), RnCLoss (:271-315).  Same call signatures, 0-dim results with
-grad; value and gradient come from the HIP kernels (sdumc_amd/csrc/loss.hip)."""
+"""Drop-in replacements of the six loss callables the driver builds (main_frame_val_text_missing.py:310-315,
+toolkit/utils/loss.py): MSELoss (:19-33), RMSELoss (:37-51), RnCLoss (:271-315), CosineSimilarityLoss4Seq (:100-119),
+KLLoss (:74-97), CELoss (:6-16).  Same constructor and call signatures, 0-dim results with grad; value and
+gradient come from the HIP kernels (sdumc_amd/csrc/loss.hip)."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from ._lib import SdumcError
+
+__all__ = ["MSELoss", "RMSELoss", "RnCLoss", "CosineSimilarityLoss4Seq", "KLLoss", "CELoss"]
 
 
 def _flat2(pred, target):
@@ -102,3 +105,73 @@ class RnCLoss(nn.Module):
     def forward(self, features, labels):
         _dev(features, labels)
         return _RnC.apply(features, labels, self.t)
+
+
+class _RowCrit(torch.autograd.Function):
+    """cosine / KL: value and the gradients to both arguments from one kernel launch."""
+
+    @staticmethod
+    def forward(ctx, a, b, fn):
+        a_, b_ = a.contiguous().float(), b.contiguous().float()
+        need = ctx.needs_input_grad
+        loss, da, db = fn(a_, b_, need_da=need[0], need_db=need[1])
+        ctx.save_for_backward(da, db)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        da, db = ctx.saved_tensors
+        return (da * g if da is not None else None), (db * g if db is not None else None), None
+
+
+def _same_2d_or_3d(name, u, v):
+    if u.dim() not in (2, 3) or u.shape != v.shape:
+        raise SdumcError(f"{name}: [B, W] or [B, G, W] inputs of one shape, not {tuple(u.shape)} and {tuple(v.shape)}")
+
+
+class CosineSimilarityLoss4Seq(nn.Module):
+    """loss.py:100-119: mean over the batch of 1 - cos(u, v); [B, G, W] inputs: the sum of that over the G groups."""
+
+    def forward(self, u, v):
+        _dev(u, v)
+        _same_2d_or_3d("CosineSimilarityLoss4Seq", u, v)
+        return _RowCrit.apply(u, v, ops.cosine_fwd_bwd)
+
+
+class KLLoss(nn.Module):
+    """loss.py:74-97: (KL(softmax(target) || softmax(pred)) + KL(softmax(pred) || softmax(target))) / 2 over the last
+    axis, reduction 'batchmean' (divided by size(0))."""
+
+    def loss(self, p, q, pad_mask=None):
+        if pad_mask is not None:
+            raise SdumcError("KLLoss: pad_mask is not built (the reference fills a 0-dim result with it)")
+        _dev(p, q)
+        _same_2d_or_3d("KLLoss", p, q)
+        return _RowCrit.apply(p, q, ops.kl_fwd_bwd)
+
+    def forward(self, pred, target):
+        return self.loss(pred, target)
+
+
+class _CE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
+        loss, dp = ops.ce_fwd_bwd(pred.contiguous().float(), target.reshape(-1).contiguous().float())
+        ctx.save_for_backward(dp)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dp,) = ctx.saved_tensors
+        return dp * g, None
+
+
+class CELoss(nn.Module):
+    """loss.py:6-16: log_softmax(pred, 1) + NLLLoss(reduction='sum') / len(pred); pred [N, C], target [N] class indices
+    of any numeric dtype (the reference calls target.long())."""
+
+    def forward(self, pred, target):
+        _dev(pred, target)
+        if pred.dim() != 2 or target.numel() != pred.shape[0]:
+            raise SdumcError(f"CELoss: pred [N, C] and N targets, not {tuple(pred.shape)} and {tuple(target.shape)}")
+        return _CE.apply(pred, target)

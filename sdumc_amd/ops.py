@@ -499,6 +499,39 @@ def rmse_fwd_bwd(a, b, weight=1.0, ssd_global=None, numel_global=None, need_db=T
     return loss, da, db
 
 
+def _row_crit(fn, name, a, b, weight, denom, need_da, need_db):
+    if a.dim() not in (2, 3) or a.shape != b.shape:
+        raise _lib.SdumcError(f"{name}: [B, W] or [B, G, W] inputs of one shape, not {tuple(a.shape)} and {tuple(b.shape)}")
+    rows, groups, width = a.shape[0], (a.shape[1] if a.dim() == 3 else 1), a.shape[-1]
+    loss = torch.empty(1, device=a.device)
+    da = torch.empty_like(a) if need_da else None
+    db = torch.empty_like(b) if need_db else None
+    check(fn(ptr(a), ptr(b), rows, groups, width, float(denom or rows), weight, ptr(loss), ptr(da), ptr(db), _st()), name)
+    return loss, da, db
+
+
+def cosine_fwd_bwd(a, b, weight=1.0, denom=None, need_da=True, need_db=True):
+    """CosineSimilarityLoss4Seq (loss.py:100-119) of a, b [B, W] or [B, G, W] (fp32, contiguous): loss [1], da, db."""
+    return _row_crit(lib.sdumc_cosine_fwd_bwd, "sdumc_cosine_fwd_bwd", a, b, weight, denom, need_da, need_db)
+
+
+def kl_fwd_bwd(a, b, weight=1.0, denom=None, need_da=True, need_db=True):
+    """KLLoss (loss.py:74-97) of a, b [B, W] or [B, G, W] (fp32, contiguous): loss [1], da, db."""
+    return _row_crit(lib.sdumc_kl_fwd_bwd, "sdumc_kl_fwd_bwd", a, b, weight, denom, need_da, need_db)
+
+
+def ce_fwd_bwd(logits, target, weight=1.0, denom=None):
+    """CELoss (loss.py:6-16): logits [N, C] fp32, target [N] class indices held as fp32: loss [1], dlogits."""
+    if logits.dim() != 2 or target.numel() != logits.shape[0]:
+        raise _lib.SdumcError(f"sdumc_ce_fwd_bwd: logits [N, C] and N targets, not {tuple(logits.shape)} and {tuple(target.shape)}")
+    rows, width = logits.shape
+    loss = torch.empty(1, device=logits.device)
+    dl = torch.empty_like(logits)
+    check(lib.sdumc_ce_fwd_bwd(ptr(logits), ptr(target), rows, 1, width, float(denom or rows), weight, ptr(loss), ptr(dl),
+                               None, _st()), "sdumc_ce_fwd_bwd")
+    return loss, dl
+
+
 def rnc_fwd_bwd(feats, labels, temperature=2.0, weight=1.0, row0=0, rows_local=None):
     n, dim = feats.shape
     rows_local = n if rows_local is None else rows_local

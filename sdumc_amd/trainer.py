@@ -34,8 +34,11 @@ class HipBackend:
     """Per-rank compute on one MI355X through the C ABI."""
 
     def __init__(self, flat_params, B, T, dims, weights, lr, betas, eps, weight_decay, seed, sample0, B_global,
-                 bf16=False, share=None, planes=False):
-        """share: the run state (engine._RunState: rng, Adam moments, hyper, losses, gradient bucket) of the training run
+                 bf16=False, share=None, planes=False, distill='rmse'):
+        """distill: 'rmse' | 'cosine' | 'kl', the criterion of the three distillation pairs (engine.TrainStep).  Cosine and KL
+        are sums over rows / B_global: the rank's loss entries 3..5 are then LOCAL shares like the MSE entries, and the
+        sums of squares of the exchange record are carried but not read.
+        share: the run state (engine._RunState: rng, Adam moments, hyper, losses, gradient bucket) of the training run
         this backend belongs to.  planes=True: the batches installed by set_batch are RESIDENT (each runs many steps): their bf16
         planes are split once per set_batch (engine.planes_wanted); default off -- a fresh batch per step would pay the split for one use.
         The reference's loader pads every batch to its own max T and ends an epoch on a short
@@ -86,6 +89,7 @@ class HipBackend:
         cfg.labels, cfg.adam_m, cfg.adam_v = _lib.ptr(self.labels), _lib.ptr(self.adam_m), _lib.ptr(self.adam_v)
         cfg.hyper, cfg.losses = _lib.ptr(self.hyper), _lib.ptr(self.losses)
         cfg.B_global = B_global
+        cfg.distill = _lib.distill_code(distill)
         self.cfg = cfg
         g = _lib.NetGrads()
         g.d_vals, g.d_fused, g.d_rnc = _lib.ptr(self.d_vals), _lib.ptr(self.d_fused), _lib.ptr(self.d_rnc)
@@ -209,7 +213,7 @@ class DataParallelStep:
 
     def __init__(self, flat_params, B, T, dims, weights=(0.5, 0.5, 0.1, 0.7, 0.1, 0.8), lr=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=1e-5, seed=0, exact=True, backend_factory=None, bf16=False,
-                 force_collectives=False, planes=False):
+                 force_collectives=False, planes=False, distill='rmse'):
         import collections
         import inspect
         self.rank, self.world = _world()
@@ -223,6 +227,11 @@ class DataParallelStep:
         extra = {"bf16": True} if bf16 else {}
         if planes:
             extra["planes"] = True      # (resident batches: HipBackend)
+        from ._lib import distill_code
+        distill_code(distill)
+        self.distill = distill
+        if distill != 'rmse':
+            extra["distill"] = distill  # (a backend without the argument refuses it: no silent RMSE)
         # One backend per batch shape (B, T_audio, T_text, T_video, T_feat4), least recently used first out, all continuing
         # ONE run state: the reference pads every batch to its own maximum and ends an epoch on a short batch.
         self._shares = "share" in inspect.signature(factory).parameters
@@ -370,8 +379,9 @@ class DataParallelStep:
                                   "call sdumc_chain_cluster_reset_error() and repeat them, e.g. with sdumc_set_chain_cluster(0)")
         l = losses.clone()
         if self.collect and self.exact:
-            mse = l[1:3].clone()
+            n = 3 if self.distill == 'rmse' else 6          # cosine / KL entries are local sums / B_global too
+            mse = l[1:n].clone()
             dist.all_reduce(mse)                            # MSE terms are local sums / B_global
-            l[1:3] = mse
+            l[1:n] = mse
             l[0] = sum(w * v for w, v in zip(self.weights, l[1:7]))
         return l
