@@ -618,6 +618,36 @@ int sdumc_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
                     float* hyper, float beta1, float beta2, float eps, float weight_decay,
                     float grad_scale, void* stream);
 
+/* The same update over PER-PARAMETER tensors in one launch: what torch.optim.Adam(model.parameters(), ...).step() of
+ * main :317 does when the gradients are the separate tensors autograd left in p.grad (sdumc_amd/optim.py).
+ * Segment i updates param[0 .. n) from grad[0 .. n) with the moments exp_avg / exp_avg_sq [state_offset .. state_offset + n)
+ * of two flat buffers of state_len floats.  param and grad need only their natural 4-byte alignment (views at any element
+ * offset of a larger tensor): a segment whose four addresses are all 16-byte aligned moves 16 bytes per lane, any other one
+ * float per lane; same arithmetic, bit for bit, either way and as the single-bucket entry above.  Segments must not overlap.
+ * hyper advances ONCE per call, as above.  The segments travel to the device BY VALUE in the kernel arguments (no copy, no
+ * synchronisation, no allocation): SDUMC_ADAM_MAX_SEGS per launch, a longer list takes further launches of the same kernel.
+ * SDUMC_EINVAL (before anything is launched): null pointers, nseg <= 0, a segment with n <= 0 or state_offset < 0 or
+ * state_offset + n > state_len. */
+#define SDUMC_ADAM_MAX_SEGS 96     /* sizeof(sdumc_adam_table) + the other arguments stay below HIP's 4 KB of kernel arguments */
+#define SDUMC_ADAM_CHUNK 1024      /* elements per 256-thread workgroup */
+typedef struct sdumc_adam_seg {
+  float* param;
+  const float* grad;
+  int64_t state_offset;    /* floats into exp_avg / exp_avg_sq */
+  int64_t n;               /* elements */
+} sdumc_adam_seg;
+/* one launch's kernel argument: its segments and the running count of workgroups behind each of them (workgroup b works on
+ * the segment s with block_end[s - 1] <= b < block_end[s], chunk b - block_end[s - 1]); filled by the call */
+typedef struct sdumc_adam_table {
+  sdumc_adam_seg seg[SDUMC_ADAM_MAX_SEGS];
+  uint32_t block_end[SDUMC_ADAM_MAX_SEGS];
+  int32_t nseg;
+  int32_t reserved;
+} sdumc_adam_table;
+int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                     float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                     void* stream);
+
 /* Batch assembly from a device-resident packed feature store = the collater's padding
  * (toolkit/utils/read_data.py:139-151, :223-248; toolkit/data/feat_data.py:232-253) on the GPU:
  * out[b, t, :] = packed[start[b] + t, :] for t < len[b], zero beyond, out is [B, Tmax, d].

@@ -222,6 +222,18 @@ class CopySeg(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
+ADAM_MAX_SEGS = 96
+
+
+class AdamSeg(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state_offset", C.c_int64), ("n", C.c_int64)]
+
+
+class AdamTable(C.Structure):      # one launch's kernel argument (filled by sdumc_adam_multi; mirrored for the size checks)
+    _fields_ = [("seg", AdamSeg * ADAM_MAX_SEGS), ("block_end", C.c_uint32 * ADAM_MAX_SEGS), ("nseg", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "sdumc_copy2d_multi": (C.c_int, [C.POINTER(CopySeg), C.c_int32, C.c_void_p]),
     "sdumc_profile_enable": (C.c_int, [C.c_int]),
@@ -288,6 +300,8 @@ _SIGS = {
     "sdumc_rnc_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sdumc_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "sdumc_adam_multi": (C.c_int, [C.POINTER(AdamSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sdumc_copy2d": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sdumc_axpy2d": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "sdumc_gather_pad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -2,6 +2,9 @@
 // (main_frame_val_text_missing.py:317) as ONE launch over the flat live-parameter bucket.
 // Dead parameters (never receive a gradient) live outside the bucket and are
 // never touched, exactly like torch.optim.Adam skips grad-None parameters.
+// sdumc_adam_multi is the same update for the loop that keeps `optimizer = optim.Adam(model.parameters(), ...)` of
+// main_frame_val_text_missing.py:317 as a line of its own (sdumc_amd/optim.py): ONE launch over the per-parameter gradient
+// tensors autograd left in p.grad, found through a segment table that travels in the kernel arguments.
 //
 // hyper (device, 4 floats): [0] lr (host-written, LambdaLR value)   [1] step count t (kernel-incremented)
 //                           [2] lr / (1 - beta1^t)                  [3] sqrt(1 - beta2^t)
@@ -16,6 +19,17 @@ __global__ void adam_hyper_kernel(float* hyper, double beta1, double beta2) {
   hyper[1] = (float)t;
   hyper[2] = (float)((double)hyper[0] / (1.0 - pow(beta1, t)));
   hyper[3] = (float)sqrt(1.0 - pow(beta2, t));
+}
+
+// The update of ONE element, shared by the flat-bucket kernel and the per-parameter one (same expression = same bits):
+// coupled L2, exp_avg.lerp_(grad, 1-beta1), exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2), denom = sqrt(v)/bc2_sqrt + eps
+__device__ __forceinline__ void adam_update(float& p, const float g, float& m, float& v, const float step_size,
+                                            const float bc2_sqrt, const float beta1, const float beta2, const float eps,
+                                            const float wd, const float gscale) {
+  const float ge = g * gscale + wd * p;
+  m = m + (ge - m) * (1.f - beta1);
+  v = v * beta2 + (1.f - beta2) * ge * ge;
+  p = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -36,10 +50,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float ge = gg[e] * gscale + wd * pp[e];
-      mm[e] = mm[e] + (ge - mm[e]) * (1.f - beta1);           // exp_avg.lerp_(grad, 1-beta1)
-      vv[e] = vv[e] * beta2 + (1.f - beta2) * ge * ge;        // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
-      pp[e] = pp[e] - step_size * (mm[e] / (sqrtf(vv[e]) / bc2_sqrt + eps));
+      float pe = pp[e], me = mm[e], ve = vv[e];
+      adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      pp[e] = pe; mm[e] = me; vv[e] = ve;
     }
     reinterpret_cast<f32x4*>(p)[i] = pp;
     reinterpret_cast<f32x4*>(m)[i] = mm;
@@ -55,12 +68,60 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       // fail loudly: a clustered utterance-level kernel whose spin ran into its cap finished with wrong data
       if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
     }
-    for (int64_t t = n4 * 4; t < n && !poisoned; ++t) {
-      const float ge = g[t] * gscale + wd * p[t];
-      m[t] = m[t] + (ge - m[t]) * (1.f - beta1);
-      v[t] = v[t] * beta2 + (1.f - beta2) * ge * ge;
-      p[t] = p[t] - step_size * (m[t] / (sqrtf(v[t]) / bc2_sqrt + eps));
+    for (int64_t t = n4 * 4; t < n && !poisoned; ++t)
+      adam_update(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+  }
+}
+
+// The same update over per-parameter tensors (sdumc_adam_multi): workgroup b finds its (segment, chunk of SDUMC_ADAM_CHUNK
+// elements) in the table's running workgroup counts -- the table is a kernel argument, every lookup is a scalar load with a
+// wave-uniform index.  A chunk starts a multiple of 4 KiB behind its segment's base, so the segment's alignment is the chunk's:
+// 16 bytes per lane where param, grad and both moments are 16-byte aligned, one float per lane (stride 256, coalesced) elsewhere.
+__global__ __launch_bounds__(256) void adam_multi_kernel(const sdumc_adam_table tb, float* __restrict__ m_all,
+                                                         float* __restrict__ v_all, const float* hyper, float beta1,
+                                                         float beta2, float eps, float wd, float gscale,
+                                                         const int32_t* chain_err) {
+  if (chain_err != nullptr && *chain_err != 0) return;     // garbage gradients (see adam_kernel): NOTHING is applied
+  const float step_size = hyper[2], bc2_sqrt = hyper[3];
+  const uint32_t b = blockIdx.x;
+  int lo = 0, hi = tb.nseg - 1;
+  while (lo < hi) {                                         // first segment with block_end > b
+    const int mid = (lo + hi) >> 1;
+    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  const sdumc_adam_seg sg = tb.seg[lo];
+  const uint32_t b0 = lo > 0 ? tb.block_end[lo - 1] : 0u;
+  const int64_t base = (int64_t)(b - b0) * SDUMC_ADAM_CHUNK;
+  const int64_t left = sg.n - base;
+  const int cnt = left < SDUMC_ADAM_CHUNK ? (int)left : SDUMC_ADAM_CHUNK;
+  float* __restrict__ p = sg.param + base;
+  const float* __restrict__ g = sg.grad + base;
+  float* __restrict__ m = m_all + sg.state_offset + base;
+  float* __restrict__ v = v_all + sg.state_offset + base;
+  const int tid = threadIdx.x;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                         reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  if (aligned) {
+    const int e0 = 4 * tid;
+    if (e0 + 4 <= cnt) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
+      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
+      f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
+      f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + e0) = pp;
+      *reinterpret_cast<f32x4*>(m + e0) = mm;
+      *reinterpret_cast<f32x4*>(v + e0) = vv;
+    } else {
+      for (int e = e0; e < cnt; ++e) adam_update(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
     }
+  } else {
+    for (int e = tid; e < cnt; e += 256) adam_update(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
   }
 }
 
@@ -104,6 +165,44 @@ extern "C" int sdumc_adam_step(float* param, const float* grad, float* exp_avg, 
   if (rc) return rc;
   return sdumc_adam_apply_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
                            0u, nullptr, stream);
+}
+
+extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                                float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                void* stream) {
+  static_assert(sizeof(sdumc_adam_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!segs || nseg <= 0 || !exp_avg || !exp_avg_sq || !hyper || state_len <= 0) return SDUMC_EINVAL;
+  uint64_t blocks_of_launch = 0;
+  for (int32_t i = 0; i < nseg; ++i) {
+    const sdumc_adam_seg& s = segs[i];
+    if (!s.param || !s.grad || s.n <= 0 || s.state_offset < 0 || s.state_offset > state_len || s.n > state_len - s.state_offset)
+      return SDUMC_EINVAL;
+    if (i % SDUMC_ADAM_MAX_SEGS == 0) blocks_of_launch = 0;
+    blocks_of_launch += (uint64_t)((s.n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
+    if (blocks_of_launch > 0x7fffffffull) return SDUMC_EINVAL;     // (one launch's grid)
+  }
+  int rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
+  if (rc) return rc;
+  const int32_t* chain_err = sdumc_chain_cluster_err_ptr_();
+  for (int32_t s0 = 0; s0 < nseg; s0 += SDUMC_ADAM_MAX_SEGS) {
+    sdumc_adam_table tb;
+    tb.nseg = nseg - s0 < SDUMC_ADAM_MAX_SEGS ? nseg - s0 : SDUMC_ADAM_MAX_SEGS;
+    tb.reserved = 0;
+    uint32_t blocks = 0;
+    for (int32_t i = 0; i < SDUMC_ADAM_MAX_SEGS; ++i) {
+      if (i < tb.nseg) {
+        tb.seg[i] = segs[s0 + i];
+        blocks += (uint32_t)((tb.seg[i].n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
+      } else {
+        tb.seg[i] = sdumc_adam_seg{nullptr, nullptr, 0, 0};
+      }
+      tb.block_end[i] = blocks;
+    }
+    hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
+                       beta2, eps, weight_decay, grad_scale, chain_err);
+    SDUMC_CHECK_LAUNCH();
+  }
+  return SDUMC_OK;
 }
 
 // One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load

@@ -563,6 +563,26 @@ def adam_step(param, grad, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight
                               weight_decay, grad_scale, _st()), "sdumc_adam_step")
 
 
+def adam_segments(params, grads, state_offsets):
+    """The ctypes segment table of adam_multi (kept by a caller that steps the same tensors again and again)."""
+    segs = (_lib.AdamSeg * max(1, len(params)))()
+    for s, p, g, off in zip(segs, params, grads, state_offsets):
+        s.param, s.grad, s.state_offset, s.n = p.data_ptr(), g.data_ptr(), off, p.numel()
+    return segs
+
+
+def adam_multi(params, grads, m, v, state_offsets, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-5,
+               grad_scale=1.0, segs=None):
+    """adam_step over per-parameter tensors in one launch: params[i] / grads[i] (contiguous fp32, any 4-byte-aligned
+    address) with the moments m / v [state_offsets[i] : + numel] of two flat buffers; hyper advances once."""
+    if segs is None:
+        segs = adam_segments(params, grads, state_offsets)
+    if v.numel() != m.numel():
+        raise _lib.SdumcError("adam_multi: the two moment buffers must have the same length")
+    check(lib.sdumc_adam_multi(segs, len(params), ptr(m), ptr(v), m.numel(), ptr(hyper), beta1, beta2, eps, weight_decay,
+                               grad_scale, _st()), "sdumc_adam_multi")
+
+
 # ---- generic MHA / Transformer-encoder pieces (transformer.hip) ------------------------------------
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
     width = x.shape[-1]
