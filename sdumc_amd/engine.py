@@ -3,6 +3,7 @@
 PyTorch-ROCm is used for device memory and streams only.  Everything numeric
 happens in libsdumc_hip.so; there is no CPU or torch fallback.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -105,6 +106,11 @@ def p3_split_into(src, dst):
     return dst
 
 
+def _planes_buffer(rows, d, device):
+    """uninitialised uint8 [rows, 6 d]: where the three bf16 planes of an fp32 [rows, d] tensor go (p3_split_into, the store's gather)"""
+    return torch.empty(rows, 6 * d, dtype=torch.uint8, device=device)
+
+
 def make_dims(B, streams, Ta, Tv, Tt, dims, train, sample0=0, p_mlp=P_MLP, bf16=False):
     d = _lib.NetDims()
     d.B, d.streams, d.Ta, d.Tv = B, streams, Ta, Tv
@@ -179,6 +185,22 @@ def _lengths_arg(lengths, B, n, device):
     return out
 
 
+def _copy_lengths(io, own, new, B):
+    """set_lengths of a NetCall / TrainStep: `new` (_lengths_arg's tensors, or None = extension off) is copied into the object's OWN
+    [B] int32 buffers `own` -- allocated on first use, the same addresses from then on (a captured graph keeps reading them) -- and
+    io.lengths points at them (None: at nothing).  Returns the own buffers."""
+    for i in range(4):
+        io.lengths[i] = None
+    if new is None:
+        return own
+    if own is None:
+        own = [torch.empty(B, dtype=torch.int32, device=t.device) for t in new]
+    for i, (dst, src) in enumerate(zip(own, new)):
+        io.lengths[i] = ptr(dst)
+        dst.copy_(src, non_blocking=True)
+    return own
+
+
 class NetCall:
     """One network invocation (1 or 2 streams): owns workspace + outputs, supports backward.
     `lengths` (extension, default None = the reference's behaviour): per-modality valid frame counts
@@ -238,7 +260,7 @@ class NetCall:
         io.ctx = ctx.handle if ctx is not None else None
         self._planes = None
         if planes_wanted(planes, (da, dt, dv), bf16):      # bf16-plane copies of the features, split once for the life of this call object
-            mk = lambda t: torch.empty(t.shape[0] * t.shape[1], 6 * t.shape[2], dtype=torch.uint8, device=dev)
+            mk = lambda t: _planes_buffer(t.shape[0] * t.shape[1], t.shape[2], dev)
             self._planes = (mk(audio), mk(video), [mk(t) for t in texts])
             io.audio_p3, io.video_p3 = ptr(self._planes[0]), ptr(self._planes[1])
             for i, t in enumerate(self._planes[2]):
@@ -268,23 +290,11 @@ class NetCall:
 
     def set_lengths(self, lengths):
         """Key-padding extension for the next forward: per-modality valid frame counts, or None = the reference's behaviour."""
-        n = 4 if self.S == 2 else 3
-        new = _lengths_arg(lengths, self.B, n, self.vals.device)
-        if new is None:
-            self._lengths = None
-            for i in range(4):
-                self.io.lengths[i] = None
-            return
-        if self._lengths is None:
-            self._lengths = [torch.empty(self.B, dtype=torch.int32, device=self.vals.device) for _ in range(n)]
-            for i, t in enumerate(self._lengths):
-                self.io.lengths[i] = ptr(t)
-        for dst, src in zip(self._lengths, new):
-            dst.copy_(src, non_blocking=True)
+        new = _lengths_arg(lengths, self.B, 4 if self.S == 2 else 3, self.vals.device)
+        self._lengths = _copy_lengths(self.io, self._lengths, new, self.B)
 
     def forward(self):
         check(lib.sdumc_net_forward(C.byref(self.dims), C.byref(self.io), _lib.current_stream()), "sdumc_net_forward")
-        self._phase_used = self.io.bits_phase      # (the backward of this call reads the set the forward read)
         return self.vals, self.fused, self.rnc, self.text_hidden, self.cross_text
 
     def next_call(self):
@@ -328,10 +338,27 @@ class _OptStateMixin:
         self.rng.set_call(2 * step)
 
 
+_NO4 = (None,) * 4
+
+# One input source of a TrainStep (TrainStep._bind): feats = the (audio, text, video, feat4) tensors the step reads -- padded [B, T, d]
+# batches, or a store's packed [rows, d] tensors when maps is given --, planes = their four bf16-plane tensors or None, maps = four
+# int32 row maps or None, store_rows = the packed tensors' row counts (0 without maps), labels [B].  The record's references are what
+# keeps a borrowed batch alive.
+_Source = collections.namedtuple("_Source", "feats planes maps store_rows labels")
+
+
 class TrainStep(_OptStateMixin):
     """The fused two-stream self-distillation step (main :119-150) on one GPU:
     forward(both streams) -> 6 losses -> backward -> Adam, ~150 launches on one stream,
-    optionally captured into a hipGraph (torch.cuda.CUDAGraph) and replayed."""
+    optionally captured into a hipGraph (torch.cuda.CUDAGraph) and replayed.
+
+    Inputs: the step reads ONE bound source at a time, installed by set_batch (a copy into the step's writable home), use_set (an input
+    set of the arena), use_store (a DeviceFeatureStore in place, through row maps) or use_batch (the caller's tensors, zero-copy); whether
+    planes are read is a property of what is bound.  The home is the step's own buffers, or with an arena the padded views of the set
+    last named by use_set / use_store (set 0 at first); set_batch binds it first when something else is bound, and splits its planes when
+    it has some.  A step without an arena starts bound to its own buffers; an arena step starts unbound (no padded buffer is touched) and
+    launch() refuses until a batch is installed.  set_lengths copies into step-owned buffers, use_lengths points at the caller's: neither
+    writes through the other's tensors."""
 
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
@@ -365,15 +392,11 @@ class TrainStep(_OptStateMixin):
         fdt = torch.bfloat16 if self.dims.bf16 == 2 else torch.float32      # dtype the features are held in
         self.feature_dtype = fdt
         self._arena = arena
-        self._lengths = None      # key-padding extension off (set_lengths / use_lengths)
-        self._use_planes = False
-        self._borrowed = None     # the caller's tensors of a zero-copy hand-over (use_batch)
-        self._set = 0
+        self._lengths = None      # set_lengths' own [B] int32 buffers, allocated on first use
         io = _lib.NetIO()
         self.io = io
         cfg = _lib.StepCfg()
         self.cfg = cfg
-        self._planes = None
         self._bits_next = None
         if arena is not None:
             if arena.feature_dtype != fdt:
@@ -387,32 +410,26 @@ class TrainStep(_OptStateMixin):
             self.rnc = arena.outs[2][:V * RNC_DIM].view(V, RNC_DIM)
             self.text_hidden = arena.outs[3][:V * D].view(V, D)
             self.cross_text = arena.outs[4][:V * NQ * H].view(V, NQ, H)
-            self._views = {}
-            self.use_set(0)
+            # the home is named, not built: (set, planes wanted) -> _Source on first need (_set_source keeps them); nothing is bound yet
+            self._home, self._sources = (0, True), {}
+            self._bind(None)
             if arena.bits is not None and train:
                 io.bits_next, io.bits_next_bytes = ptr(arena.bits), arena.bits.numel()
         else:
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self.audio = torch.empty(B, Ta, dims[0], device=dev, dtype=fdt)
-            self.text = torch.empty(B, Tt, dims[1], device=dev, dtype=fdt)
-            self.video = torch.empty(B, Tv, dims[2], device=dev, dtype=fdt)
-            self.feat4 = torch.empty(B, T4, dims[1], device=dev, dtype=fdt)
-            self.labels = torch.empty(B, device=dev)
+            feats = tuple(torch.empty(B, t, d, device=dev, dtype=fdt) for t, d in zip(self.T, self._fdims))
             self.vals = torch.empty(V, 1, device=dev)
             self.fused = torch.empty(V, H, device=dev)
             self.rnc = torch.empty(V, RNC_DIM, device=dev)
             self.text_hidden = torch.empty(V, D, device=dev)
             self.cross_text = torch.empty(V, NQ, H, device=dev)
-            io.audio, io.video = ptr(self.audio), ptr(self.video)
-            io.text[0], io.text[1] = ptr(self.text), ptr(self.feat4)
-            cfg.labels = ptr(self.labels)
             # fp32 storage, a RESIDENT batch (planes=True): bf16-plane copies of the four feature tensors, split once by set_batch --
             # 1.5x the features' bytes on top of them
+            own_planes = None
             if planes_wanted(planes, dims, bf16):
-                self._use_planes = True
-                self._planes = [torch.empty(t.shape[0] * t.shape[1], 6 * t.shape[2], dtype=torch.uint8, device=dev)
-                                for t in (self.audio, self.text, self.video, self.feat4)]
-                io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in self._planes)
+                own_planes = [_planes_buffer(B * t, d, dev) for t, d in zip(self.T, self._fdims)]
+            self._home = _Source(feats, own_planes, None, (0,) * 4, torch.empty(B, device=dev))      # the step's own buffers
+            self._bind(self._home)
             # fp32 train steps: a buffer of its own for the NEXT step's keep-bits (generated in this step's idle middle, found at the next
             # step's head under its {seed, call, shape} tag; bit-identical masks) -- not in the workspace: it must survive whatever else
             # runs between two steps of this shape
@@ -446,33 +463,46 @@ class TrainStep(_OptStateMixin):
         if arena is None:
             self.grads.zero_()      # alignment padding between tensors is never written by the kernels (an arena zeroes it once)
 
+    def _bind(self, src):
+        """Installs `src` (a _Source; None = nothing: launch() then refuses) as what the step reads.  The ONLY code that writes the
+        feature, plane, row-map and label pointers of io / cfg and the step's .audio .text .video .feat4 .labels."""
+        self._src = src
+        feats, planes, maps, rows, labels = src if src is not None else (_NO4, None, None, (0,) * 4, None)
+        self.audio, self.text, self.video, self.feat4 = feats
+        self.labels = labels
+        io = self.io
+        io.audio, io.text[0], io.video, io.text[1] = (ptr(t) for t in feats)
+        io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in planes or _NO4)
+        for i, m in enumerate(maps or _NO4):
+            io.row_map[i] = ptr(m)
+            io.store_rows[i] = rows[i]
+        self.cfg.labels = ptr(labels)
+
+    @property
+    def _planes(self):
+        """the plane tensors the step reads now (None: the bound source has none)"""
+        return self._src.planes if self._src is not None else None
+
+    def _set_source(self, k, planes):
+        """Arena steps: input set `k` as a source -- its padded buffers viewed at this step's shape, with the set's planes when they
+        are wanted and exist.  Built once per (set, planes): set_batch tells by identity whether its home is what is bound."""
+        st = self._arena.sets[k]
+        key = (k, bool(planes) and st.planes is not None)
+        src = self._sources.get(key)
+        if src is None:
+            B, T, fd = self.B, self.T, self._fdims
+            feats = tuple(st.inputs[i][:B * T[i] * fd[i]].view(B, T[i], fd[i]) for i in range(4))
+            src = self._sources[key] = _Source(feats, st.planes if key[1] else None, None, (0,) * 4, st.labels[:B])
+        return src
+
     def use_set(self, k, planes=True):
         """Arena steps: read the batch held in input set `k` of the arena (FusedTrainer alternates two sets -- the next batch is
         assembled in the other one while this step runs; bench.py rotates K resident batches).  planes=False: this batch has no
         planes in the set (fresh tensors handed to step(): splitting them for one use costs more than it saves).  Pointers only."""
-        a = self._arena
-        if a is None:
+        if self._arena is None:
             raise _lib.SdumcError("use_set: this step owns its input buffers (no arena)")
-        st = a.sets[k]
-        v = self._views.get(k)
-        if v is None:
-            B, T, fd = self.B, self.T, self._fdims
-            v = tuple(st.inputs[i][:B * T[i] * fd[i]].view(B, T[i], fd[i]) for i in range(4)) + (st.labels[:B],)
-            self._views[k] = v
-        self.audio, self.text, self.video, self.feat4, self.labels = v
-        io = self.io
-        io.audio, io.text[0], io.video, io.text[1] = (ptr(t) for t in st.inputs)
-        for i in range(4):
-            io.row_map[i] = None
-            io.store_rows[i] = 0
-        self._use_planes = bool(planes) and st.planes is not None
-        if self._use_planes:
-            io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in st.planes)
-        else:
-            io.audio_p3 = io.video_p3 = io.text_p3[0] = io.text_p3[1] = None
-        self.cfg.labels = ptr(st.labels)
-        self._set = k
-        self._borrowed = None
+        self._home = (k, planes)
+        self._bind(self._set_source(k, planes))
         return self
 
     def use_store(self, store, k):
@@ -484,40 +514,25 @@ class TrainStep(_OptStateMixin):
         if a is None or self.dims.bf16 == 1 or (not hf and store.packed_p3 is None) or store.packed['audio'].dtype != self.feature_dtype:
             raise _lib.SdumcError("use_store: an arena step in fp32 storage with a store that holds planes, or in bf16 storage with a bf16 store")
         st = a.sets[k]
-        io = self.io
-        pk = store.packed
-        io.audio, io.text[0], io.video, io.text[1] = ptr(pk['audio']), ptr(pk['text']), ptr(pk['video']), ptr(pk['feat4'])
-        if not hf:
-            p3 = store.packed_p3
-            io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = ptr(p3['audio']), ptr(p3['text']), ptr(p3['video']), ptr(p3['feat4'])
-        maps = st.ensure_maps()
-        for i, m in enumerate(('audio', 'text', 'video', 'feat4')):
-            io.row_map[i] = ptr(maps[i])
-            io.store_rows[i] = int(pk[m].shape[0])
-        self.labels = st.labels[:self.B]
-        self.cfg.labels = ptr(st.labels)
-        self._use_planes, self._set = not hf, k
-        self._borrowed = None
+        mods = ('audio', 'text', 'video', 'feat4')
+        feats = tuple(store.packed[m] for m in mods)
+        planes = None if hf else tuple(store.packed_p3[m] for m in mods)
+        self._home = (k, True)
+        self._bind(_Source(feats, planes, st.ensure_maps(), tuple(int(t.shape[0]) for t in feats), st.labels[:self.B]))
         return self
 
-    def _point_lengths(self, tensors):
-        for i in range(4):
-            self.io.lengths[i] = ptr(tensors[i]) if tensors is not None else None
-
     def set_batch(self, audio, text, video, feat4, labels):
-        """Copies one batch into the step's resident input buffers (shapes are fixed per TrainStep); in bf16-storage mode the
-        buffers are bf16 and fp32 inputs are rounded by the copy.  With planes (a resident batch) the bf16 planes are split here."""
-        self._restore_own_inputs()
-        self.audio.copy_(audio, non_blocking=True)
-        self.text.copy_(text, non_blocking=True)
-        self.video.copy_(video, non_blocking=True)
-        self.feat4.copy_(feat4, non_blocking=True)
-        self.labels.copy_(labels.reshape(-1), non_blocking=True)
-        planes = None
-        if self._use_planes:
-            planes = self._planes if self._arena is None else self._arena.sets[self._set].planes
-        if planes is not None:
-            for src, dst in zip((self.audio, self.text, self.video, self.feat4), planes):
+        """Copies one batch into the step's writable home (shapes are fixed per TrainStep; the class docstring says what the home
+        is), binding it first when the step reads something else; in bf16-storage mode the buffers are bf16 and fp32 inputs are rounded
+        by the copy.  With planes (a resident batch) the bf16 planes are split here."""
+        home = self._home if self._arena is None else self._set_source(*self._home)
+        if self._src is not home:
+            self._bind(home)
+        for dst, src in zip(home.feats, (audio, text, video, feat4)):
+            dst.copy_(src, non_blocking=True)
+        home.labels.copy_(labels.reshape(-1), non_blocking=True)
+        if home.planes is not None:
+            for src, dst in zip(home.feats, home.planes):
                 p3_split_into(src, dst)
 
     def use_batch(self, audio, text, video, feat4, labels):
@@ -537,54 +552,24 @@ class TrainStep(_OptStateMixin):
         if not ok:
             self.set_batch(audio, text, video, feat4, labels)
             return False
-        io = self.io
-        io.audio, io.text[0], io.video, io.text[1] = ptr(audio), ptr(text), ptr(video), ptr(feat4)
-        io.audio_p3 = io.video_p3 = io.text_p3[0] = io.text_p3[1] = None      # (a fresh batch: no planes to split for one use)
-        for i in range(4):
-            io.row_map[i] = None
-            io.store_rows[i] = 0
-        self.cfg.labels = ptr(labels.reshape(-1))
-        self._borrowed = (audio, text, video, feat4, labels)
-        self._use_planes = False
+        self._bind(_Source(ts, None, None, (0,) * 4, labels.reshape(-1)))      # (a fresh batch: no planes to split for one use)
         return True
-
-    def _restore_own_inputs(self):
-        """after use_batch: point the step back at its own input buffers (set_batch writes those)"""
-        if self._borrowed is None:
-            return
-        self._borrowed = None
-        if self._arena is not None:
-            self.use_set(self._set)
-            return
-        io = self.io
-        io.audio, io.video = ptr(self.audio), ptr(self.video)
-        io.text[0], io.text[1] = ptr(self.text), ptr(self.feat4)
-        self.cfg.labels = ptr(self.labels)
-        if self._planes is not None:
-            io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in self._planes)
-            self._use_planes = True
 
     def set_lengths(self, lengths):
         """Key-padding extension: (audio, text, video, feat4) valid frame counts of the current batch, or None to go back
         to the reference's behaviour (padded frames take part in the softmax)."""
         new = _lengths_arg(lengths, self.B, 4, self.params.device)
-        if self.graph is not None and (new is None) != (self._lengths is None):
+        on = self.io.lengths[0] is not None
+        if self.graph is not None and (new is None) == on:
             raise _lib.SdumcError("the captured hipGraph was recorded with the key-padding extension "
-                                  + ("on" if self._lengths is not None else "off") + ": switch it before capture()")
-        if new is None:
-            self._lengths = None
-            self._point_lengths(None)
-            return
-        if self._lengths is None:
-            self._lengths = [torch.empty(self.B, dtype=torch.int32, device=self.params.device) for _ in range(4)]
-        self._point_lengths(self._lengths)
-        for dst, src in zip(self._lengths, new):
-            dst.copy_(src, non_blocking=True)      # resident buffers: a captured graph keeps reading the same addresses
+                                  + ("on" if on else "off") + ": switch it before capture()")
+        self._lengths = _copy_lengths(self.io, self._lengths, new, self.B)
 
     def use_lengths(self, tensors):
-        """Arena steps: the key-padding lengths as four device int32 buffers the batch's assembly already filled (or None = off)."""
-        self._lengths = list(tensors) if tensors is not None else None
-        self._point_lengths(self._lengths)
+        """Arena steps: the key-padding lengths as four device int32 buffers the batch's assembly already filled (or None = off).
+        Pointers only: the step never writes these."""
+        for i in range(4):
+            self.io.lengths[i] = ptr(tensors[i]) if tensors is not None else None
 
     def set_lr(self, lr):
         self.hyper[0] = lr
@@ -593,6 +578,8 @@ class TrainStep(_OptStateMixin):
         """Enqueues the step.  next_step: the TrainStep that runs NEXT in this arena (its dims decide how this step's middle lays out
         the next keep-bits set); prefetch: the sdumc_gather_batch descriptor of the next batch, issued by the step beside its middle
         and backward; pregen=False: no keep-bits for a next step this time (the caller does not expect a step of a known shape to follow)."""
+        if self._src is None:
+            raise _lib.SdumcError("launch: no batch is installed (set_batch, use_set, use_store or use_batch first)")
         st = _lib.current_stream() if stream is None else stream
         io = self.io
         a = self._arena
@@ -655,9 +642,9 @@ class _InputSet:
     """One resident batch slot of an arena: the four feature buffers (flat, capacity-sized), their P3 planes (fp32 storage, planes on),
     the labels and the valid frame counts."""
 
-    def __init__(self, n, planes_bytes, B, dtype, dev, rows):
+    def __init__(self, n, B, dtype, dev, rows):
         self._n, self._dtype, self._inputs = n, dtype, None      # (the padded copies' buffers exist only once something is copied)
-        self.planes = [torch.empty(k, device=dev, dtype=torch.uint8) for k in planes_bytes] if planes_bytes is not None else None
+        self.planes = None    # (_StepArena.ensure_planes)
         self.labels = torch.empty(B, device=dev)
         self.lengths = [torch.empty(B, dtype=torch.int32, device=dev) for _ in range(4)]
         self.maps = None      # row maps (int32 per frame): a batch read in place from a DeviceFeatureStore (ensure_maps)
@@ -693,15 +680,14 @@ class _StepArena:
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         goff = lib.sdumc_step_grads_offset(C.byref(d))
         self.workspace[goff:goff + 4 * lay.live].zero_()
-        fd = (dims[0], dims[1], dims[2], dims[1])
-        n = [self.B * self.T[i] * fd[i] for i in range(4)]
+        self._fdims = fd = (dims[0], dims[1], dims[2], dims[1])
+        rows = [self.B * self.T[i] for i in range(4)]
+        n = [rows[i] * fd[i] for i in range(4)]
         self.feature_dtype = torch.bfloat16 if d.bf16 == 2 else torch.float32
         # planes: True = the input sets carry P3 planes from the start; None = as soon as a store with planes (or a resident batch)
         # asks for them (ensure_planes); False = never
         self._planes_ok = planes is not False and planes_wanted(True, dims, bf16)
-        self._n = n
-        rows = [self.B * self.T[i] for i in range(4)]
-        self.sets = [_InputSet(n, None, self.B, self.feature_dtype, dev, rows) for _ in range(max(1, int(sets)))]
+        self.sets = [_InputSet(n, self.B, self.feature_dtype, dev, rows) for _ in range(max(1, int(sets)))]
         if planes is True:
             self.ensure_planes()
         V = 2 * self.B
@@ -718,23 +704,10 @@ class _StepArena:
             return False
         for st in self.sets:
             if st.planes is None:
-                st.planes = [torch.empty(6 * k, device=self.workspace.device, dtype=torch.uint8) for k in self._n]
+                st.planes = [_planes_buffer(r, d, self.workspace.device) for r, d in zip(st._rows, self._fdims)]
         return True
 
-    # (the single-set views older callers used)
-    @property
-    def inputs(self):
-        return self.sets[0].inputs
-
-    @property
-    def labels(self):
-        return self.sets[0].labels
-
-    @property
-    def lengths(self):
-        return self.sets[0].lengths
-
-    def fits(self, B, T, nbytes):
+    def fits(self, B, T, nbytes=0):
         return B <= self.B and all(t <= c for t, c in zip(T, self.T)) and nbytes <= self.workspace.numel()
 
 
@@ -746,7 +719,9 @@ class FusedTrainer:
     batch (every modality is padded to its batch maximum, read_data.py:223-248; the last batch of an epoch is short):
     one TrainStep per shape, created on first use, all sharing one optimiser state, so `step()` over a data loader is one
     continuous run of main_frame_val_text_missing.py:119-150.  At most `max_cached` shapes keep their workspace (least
-    recently used first out); a shape seen again after eviction is simply rebuilt.
+    recently used first out); a shape seen again after eviction is simply rebuilt.  `step()` hands each batch over zero-copy
+    (TrainStep.use_batch), holds the caller's tensors itself in one slot until the next `step()`, and unbinds the per-shape step after the
+    launch: a cached step keeps no batch alive, and a stray launch() on it raises instead of reading freed memory.
 
     With capacity= and a DeviceFeatureStore, `run_epoch` is the replacement for the reference's loop over its DataLoader
     (main :89-109 over feat_data.py:232-253): the epoch's index vectors are uploaded once, every batch is assembled on the device
@@ -775,6 +750,7 @@ class FusedTrainer:
         self._arena_kw = dict(bf16=step_kwargs.get("bf16", False), sets=sets, planes=planes,
                               bits_next=step_kwargs.get("bits_next", True), prefetch_workgroups=prefetch_workgroups)
         self._last_shape = None
+        self._batch = None        # the caller's tensors of step()'s zero-copy hand-over, until the next step()
         # inplace (fp32 storage, a store with planes): batches are read from the store through row maps, no padded copy (use_store);
         # False: every batch is gathered into the arena's input sets (fp32 rows + plane rows)
         self.inplace = bool(inplace)
@@ -792,15 +768,19 @@ class FusedTrainer:
         if ts is None:
             while len(self._steps) >= self.max_cached:
                 del self._steps[next(iter(self._steps))]
-            if self.arena is not None and not (B <= self.arena.B and all(t <= c for t, c in zip(T, self.arena.T))):
-                # a batch beyond the declared capacity: grow the arena (every cached step pointed into the old one)
-                cap_T = tuple(max(t, c) for t, c in zip(T, self.arena.T))
-                self.arena = _StepArena(self.params, max(B, self.arena.B), cap_T, self.dims, **self._arena_kw)
-                self._steps.clear()
+            self._fit_arena(B, T)
             kw = {k: v for k, v in self.kw.items() if not (self.arena is not None and k in ("planes", "bits_next"))}
             ts = TrainStep(self.params, B, T, self.dims, share=self.state, arena=self.arena, **kw)
         self._steps[key] = ts
         return ts
+
+    def _fit_arena(self, B, T):
+        """a batch beyond the arena's capacity: a larger arena takes its place (every cached step pointed into the old one: they go)"""
+        a = self.arena
+        if a is None or a.fits(B, T):
+            return
+        self.arena = _StepArena(self.params, max(B, a.B), tuple(max(t, c) for t, c in zip(T, a.T)), self.dims, **self._arena_kw)
+        self._steps.clear()
 
     def set_lr(self, lr):
         self.state.hyper[0] = lr
@@ -874,10 +854,7 @@ class FusedTrainer:
         # the arena must hold the epoch's largest batch BEFORE the first descriptor is built (growing it invalidates every cached step);
         # the per-shape step objects themselves are made one step ahead of the GPU, inside the loop: the host runs ahead of the device
         # anyway, so a shape seen for the first time costs no device time
-        Bm = max(B for B, _ in plan.shapes)
-        Tm = tuple(max(T[i] for _, T in plan.shapes) for i in range(4))
-        if not (Bm <= self.arena.B and all(t <= c for t, c in zip(Tm, self.arena.T))):
-            self._get(max(Bm, self.arena.B), tuple(max(t, c) for t, c in zip(Tm, self.arena.T)))
+        self._fit_arena(max(B for B, _ in plan.shapes), tuple(max(T[i] for _, T in plan.shapes) for i in range(4)))
         inplace = self._in_place(store)
         planes = inplace or self._store_planes(store)
         nxt = self._get(*plan.shapes[0])
@@ -900,7 +877,11 @@ class FusedTrainer:
         ts = self._get(audio.shape[0], (audio.shape[1], text.shape[1], video.shape[1], feat4.shape[1]))
         if self.arena is not None:
             ts.use_set(0, planes=False)      # (fresh tensors: a split for one use costs more than the planes save)
-        # the caller's device tensors are read where they are when they qualify (no 224 MB copy per batch); else copied
-        ts.use_batch(audio, text, video, feat4, labels.reshape(-1) if torch.is_tensor(labels) else labels)
+        # the caller's device tensors are read where they are when they qualify (no 224 MB copy per batch); else copied.  The trainer
+        # holds them, in ONE slot, until the next step(); the cached per-shape step is unbound again and keeps nothing alive
+        batch = (audio, text, video, feat4, labels.reshape(-1) if torch.is_tensor(labels) else labels)
+        self._batch = batch if ts.use_batch(*batch) else None
         ts.set_lengths(lengths)
-        return self._launch(ts)
+        losses = self._launch(ts)
+        ts._bind(None)
+        return losses

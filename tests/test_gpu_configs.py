@@ -564,7 +564,7 @@ def test_zero_copy_hand_over_equals_set_batch(E):
     ts.use_batch(*b1)
     ts.run()
     ts.set_batch(*b0)
-    assert ts._use_planes and ts.io.audio_p3 == ts._planes[0].data_ptr()
+    assert ts._planes is not None and ts.io.audio_p3 == ts._planes[0].data_ptr()
     flat2, _ = flat_from(E, P, dims)
     ts2 = E.TrainStep(flat2, B, Tn, dims, seed=9, lr=1e-3, planes=True)
     ts2.set_batch(*b0)
@@ -578,6 +578,161 @@ def test_zero_copy_hand_over_equals_set_batch(E):
     th = E.TrainStep(flat, B, Tn, dims, seed=9, bf16=True)
     assert th.use_batch(*[t.bfloat16() for t in b0[:4]], b0[4]) is True
     assert torch.equal(th.run(), la)
+
+
+def test_trainer_step_keeps_at_most_one_batch_alive(E):
+    """FusedTrainer.step() hands batches over zero-copy; the trainer holds the caller's tensors in ONE slot that the next step()
+    replaces, and the cached per-shape steps keep none: over a ragged loader every earlier batch is freed once the following step has
+    been enqueued (device memory does not grow with the number of shapes seen), with and without an arena.  A directly used
+    TrainStep.use_batch keeps its batch until the next set_batch / use_batch: that contract stands."""
+    import gc
+    import weakref
+    from oracle import sdumc_oracle as O
+    dims, Tcap = (64, 128, 64, 128), (70, 33, 66, 33)
+    P = O.init_params(dims, seed=2)
+    shapes = [(6, Tcap), (4, (66, 31, 64, 32)), (3, (70, 32, 66, 33)), (5, (64, 33, 60, 30)), (6, Tcap)]
+    assert len(set(shapes)) >= 4
+    for cap in ((6, Tcap), None):
+        flat, lay = flat_from(E, P, dims)
+        tr = E.FusedTrainer(flat, dims, lr=1e-3, seed=9, capacity=cap)
+        refs = []
+        for i, (B, Tn) in enumerate(shapes):
+            b = [t.cuda() for t in O.synthetic_batch(B, Tn, dims, seed=70 + i)]
+            tr.step(*b)
+            gc.collect()
+            assert all(r() is None for r in refs), (cap, i, [r() is not None for r in refs])
+            refs.append(weakref.ref(b[0]))
+            del b
+        torch.cuda.synchronize()
+        gc.collect()
+        assert all(r() is None for r in refs[:-1]), cap
+        assert torch.isfinite(tr.state.losses).all()
+    B, Tn = shapes[1]
+    flat, lay = flat_from(E, P, dims)
+    ts = E.TrainStep(flat, B, Tn, dims, seed=9)
+    for install in (ts.use_batch, ts.set_batch):
+        b = [t.cuda() for t in O.synthetic_batch(B, Tn, dims, seed=80)]
+        r = weakref.ref(b[0])
+        assert ts.use_batch(*b) is True
+        del b
+        ts.run()
+        gc.collect()
+        assert r() is not None
+        install(*[t.cuda() for t in O.synthetic_batch(B, Tn, dims, seed=81)])
+        gc.collect()
+        assert r() is None, install.__name__
+    torch.cuda.synchronize()
+
+
+def test_launch_without_an_installed_batch_raises(E):
+    """An arena step starts unbound, and FusedTrainer.step() leaves its per-shape step unbound: launch() raises SdumcError naming the
+    four ways to install a batch instead of reading buffers nobody filled (or a batch the caller has freed)."""
+    from oracle import sdumc_oracle as O
+    from sdumc_amd import _lib
+    dims, B, Tn = (64, 128, 64, 128), 4, (70, 32, 64, 33)
+    P = O.init_params(dims, seed=2)
+    b = [t.cuda() for t in O.synthetic_batch(B, Tn, dims, seed=60)]
+    flat, lay = flat_from(E, P, dims)
+    tr = E.FusedTrainer(flat, dims, lr=1e-3, seed=9, capacity=(B, Tn))
+    tr.step(*b)
+    with pytest.raises(_lib.SdumcError, match="set_batch, use_set, use_store or use_batch"):
+        tr._get(B, Tn).launch()
+    flat, lay = flat_from(E, P, dims)
+    ts = E.TrainStep(flat, B, Tn, dims, seed=9, arena=E.StepArena(flat, B, Tn, dims))
+    with pytest.raises(_lib.SdumcError, match="set_batch, use_set, use_store or use_batch"):
+        ts.launch()
+    assert ts._arena.sets[0]._inputs is None      # (nothing was touched)
+    ts.set_batch(*b)                              # an unbound arena step: set 0 is its home
+    ts.launch()
+    torch.cuda.synchronize()
+    assert torch.isfinite(ts.losses).all() and ts.io.audio == ts._arena.sets[0].inputs[0].data_ptr()
+
+
+def _store_case(E, seed_ix=1, B=4):
+    from oracle import sdumc_oracle as O
+    from sdumc_amd.data import DeviceFeatureStore
+    dims, Tcap = (64, 128, 64, 128), (70, 33, 66, 32)
+    store = DeviceFeatureStore.synthetic(48, Tcap, dims, seed=5, planes=True)
+    ix = torch.randperm(48, generator=torch.Generator().manual_seed(seed_ix))[:B]
+    return O.init_params(dims, seed=8), dims, Tcap, store, ix
+
+
+def test_set_lengths_after_use_lengths_writes_step_owned_buffers(E):
+    """step(lengths=...) after step_from_store(key_padding=True) on the same shape: set_lengths copies into buffers the step owns,
+    never into the arena set's capacity-sized length tensors that use_lengths pointed at (B = 4 < B_cap = 6: a shape error before; at
+    B = B_cap a silent overwrite of state every cached step shares).  The arena's tensors are untouched, the mask is in force, and the
+    two steps equal those of a trainer whose capacity is the batch itself, bit for bit."""
+    P, dims, Tcap, store, ix = _store_case(E)
+    b, pads, emos, vals, names = store.batch(ix)
+    keys = ("audios", "texts", "videos", "feat4s")
+    lens = [torch.tensor([b[k].shape[1] - p for p in pad], dtype=torch.int32) for k, pad in zip(keys, pads)]
+    assert any(int(l.min()) < b[k].shape[1] for k, l in zip(keys, lens))
+
+    def run(cap_B, masked):
+        flat, lay = flat_from(E, P, dims)
+        tr = E.FusedTrainer(flat, dims, lr=1e-3, seed=11, capacity=(cap_B, Tcap))
+        l0 = tr.step_from_store(store, ix, key_padding=True).clone()
+        before = [t.clone() for t in tr.arena.sets[0].lengths]
+        l1 = tr.step(*[b[k] for k in keys], vals, lengths=lens if masked else None).clone()
+        torch.cuda.synchronize()
+        for x, y in zip(before, tr.arena.sets[0].lengths):
+            assert torch.equal(x, y)
+        return l0, l1, flat.clone()
+
+    got, plain, want = run(6, True), run(6, False), run(4, True)
+    assert torch.equal(got[0], plain[0]) and not torch.equal(got[1], plain[1])
+    for x, y in zip(got, want):
+        assert torch.equal(x, y)
+
+
+def test_set_batch_after_use_store_trains_on_the_copied_batch(E):
+    """set_batch on an arena step that reads a store in place binds the step's home (the padded views of the set use_store named)
+    before it copies: the step trains on the batch it was given, not on the store's previous one through row maps left in place.
+    Losses and final parameters bit for bit equal to the run that names the set itself (use_set) before the copy."""
+    from oracle import sdumc_oracle as O
+    P, dims, Tcap, store, ix = _store_case(E)
+    B, Tn = store.batch_shape(ix)
+    b1 = [t.cuda() for t in O.synthetic_batch(B, Tn, dims, seed=61)]
+
+    def run(name_the_set):
+        flat, lay = flat_from(E, P, dims)
+        tr = E.FusedTrainer(flat, dims, lr=1e-3, seed=11, capacity=(6, Tcap))
+        l0 = tr.step_from_store(store, ix).clone()
+        ts = tr._get(B, Tn)
+        assert ts.io.row_map[0] is not None      # (the step read the store in place)
+        if name_the_set:
+            ts.use_set(0)
+        ts.set_batch(*b1)
+        assert ts.io.row_map[0] is None and ts.io.audio == tr.arena.sets[0].inputs[0].data_ptr()
+        ts.launch()
+        l1 = ts.losses.clone()
+        torch.cuda.synchronize()
+        return l0, l1, flat.clone()
+
+    for x, y in zip(run(False), run(True)):
+        assert torch.equal(x, y)
+
+
+def test_in_place_runs_allocate_no_padded_input_buffers(E):
+    """_InputSet's padded feature buffers exist only once something is copied into them: an in-place run_epoch / step_from_store
+    (row maps into the store) allocates none -- constructing the arena's steps touches no input set --, inplace=False does."""
+    P, dims, Tcap, store, ix = _store_case(E)
+    g = torch.Generator().manual_seed(1)
+    batches = [torch.randperm(48, generator=g)[:B] for B in (6, 4, 6)]
+    for inplace in (True, False):
+        for epoch in (True, False):
+            flat, lay = flat_from(E, P, dims)
+            tr = E.FusedTrainer(flat, dims, lr=1e-3, seed=11, capacity=(6, Tcap), inplace=inplace)
+            if epoch:
+                tr.run_epoch(store, batches)
+            else:
+                tr.step_from_store(store, ix)
+            torch.cuda.synchronize()
+            assert torch.isfinite(tr.state.losses).all()
+            if inplace:
+                assert all(st._inputs is None for st in tr.arena.sets), epoch
+            else:
+                assert tr.arena.sets[0]._inputs is not None, epoch
 
 
 def test_keep_bits_sets_are_tagged_with_call_and_shape(E):
