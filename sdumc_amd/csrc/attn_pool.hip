@@ -1125,10 +1125,14 @@ extern "C" size_t sdumc_attnpool_bwd_workspace_bytes(int32_t V, int32_t T, int32
 
 extern "C" int sdumc_attnpool_bwd(const sdumc_attnpool_bwd_t* bp, void* stream) {
   if (!bp) return SDUMC_EINVAL;
-  const sdumc_attnpool_bwd_t& b = *bp;
+  sdumc_attnpool_bwd_t b = *bp;
   int rc = check(b.f);
   if (rc) return rc;
   if (!b.dout || !b.dz || (!b.dq && !b.dq_sum) || !b.workspace) return SDUMC_EINVAL;
+  // T == 1: the softmax of one frame is constant, its score gradient EXACTLY 0.  The kernels form dS = scale * A * (dA - delta)
+  // from the same dot product summed in two orders; the rounding difference would leak into dz, dq and everything behind them,
+  // so the backward of a single frame runs with scale = 0 (the kernels read the scale for dS only).
+  if (b.f.T == 1) b.f.scale = 0.f;
   const sdumc_attnpool& p = b.f;
   if ((!b.dxd || b.dout_masked) && !v2_takes(p)) return SDUMC_EINVAL;      // (dxd left to the consumer: the wavefront-tiled kernels only)
   if (b.dq_sum && (p.q_stride != 0 || p.tickets)) return SDUMC_EINVAL;      // the sum over samples is the gradient of a SHARED query
@@ -1234,6 +1238,7 @@ extern "C" int sdumc_attnpool_bwd_multi(const sdumc_attnpool_bwd_t* bs, int32_t 
       if ((p.tickets != nullptr) != (bs[0].f.tickets != nullptr)) return SDUMC_EINVAL;
       if (b.workspace_bytes < sdumc_attnpool_bwd_workspace_bytes_dim(p.V, p.T, p.nq, D)) return SDUMC_ENOMEM;
       m.b[i] = b;
+      if (p.T == 1) m.b[i].f.scale = 0.f;      // (exactly zero score gradient: see sdumc_attnpool_bwd)
       m.nchunk[i] = (p.T + CH - 1) / CH;
       wg += m.nchunk[i] * p.V;
       dq += (unsigned long long)p.V * p.nq * D;

@@ -537,7 +537,10 @@ extern "C" int sdumc_colsum(const float* a, int64_t rows, int32_t cols, int32_t 
 extern "C" int sdumc_add_n(const float* const* xs, int32_t k, float* y, int64_t n, void* stream) {
   if (!xs || k < 1 || k > 8 || !y || n < 0) return SDUMC_EINVAL;
   AddN a;
-  for (int i = 0; i < 8; ++i) a.x[i] = i < k ? xs[i] : nullptr;
+  for (int i = 0; i < 8; ++i) {
+    a.x[i] = i < k ? xs[i] : nullptr;
+    if (i < k && !xs[i]) return SDUMC_EINVAL;
+  }
   if (n == 0) return SDUMC_OK;
   hipLaunchKernelGGL(add_n_kernel, dim3(nblk(n)), dim3(256), 0, as_stream(stream), a, k, y, n);
   SDUMC_CHECK_LAUNCH();

@@ -1348,7 +1348,8 @@ int pool_fwd(const Ctx& c, int k, int m) {
 // chain.hip: the utterance-level network (model :293-332, :338-368) in one launch per stage and direction instead of one
 // launch per layer.  Taken when the virtual batch is small enough that those layers are launch-bound (V <= 512: up to
 // B = 256 per GPU); larger batches keep the per-layer MFMA GEMMs, which are then compute-bound.  SDUMC_CHAIN=0 / 1 forces
-// either path (A/B measurements, parity tests of both).
+// either path (A/B measurements; tests/test_gpu_perlayer.py holds the per-layer path to the oracle on both sides of the
+// threshold and, with SDUMC_CHAIN=0 in a child process, at the smallest shapes).
 // ------------------------------------------------------------------------------------------
 bool use_chain(const Ctx& c) {
   static const int forced = [] { const char* e = getenv("SDUMC_CHAIN"); return e ? atoi(e) : -1; }();
