@@ -910,7 +910,12 @@ typedef struct sdumc_net_io {
    * projections fetch their A rows through the map (sdumc_gemm_p3.a_map), the frame projections' weight gradients their B rows
    * (sdumc_gg_problem.b_map); nothing else reads the features.  All four (three when streams == 1) or none; fp32 storage: needs the
    * *_p3 planes and the default split arithmetic; bf16 storage (audio / video / text[s] = the store's packed bf16 tensors): feature
-   * widths multiples of 128; else SDUMC_EINVAL.  The bf16 weight-gradient kernel reads map entries four at a time: each map must be
+   * widths multiples of 128; else SDUMC_EINVAL.  The backward additionally needs every modality's frame_dim_reshape weight gradient
+   * in the grouped launch (grouped weight gradients on; fp32 storage: its split arithmetic on -- sdumc_set_split_ bit 0 --
+   * and widths multiples of 4; the packed tensors 16-byte aligned):
+   * sdumc_net_backward, sdumc_net_backward_phase (EITHER phase) and sdumc_train_step decide their schedule first and return
+   * SDUMC_EINVAL before anything of the call is enqueued -- no fill, no fork, for sdumc_train_step no forward and no loss stage;
+   * sdumc_net_forward does not read the fp32 tensors and accepts such a batch.  The bf16 weight-gradient kernel reads map entries four at a time: each map must be
    * readable up to a multiple of four entries.  store_rows[i] (optional): rows of packed tensor i -- tensors (and planes) below
    * 4 GiB keep the kernels' descriptor addressing, which is faster than 64-bit addresses; 0 = unknown. */
   const int32_t* row_map[4];

@@ -603,6 +603,8 @@ struct Ctx {
   // bf16 buffers: `off` is the buffer's offset in floats, `elems` an element offset inside it
   unsigned short* ph(int64_t off, int64_t elems = 0) const { return reinterpret_cast<unsigned short*>(W + off) + elems; }
   bool h() const { return pl.hf; }
+  // element `elems` of an activation buffer in the call's storage, as the launchers take it (they read bf16 buffers through float*)
+  float* act(int64_t off, int64_t elems = 0) const { return h() ? reinterpret_cast<float*>(ph(off, elems)) : p(off) + elems; }
   void init_lanes() {
     lanes = io.ctx ? static_cast<LaneSet*>(io.ctx) : default_lanes();
     static LaneSet none;
@@ -1903,28 +1905,28 @@ int forward(const Ctx& c) {
   return SDUMC_OK;
 }
 
+// the pooling-backward descriptor of run sg of site (k, m), without its workspace
+sdumc_attnpool_bwd_t fill_pool_bwd(const Ctx& c, int k, int m, const Seg& sg, const float* dout_base, float* dq_base) {
+  const Plan& pl = c.pl;
+  sdumc_attnpool_bwd_t b;
+  memset(&b, 0, sizeof(b));
+  b.f = attn_desc(c, k, m, sg);
+  const int64_t voff = (int64_t)sg.s0 * pl.B * (k == 0 ? 1 : NQ) * D;
+  b.dout = dout_base + voff;
+  b.dq = dq_base + voff;
+  b.dz = c.act(pl.dz[k][m], sg.row0 * D);
+  b.dxd = c.act(pl.dxd[k][m], sg.row0 * D);
+  if (dxfold(c, m)) { b.dxd = nullptr; b.dout_masked = c.p(pl.dom[k][m]) + voff; }
+  return b;
+}
 // backward of the pooling of site (k, m): dz (pre-tanh key gradient), dxd (pooling path), dq
 int pool_bwd(const Ctx& c, int k, int m, const float* dout_base /* [V, nq, D] */, float* dq_base /* [V, nq, D] */,
              float* dq_sum = nullptr /* shared query: [nq, D] sum over the samples instead of dq */) {
-  const Plan& pl = c.pl;
-  const int nq = k == 0 ? 1 : NQ;
-  for (const Seg& sg : pl.segs[m]) {
-    sdumc_attnpool_bwd_t b;
-    memset(&b, 0, sizeof(b));
-    b.f = attn_desc(c, k, m, sg);
-    const int64_t voff = (int64_t)sg.s0 * pl.B * nq * D;
-    b.dout = dout_base + voff;
-    b.dz = c.p(pl.dz[k][m]) + sg.row0 * D;
-    b.dxd = c.p(pl.dxd[k][m]) + sg.row0 * D;
-    if (c.h()) {
-      b.dz = reinterpret_cast<float*>(c.ph(pl.dz[k][m], sg.row0 * D));
-      b.dxd = reinterpret_cast<float*>(c.ph(pl.dxd[k][m], sg.row0 * D));
-    }
-    if (dxfold(c, m)) { b.dxd = nullptr; b.dout_masked = c.p(pl.dom[k][m]) + voff; }
-    b.dq = dq_base + voff;
+  for (const Seg& sg : c.pl.segs[m]) {
+    sdumc_attnpool_bwd_t b = fill_pool_bwd(c, k, m, sg, dout_base, dq_base);
     b.dq_sum = dq_sum;
     b.workspace = c.scr;
-    b.workspace_bytes = (size_t)pl.scratch_floats * sizeof(float);
+    b.workspace_bytes = (size_t)c.pl.scratch_floats * sizeof(float);
     RET(sdumc_attnpool_bwd(&b, c.st));
   }
   return SDUMC_OK;
@@ -2007,12 +2009,11 @@ void keys_dw_queue(const Ctx& c, int m, int k0, int k1) {
     int s = 0;
     for (const Seg& sg : pl.segs[m]) {
       q.K[s] = sg.V * sg.T;
+      q.A[s] = c.act(pl.dz[k][m], sg.row0 * D);
       if (c.h()) {     // bf16 storage: dz and the materialised masked frames xd (train) / the shared x (eval)
-        q.A[s] = reinterpret_cast<const float*>(c.ph(pl.dz[k][m], sg.row0 * D));
         q.B[s] = reinterpret_cast<const float*>(c.d.train ? c.ph(pl.xd[k][m], sg.row0 * D) : c.ph(sg.x_off));
         q.b_row_mod[s] = (!c.d.train && sg.x_samples < sg.V) ? sg.x_samples * sg.T : 0;
       } else {
-        q.A[s] = c.p(pl.dz[k][m]) + sg.row0 * D;
         q.B[s] = c.p(sg.x_off);
         q.b_row_mod[s] = sg.x_samples < sg.V ? sg.x_samples * sg.T : 0;
         const sdumc_dropout dd = in_drop(c, k, m, sg.T, sg.s0, sg.row0);
@@ -2076,14 +2077,10 @@ int keys_dx_sum_problems(const Ctx& c, int m, int k, sdumc_rows_problem* q) {
     sdumc_rows_problem& r = q[n++];
     memset(&r, 0, sizeof(r));
     const int fold = sg.V / sg.x_samples;              // streams that share the run's frames: 2 (audio, video), 1 (the text slot: dx rows = virtual rows)
-    r.A = c.p(pl.dz[k][m]) + sg.row0 * D;
-    r.B = c.P + L.w;
-    r.C = c.p(pl.dx[m][sg.s0]);
-    if (c.h()) {      // bf16 dz / dx; B = the transposed bf16 weight copy (its rows are the output columns)
-      r.A = reinterpret_cast<const float*>(c.ph(pl.dz[k][m], sg.row0 * D));
-      r.B = reinterpret_cast<const float*>(c.ph(pl.wht, L.w));
-      r.C = reinterpret_cast<float*>(c.ph(pl.dx[m][sg.s0]));
-    }
+    r.A = c.act(pl.dz[k][m], sg.row0 * D);
+    // (bf16 storage: B = the transposed bf16 weight copy -- its rows are the output columns)
+    r.B = c.h() ? reinterpret_cast<const float*>(c.ph(pl.wht, L.w)) : c.P + L.w;
+    r.C = c.act(pl.dx[m][sg.s0]);
     r.M = sg.V * sg.T;
     r.lda = r.ldb = r.ldc = D;
     r.accumulate = k == 0 ? 1 : 0;
@@ -2160,176 +2157,277 @@ int keys_gemm_bwd(const Ctx& c, int m, int k0, int k1, int parts = 3, int rows_c
   return run(c, g);
 }
 
-// phases: bit 0 = the utterance-level part (finishes every gradient in [0, pm.early)), bit 1 = the frame-level part
-int backward(const Ctx& c, const sdumc_net_grads& og, int phases = 3) {
-  const Plan& pl = c.pl;
-  const ParamMap& pm = c.pm;
-  const int B = pl.B, S = pl.S, V = pl.V;
-  const int din[3] = {c.d.da, c.d.dt, c.d.dv};
-  const float s_mlp = c.d.train ? 1.0f / (1.0f - (float)c.d.p_mlp) : 1.0f;
+// The backward pass.  plan_backward() decides the schedule -- which modality's Cross_Attention dX goes early and on which lane,
+// which weight gradients ride in which grouped launch -- ONCE, before the first launch; backward() and its parts read the record.
+struct BwdSchedule {
+  int rc = SDUMC_OK;               // SDUMC_EINVAL: the schedule cannot serve the io (row maps with a per-layer frame dW, below)
+  bool utterance = true;           // phases bit 0: the utterance-level part (finishes every gradient in [0, pm.early))
+  bool frame = true;               // phases bit 1: the frame-level part
+  bool chain = false;              // 12'-9' and 7'-3' as one launch each (chain.hip) instead of per layer
+  bool dw_grouped = false;         // the frame-level weight gradients leave in the grouped launches (gg_frame)
+  bool pool_grouped = false;       // 8': the Cross_Attention pooling backward of all modalities as ONE launch on the caller's stream
+  bool early_one_launch = false;   // the early Cross_Attention sites of every early modality: ONE rows launch on lane 3
+  bool flush1_after_pool = false;  // batch 1 of the weight gradients leaves ahead of 8' (else it rides with the input_proj dW)
+  bool flush2_after_query = false; // batch 2 (query_proj, the query MLPs) leaves behind 6' (grouped mode: it waits for batch 3)
+  bool flush3_after_utt = false;   // batch 3 leaves behind 3' (else it rides with the FRA2UTT input_proj dW of the frame-level part)
+  bool fra_fold = false;           // 8' leaves its dq slabs unsummed: the clustered stage 7'-3' sums the chunks
+  struct Mod {
+    bool early = false;            // the Cross_Attention key-projection backward runs early, beside steps 7'-3'
+    int early_lane = 3;            // ... on this lane: the modality's own, or lane 3
+    bool ca_dw_grouped = false;    // the Cross_Attention input_proj dW is queued right behind the grouped pooling backward of 8'
+    bool fra_dw_grouped = false;   // the FRA2UTT input_proj dW is queued behind the FRA2UTT pooling backward
+    bool ca_dw_late = false;       // ... and the Cross_Attention one with it (it left neither in 8' nor with the early dX)
+    bool dw_on_lane3 = false;      // per-layer key-projection dW: on lane 3, off the modality's dz -> dX -> mask-sum -> frame dW chain
+    bool dx_sum = false;           // the rows launches add keep . dxd straight into dx: no mask-sum launch
+    bool frame_dw_grouped = false; // frame_dim_reshape dW: a problem of the grouped launch behind the join (else per stream)
+    int k1 = 2;                    // the sites [0, k1) are left for the frame-level pass
+  } mod[3];
+};
+const float* feat_in(const Ctx& c, int m, int s) { return m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]); }
+// launches nothing, records no event, touches no stream: a function of dims, io, the context's options, the process-wide switches
+// (environment, setters) and whether the caller's stream is under capture (c.capturing, asked once by init_lanes)
+BwdSchedule plan_backward(const Ctx& c, int phases) {
+  BwdSchedule s;
+  s.utterance = (phases & 1) != 0;
+  s.frame = (phases & 2) != 0;
+  s.chain = use_chain(c);
+  s.dw_grouped = gg_frame(c);
+  s.pool_grouped = attn_multi_ok(c);
+  // batch 1 of the weight gradients (heads, cross_attention_mlp, cross_*_mlp) -- in the grouped mode together with the
+  // Cross_Attention input_proj dW, right behind the pooling backward that produces their dz
+  s.flush1_after_pool = !(s.dw_grouped && s.pool_grouped);
+  // batch 3: fc_att, attention_mlp, audio/text/video_mlp.  Grouped mode with the frame-level part following in this call:
+  // they stay queued and ride with the FRA2UTT input_proj dW in one launch.
+  s.flush3_after_utt = !(s.dw_grouped && s.frame);
+  s.flush2_after_query = !s.chain && !gg_utt(c);
+  s.fra_fold = fra_fold(c);
   // Early Cross_Attention key-projection backward (bit m of c.bgb): a modality that owns a side lane keeps going on that lane --
   // the caller's stream waits only for the pooling backward before it, so the GEMMs run beside steps 7'-3' and, in phased
   // calls (the data-parallel step), beside whatever the caller does between the phases; a modality on the caller's stream
   // goes through lane 3, which phased calls cannot use for frame-level work (phase 0 ends by waiting for lane 3).
   // With the grouped weight-gradient launches lane 3 carries persistent kernels that fill the chip for 0.1-0.2 ms each, so
   // nothing the critical path waits for may queue behind them: the early dX then always takes the modality's own lane.
-  const bool ggf = gg_frame(c);
   // The early modality keeps its per-layer dW + dX pair (small-footprint kernels that run beside the utterance-level stage
   // 7'-3'); measured in the grouped mode, fp32 C2: 1.787 ms, against 1.816 with only its dX early and the dW grouped, 1.833 with
   // no early work at all, 1.831 with the pair issued behind that stage instead of beside it.
-  int own_lane = 0;
-  for (int m = 0; m < 3; ++m)
-    if (phases != 3 && (c.bgb & (1 << m)) && c.multi && LANE_OF[m] != 0) own_lane |= 1 << m;
   // (in a single call the lane-3 route measured 0.15 % faster than the own-lane route; phased calls gain 0.6 % from the latter)
   // (dxsum: audio's AND video's Cross_Attention sites go early, in one launch -- each site is a launch of its own there, the first of
   //  a modality writes dx, and two of them back to back on video's lane made it the longest: 1.2917-1.2925 ms against 1.307-1.308
   //  with audio's alone, 1.2946-1.2986 with all three)
-  const int bgb = phases == 3 ? ((c.bgb && dxsum(c, 0) && dxsum(c, 2)) ? 5 : c.bgb) : own_lane;
-  // grouped mode: the dW of the Cross_Attention input_proj layers rides in the launch right behind the (grouped) pooling backward
-  // of phase 0 (bit m of ca_dw_mask), the dW of the FRA2UTT ones in the launch behind the FRA2UTT pooling backward of phase 1
-  const bool ca_dw_grouped = ggf && attn_multi_ok(c);
-  int ca_dw_mask = 0, fra_dw_mask = 0;
+  const bool audio_and_video = phases == 3 && c.bgb && dxsum(c, 0) && dxsum(c, 2);
+  bool any_early = false, one_launch = true;
   for (int m = 0; m < 3; ++m) {
+    BwdSchedule::Mod& M = s.mod[m];
+    const bool own_lane = phases != 3 && (c.bgb & (1 << m)) && c.multi && LANE_OF[m] != 0;
+    M.early = phases == 3 ? (audio_and_video ? m != 1 : (c.bgb & (1 << m)) != 0) : own_lane;
+    M.early_lane = own_lane ? LANE_OF[m] : 3;
+    M.k1 = M.early ? 1 : 2;
+    M.dx_sum = dxsum(c, m);
+    // grouped mode: the dW of the Cross_Attention input_proj layers rides in the launch right behind the (grouped) pooling backward
+    // of phase 0, the dW of the FRA2UTT ones in the launch behind the FRA2UTT pooling backward of phase 1.
     // Only the dX of the early modality's Cross_Attention site runs early (it feeds that modality's mask-sum); its dW rides in the
     // grouped launch like every other weight gradient.  Round 3 measured the per-layer dW + dX PAIR ahead (1.787 vs 1.816 ms);
     // with the round-4 pooling kernels and reduce launches the order flipped: fp32 C2 1.690-1.698 vs 1.701-1.706 ms with the pair,
     // bf16 storage 0.956-0.959 vs 1.019-1.021 (three alternations on one box).
-    if (ca_dw_grouped && keys_dw_groupable(c, m)) ca_dw_mask |= 1 << m;
-    if (ggf && keys_dw_groupable(c, m)) fra_dw_mask |= 1 << m;
+    M.fra_dw_grouped = s.dw_grouped && keys_dw_groupable(c, m);
+    M.ca_dw_grouped = M.fra_dw_grouped && s.pool_grouped;
+    M.ca_dw_late = M.fra_dw_grouped && !M.ca_dw_grouped && !M.early;   // (the Cross_Attention one, when it did not leave in phase 0)
+    // modality m's per-layer key-projection dW runs on lane 3 (ungrouped modes): audio's, on bf16 storage.
+    // (re-measured with the clustered utterance-level kernels: fp32 1.923 ms with none on lane 3 vs 1.930 with audio's;
+    //  bf16 storage 1.148 vs 1.128 -- so the default follows the mode)
+    M.dw_on_lane3 = !M.fra_dw_grouped && c.multi && !c.capturing && c.h() && m == 0;
+    // grouped or per-layer is decided ONCE per modality: the grouped problem overwrites its output (accumulate = 0) after the
+    // lanes have joined, so a modality whose streams took different paths would lose the per-layer stream's contribution
+    M.frame_dw_grouped = s.dw_grouped && (c.h() || ((m == 0 ? c.d.da : (m == 1 ? c.d.dt : c.d.dv)) & 3) == 0);
+    for (int st = 0; st < (m == 1 ? c.pl.S : 1); ++st)
+      if (reinterpret_cast<uintptr_t>(feat_in(c, m, st)) & 15) M.frame_dw_grouped = false;
+    if (!M.frame_dw_grouped && c.io.row_map[0]) s.rc = SDUMC_EINVAL;      // (only the grouped launch fetches its rows through a map
+                                                                          //  -- in fp32 storage its split-arithmetic kernel: below)
+    any_early = any_early || M.early;
+    one_launch = one_launch && (!M.early || (M.dx_sum && M.early_lane == 3 && M.ca_dw_grouped));
   }
-  // early_done[m]: lane 3 has finished modality m's early key-projection backward (dxd of its Cross_Attention site).  The
-  // modality's own lane waits for exactly this event before its mask-sum -- not for whatever else lane 3 has been handed by
-  // then (the utterance-level dW batches, the other key-projection dW GEMMs: ~0.25 ms of work that only feeds the bucket).
-  hipEvent_t early_done[3] = {nullptr, nullptr, nullptr};
-  auto record_early = [&](int m) -> int {
-    if (c.sts[3] == c.sts[LANE_OF[m]]) return SDUMC_OK;
-    early_done[m] = next_event(c);
-    return hipEventRecord(early_done[m], c.sts[3]) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-  };
-  // the early key-projection backward of the Cross_Attention sites (bit m of bgb), ordered after what lane 0 has issued so far
-  auto early_keys = [&]() -> int {
-    constexpr int ecap = 160;      // (workgroups of the merged early launch: 160 1.3266-1.3297 ms, 128 1.3304-1.3345, 96 1.3645-1.3712, 200 / 256 +1.5 %)
-    bool all_sum = true;
-    for (int m = 0; m < 3; ++m) all_sum = all_sum && (!(bgb & (1 << m)) || dxsum(c, m));
-    if (all_sum && !own_lane && bgb && !(bgb & ~ca_dw_mask)) {      // the early Cross_Attention sites of every early modality: ONE rows launch on lane 3
-      sdumc_rows_problem q[8];
-      int n = 0;
-      for (int m = 0; m < 3; ++m)
-        if (bgb & (1 << m)) n += keys_dx_sum_problems(c, m, 1, q + n);
-      RET(link(c, 0, 3));
-      c.use(3);
-      bool one_fold = true;      // (a bf16 launch takes one fold: runs of shared and of separate frames go in separate launches there)
-      for (int i = 1; i < n; ++i) one_fold = one_fold && q[i].fold == q[0].fold;
-      if (c.h() && !one_fold) {
-        for (int i = 0; i < n; ++i) RET(dx_sum_launch(c, q + i, 1, ecap));
-      } else
-      RET(dx_sum_launch(c, q, n, ecap));
-      for (int m = 0; m < 3; ++m)
-        if (bgb & (1 << m)) RET(record_early(m));
-      c.use(0);
-      return SDUMC_OK;
-    }
-    for (int m = 0; m < 3; ++m) {
-      if (!(bgb & (1 << m))) continue;
-      const int lane = (own_lane & (1 << m)) ? LANE_OF[m] : 3;
-      RET(link(c, 0, lane));
-      c.use(lane);
-      // The early dX runs as the persistent rows launch on HALF of the CUs: a full-chip launch holds every CU's register file, so
-      // the FRA2UTT pooling backward of the three modality lanes -- the next link of the critical chain, HBM-bound, issued while
-      // this launch is still running -- crawled beside it (86-104 us instead of ~60); the early dX itself has slack until its
-      // modality's mask-sum.  Measured, fp32 C2, three alternations on one box: 128 workgroups 1.670-1.680 ms, 64: 1.675-1.679,
-      // 256 (every CU): 1.686-1.689, the tiled 64x64 kernel: 1.689-1.695.
-      // (round 4, rows launch on the bf16 matrix pipe: 160 workgroups 1.414-1.427 against 128 1.424-1.438 and 192 1.425-1.438)
-      constexpr int early_dx = 160;
-      RET(keys_gemm_bwd(c, m, 1, 2, (ca_dw_mask & (1 << m)) ? 2 : 3, early_dx));
-      if (lane == 3) RET(record_early(m));
-      c.use(0);
-    }
-    return SDUMC_OK;
-  };
-  if (phases & 1) {
-  // every live gradient tensor is overwritten below when all five output gradients are given
-  if (!og.d_vals || !og.d_fused || !og.d_rnc || !og.d_text_hidden || !og.d_cross_text) RET(sdumc_fill(c.G, 0.f, pm.live, c.st));
+  s.early_one_launch = any_early && one_launch;
+  if (c.io.row_map[0] && !c.h() && !sdumc_split_on_(SDUMC_SPLIT_GROUP)) s.rc = SDUMC_EINVAL;
+  return s;
+}
 
-  const bool chain = use_chain(c);
-  if (chain) {
-    // 12'-9' in one launch (chain.hip); the weight gradients of these layers are queued for lane 3 as before
+// early_done[m]: lane 3 has finished modality m's early key-projection backward (dxd of its Cross_Attention site).  The
+// modality's own lane waits for exactly this event before its mask-sum -- not for whatever else lane 3 has been handed by
+// then (the utterance-level dW batches, the other key-projection dW GEMMs: ~0.25 ms of work that only feeds the bucket).
+int record_early(const Ctx& c, int m, hipEvent_t* early_done) {
+  if (c.sts[3] == c.sts[LANE_OF[m]]) return SDUMC_OK;
+  early_done[m] = next_event(c);
+  return hipEventRecord(early_done[m], c.sts[3]) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
+}
+int await_early(const Ctx& c, const BwdSchedule& sch, int m, const hipEvent_t* early_done) {
+  if (!sch.mod[m].early || sch.mod[m].early_lane != 3) return SDUMC_OK;   // dxd of this modality's Cross_Attention site (issued early on lane 3)
+  if (early_done[m]) return hipStreamWaitEvent(c.st, early_done[m], 0) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
+  return link(c, 3, LANE_OF[m]);
+}
+// the early key-projection backward of the Cross_Attention sites (mod[m].early), ordered after what lane 0 has issued so far
+int early_keys(const Ctx& c, const BwdSchedule& sch, hipEvent_t* early_done) {
+  constexpr int ecap = 160;      // (workgroups of the merged early launch: 160 1.3266-1.3297 ms, 128 1.3304-1.3345, 96 1.3645-1.3712, 200 / 256 +1.5 %)
+  if (sch.early_one_launch) {
+    sdumc_rows_problem q[8];
+    int n = 0;
+    for (int m = 0; m < 3; ++m)
+      if (sch.mod[m].early) n += keys_dx_sum_problems(c, m, 1, q + n);
+    RET(link(c, 0, 3));
+    c.use(3);
+    bool one_fold = true;      // (a bf16 launch takes one fold: runs of shared and of separate frames go in separate launches there)
+    for (int i = 1; i < n; ++i) one_fold = one_fold && q[i].fold == q[0].fold;
+    if (c.h() && !one_fold) {
+      for (int i = 0; i < n; ++i) RET(dx_sum_launch(c, q + i, 1, ecap));
+    } else
+    RET(dx_sum_launch(c, q, n, ecap));
+    for (int m = 0; m < 3; ++m)
+      if (sch.mod[m].early) RET(record_early(c, m, early_done));
+    c.use(0);
+    return SDUMC_OK;
+  }
+  for (int m = 0; m < 3; ++m) {
+    const BwdSchedule::Mod& M = sch.mod[m];
+    if (!M.early) continue;
+    RET(link(c, 0, M.early_lane));
+    c.use(M.early_lane);
+    // The early dX runs as the persistent rows launch on HALF of the CUs: a full-chip launch holds every CU's register file, so
+    // the FRA2UTT pooling backward of the three modality lanes -- the next link of the critical chain, HBM-bound, issued while
+    // this launch is still running -- crawled beside it (86-104 us instead of ~60); the early dX itself has slack until its
+    // modality's mask-sum.  Measured, fp32 C2, three alternations on one box: 128 workgroups 1.670-1.680 ms, 64: 1.675-1.679,
+    // 256 (every CU): 1.686-1.689, the tiled 64x64 kernel: 1.689-1.695.
+    // (round 4, rows launch on the bf16 matrix pipe: 160 workgroups 1.414-1.427 against 128 1.424-1.438 and 192 1.425-1.438)
+    constexpr int early_dx = 160;
+    RET(keys_gemm_bwd(c, m, 1, 2, M.ca_dw_grouped ? 2 : 3, early_dx));
+    if (M.early_lane == 3) RET(record_early(c, m, early_done));
+    c.use(0);
+  }
+  return SDUMC_OK;
+}
+
+// 7'. query_proj: dW/db per modality (queued for lane 3)
+void query_proj_dw_queue(const Ctx& c) {
+  const int M = c.pl.V * NQ;
+  sdumc_gemm gw = G_(SDUMC_TN, D, D, M, 3);
+  for (int m = 0; m < 3; ++m) {
+    gw.A[m] = c.p(c.pl.d_qp) + (int64_t)m * M * D;
+    gw.B[m] = c.p(c.pl.q);
+    gw.C[m] = c.G + c.pm.ca_q[m].w;
+    gw.colsum_a[m] = c.G + c.pm.ca_q[m].b;
+  }
+  gw.lda = gw.ldb = gw.ldc = D;
+  c.deferred.push_back(gw);
+}
+
+// The two utterance-level stages: steps 12'-9' (heads ... cross_*_mlp) and steps 7'-3' (query_proj ... audio/text/video_mlp).
+// sch.chain: ONE launch (chain.hip) computes the stage's input gradients; the layers below then only queue their dW for lane 3
+// (lin_bwd* with a null dx: the dx arguments behind it are not read), in the order of the per-layer form.
+int bwd_heads(const Ctx& c, const sdumc_net_grads& og, const BwdSchedule& sch) {
+  const Plan& pl = c.pl;
+  const ParamMap& pm = c.pm;
+  const bool per_layer = !sch.chain;
+  const int V = pl.V, M7 = V * NQ;
+  const float s_mlp = c.d.train ? 1.0f / (1.0f - (float)c.d.p_mlp) : 1.0f;
+  auto dx = [&](int64_t off) { return per_layer ? c.p(off) : nullptr; };
+  if (sch.chain) {
     const sdumc_chain_args ca = chain_args(c, false, &og, false);
     RET(chain_launch(c, ca, 2));
     mark(c.st, 6);
-    const int M7 = V * NQ;
-    if (og.d_rnc) {
-      RET(lin_bwd(c, pm.rnc2, og.d_rnc, RD, c.p(pl.r1), RD, V, nullptr, 0, 0));
-      RET(lin_bwd(c, pm.rnc0, c.p(pl.d_r1), RD, c.p(pl.z), H, V, nullptr, 0, 0));
-    }
-    if (og.d_vals) RET(lin_bwd(c, pm.fc_out_v, og.d_vals, 1, c.p(pl.z), H, V, nullptr, 0, 0));
-    RET(lin_bwd(c, pm.cross_fc_att, c.p(pl.d_beta), NQ, c.p(pl.e2), H, V, nullptr, 0, 0));
-    RET(lin_bwd(c, pm.catt3, c.p(pl.d_e2), H, c.p(pl.e1), D, V, nullptr, 0, 0));
-    RET(lin_bwd(c, pm.catt0, c.p(pl.d_e1), D, c.p(pl.h), NQ * H, V, nullptr, 0, 0));
-    GroupPtrs q3 = {c.p(pl.d_c), (int64_t)M7 * H, H, c.p(pl.c1), (int64_t)M7 * D, D, nullptr, 0, 0};
-    RET(lin_bwd_grouped(c, pm.cmlp3, 3, M7, q3));
-    GroupPtrs q0 = {c.p(pl.d_c1), (int64_t)M7 * D, D, c.p(pl.ca_out), (int64_t)M7 * D, D, nullptr, 0, 0};
-    RET(lin_bwd_grouped(c, pm.cmlp0, 3, M7, q0));
-  } else {
+  }
   // 12'. heads: r = L2(relu(L0(z))), vals = fc_out_v(z), plus the external gradient of cross_fused_feat
-  float* d_z = c.p(pl.d_z);
+  float* d_z = dx(pl.d_z);
   if (og.d_rnc) {
-    RET(lin_bwd(c, pm.rnc2, og.d_rnc, RD, c.p(pl.r1), RD, V, c.p(pl.d_r1), RD, 0, c.p(pl.r1), 1.0f));
+    RET(lin_bwd(c, pm.rnc2, og.d_rnc, RD, c.p(pl.r1), RD, V, dx(pl.d_r1), RD, 0, c.p(pl.r1), 1.0f));
     RET(lin_bwd(c, pm.rnc0, c.p(pl.d_r1), RD, c.p(pl.z), H, V, d_z, H, 0));
-  } else {
+  } else if (per_layer) {
     RET(sdumc_fill(d_z, 0.f, (int64_t)V * H, c.st));
   }
   if (og.d_vals) RET(lin_bwd(c, pm.fc_out_v, og.d_vals, 1, c.p(pl.z), H, V, d_z, H, 1));
   //      (d_z + the external gradient of cross_fused_feat, added inside the kernel instead of by an axpy launch)
-  RET(sdumc_zpool_bwd_add_(c.p(pl.h), c.p(pl.beta), d_z, og.d_fused, c.p(pl.d_h), c.p(pl.d_beta), V, c.st));
+  if (per_layer) RET(sdumc_zpool_bwd_add_(c.p(pl.h), c.p(pl.beta), d_z, og.d_fused, c.p(pl.d_h), c.p(pl.d_beta), V, c.st));
   // 11'. cross_fc_att, cross_attention_mlp
-  RET(lin_bwd(c, pm.cross_fc_att, c.p(pl.d_beta), NQ, c.p(pl.e2), H, V, c.p(pl.d_e2), H, 0, c.p(pl.e2), s_mlp));
-  RET(lin_bwd(c, pm.catt3, c.p(pl.d_e2), H, c.p(pl.e1), D, V, c.p(pl.d_e1), D, 0, c.p(pl.e1), s_mlp));
-  RET(lin_bwd(c, pm.catt0, c.p(pl.d_e1), D, c.p(pl.h), NQ * H, V, c.p(pl.d_h), NQ * H, 1));
+  RET(lin_bwd(c, pm.cross_fc_att, c.p(pl.d_beta), NQ, c.p(pl.e2), H, V, dx(pl.d_e2), H, 0, c.p(pl.e2), s_mlp));
+  RET(lin_bwd(c, pm.catt3, c.p(pl.d_e2), H, c.p(pl.e1), D, V, dx(pl.d_e1), D, 0, c.p(pl.e1), s_mlp));
+  RET(lin_bwd(c, pm.catt0, c.p(pl.d_e1), D, c.p(pl.h), NQ * H, V, dx(pl.d_h), NQ * H, 1));
   // 10'. modality-weighted sum; the external gradient of cross_hiddens[:,1] joins here
-  RET(sdumc_hweight_bwd(c.p(pl.c), c.p(pl.alpha), c.p(pl.d_h), og.d_cross_text, c.p(pl.d_c), c.p(pl.d_alpha), V, s_mlp,
-                        c.st));   // d_c comes out already masked: gradient w.r.t. the pre-activation of cross_*_mlp.3
+  if (per_layer)
+    RET(sdumc_hweight_bwd(c.p(pl.c), c.p(pl.alpha), c.p(pl.d_h), og.d_cross_text, c.p(pl.d_c), c.p(pl.d_alpha), V, s_mlp,
+                          c.st));   // d_c comes out already masked: gradient w.r.t. the pre-activation of cross_*_mlp.3
   // 9'. cross_{audio,text,video}_mlp
-  {
-    const int M = V * NQ;
-    GroupPtrs q3 = {c.p(pl.d_c), (int64_t)M * H, H, c.p(pl.c1), (int64_t)M * D, D, c.p(pl.d_c1), (int64_t)M * D, D,
-                    c.p(pl.c1), s_mlp};
-    RET(lin_bwd_grouped(c, pm.cmlp3, 3, M, q3));
-    GroupPtrs q0 = {c.p(pl.d_c1), (int64_t)M * D, D, c.p(pl.ca_out), (int64_t)M * D, D, c.p(pl.d_ca_out), (int64_t)M * D, D};
-    RET(lin_bwd_grouped(c, pm.cmlp0, 3, M, q0));
+  GroupPtrs q3 = {c.p(pl.d_c), (int64_t)M7 * H, H, c.p(pl.c1), (int64_t)M7 * D, D, dx(pl.d_c1), (int64_t)M7 * D, D,
+                  c.p(pl.c1), s_mlp};
+  RET(lin_bwd_grouped(c, pm.cmlp3, 3, M7, q3));
+  GroupPtrs q0 = {c.p(pl.d_c1), (int64_t)M7 * D, D, c.p(pl.ca_out), (int64_t)M7 * D, D, dx(pl.d_ca_out), (int64_t)M7 * D, D};
+  return lin_bwd_grouped(c, pm.cmlp0, 3, M7, q0);
+}
+int bwd_stage_a(const Ctx& c, const sdumc_net_grads& og, const BwdSchedule& sch) {
+  const Plan& pl = c.pl;
+  const ParamMap& pm = c.pm;
+  const bool per_layer = !sch.chain;
+  const int V = pl.V, M7 = V * NQ;
+  const float s_mlp = c.d.train ? 1.0f / (1.0f - (float)c.d.p_mlp) : 1.0f;
+  auto dx = [&](int64_t off) { return per_layer ? c.p(off) : nullptr; };
+  if (sch.chain) {
+    const sdumc_chain_args ca = chain_args(c, false, &og, true);
+    mark(c.st, 7);
+    RET(chain_launch(c, ca, 3));
+    mark(c.st, 8);
   }
-  }   // !chain
-  // 8'. the three Cross_Attention blocks
-  const bool grouped = attn_multi_ok(c);
-  // batch 1 of the weight gradients (heads, cross_attention_mlp, cross_*_mlp) -- in the grouped mode together with the
-  // Cross_Attention input_proj dW, right behind the pooling backward that produces their dz
-  if (!ca_dw_grouped) RET(flush_dw(c));
-  if (grouped) {   // one grouped launch on the caller's stream, then the early key-projection backwards leave for their lanes
+  // 7'. query_proj: dW/db per modality, d_q = sum_m d_qp[m] W_q[m]
+  query_proj_dw_queue(c);
+  for (int m = 0; per_layer && m < 3; ++m) {
+    sdumc_gemm gx = G_(SDUMC_NN, M7, D, D);
+    gx.A[0] = c.p(pl.d_qp) + (int64_t)m * M7 * D;
+    gx.lda = D;
+    gx.B[0] = c.P + pm.ca_q[m].w;
+    gx.ldb = D;
+    gx.C[0] = c.p(pl.d_q);
+    gx.ldc = D;
+    gx.accumulate = m > 0;
+    RET(run(c, gx));
+  }
+  // 6'. the 7 query MLPs
+  //   the external gradient of text_hidden (= q[:, 5]) joins d_q inside the same launch
+  if (per_layer)
+    RET(sdumc_relu_drop_bwd_add_(c.p(pl.d_q), c.p(pl.q), s_mlp, c.p(pl.d_q), 7LL * V * D, og.d_text_hidden, NQ * D, 5 * D, D,
+                                 c.st));
+  GroupPtrs qq = {c.p(pl.d_q), D, NQ * D, c.p(pl.qin), (int64_t)V * D, D, dx(pl.d_qin), (int64_t)V * D, D};
+  RET(lin_bwd_grouped(c, pm.query, 7, V, qq));
+  if (sch.flush2_after_query) RET(flush_dw(c));   // batch 2
+  // 5'. fusion algebra (d_alpha already holds the second-level contribution)
+  if (per_layer) RET(sdumc_fusion_bwd(c.p(pl.u), c.p(pl.alpha), c.p(pl.d_qin), c.p(pl.d_u), c.p(pl.d_alpha), V, c.st));
+  // 4'. fc_att, attention_mlp
+  RET(lin_bwd(c, pm.fc_att, c.p(pl.d_alpha), 3, c.p(pl.att2), D, V, dx(pl.d_att2), D, 0, c.p(pl.att2), s_mlp));
+  RET(lin_bwd(c, pm.att3, c.p(pl.d_att2), D, c.p(pl.att1), D, V, dx(pl.d_att1), D, 0, c.p(pl.att1), s_mlp));
+  //   d_u = (fusion part + att0 part) masked by u: the accumulate runs first, then the mask
+  RET(lin_bwd(c, pm.att0, c.p(pl.d_att1), D, c.p(pl.u), 3 * D, V, dx(pl.d_u), 3 * D, 1, c.p(pl.u), s_mlp));
+  // 3'. audio/text/video_mlp
+  GroupPtrs q3 = {c.p(pl.d_u), D, 3 * D, c.p(pl.u1), (int64_t)V * D, D, dx(pl.d_u1), (int64_t)V * D, D,
+                  c.p(pl.u1), s_mlp};
+  RET(lin_bwd_grouped(c, pm.umlp3, 3, V, q3));
+  GroupPtrs q0 = {c.p(pl.d_u1), (int64_t)V * D, D, c.p(pl.hpre), (int64_t)V * D, D, dx(pl.d_hpre), (int64_t)V * D, D};
+  return lin_bwd_grouped(c, pm.umlp0, 3, V, q0);
+}
+
+// 8'. the three Cross_Attention blocks: their pooling backward and the early key-projection backwards
+int bwd_cross_pool(const Ctx& c, const BwdSchedule& sch, hipEvent_t* early_done) {
+  const Plan& pl = c.pl;
+  const int64_t VQD = (int64_t)pl.V * NQ * D;
+  if (sch.flush1_after_pool) RET(flush_dw(c));
+  if (sch.pool_grouped) {   // one grouped launch on the caller's stream, then the early key-projection backwards leave for their lanes
     sdumc_attnpool_bwd_t bb[4];
     int n = 0;
-    float* ws = fra_fold(c) ? c.p(pl.dq_ws) : c.scr;   // folded: the slabs outlive this launch (stage 7'-3' sums them)
+    const bool fold = sch.fra_fold;
+    float* ws = fold ? c.p(pl.dq_ws) : c.scr;   // folded: the slabs outlive this launch (stage 7'-3' sums them)
     const int order[3] = {0, 2, 1};
     for (int oi = 0; oi < 3; ++oi) {
       const int m = order[oi];
       for (const Seg& sg : pl.segs[m]) {
         sdumc_attnpool_bwd_t& b = bb[n++];
-        memset(&b, 0, sizeof(b));
-        b.f = attn_desc(c, 1, m, sg);
-        const int64_t voff = (int64_t)sg.s0 * pl.B * NQ * D;
-        b.dout = c.p(pl.d_ca_out) + (int64_t)m * V * NQ * D + voff;
-        b.dq = c.p(pl.d_qp) + (int64_t)m * V * NQ * D + voff;
-        if (c.h()) {
-          b.dz = reinterpret_cast<float*>(c.ph(pl.dz[1][m], sg.row0 * D));
-          b.dxd = reinterpret_cast<float*>(c.ph(pl.dxd[1][m], sg.row0 * D));
-        } else {
-          b.dz = c.p(pl.dz[1][m]) + sg.row0 * D;
-          b.dxd = c.p(pl.dxd[1][m]) + sg.row0 * D;
-        }
-        if (dxfold(c, m)) { b.dxd = nullptr; b.dout_masked = c.p(pl.dom[1][m]) + voff; }
+        b = fill_pool_bwd(c, 1, m, sg, c.p(pl.d_ca_out) + m * VQD, c.p(pl.d_qp) + m * VQD);
         const size_t bytes = sdumc_attnpool_bwd_workspace_bytes(sg.V, sg.T, NQ);
         b.workspace = ws;
         b.workspace_bytes = bytes;
-        if (fra_fold(c)) {      // the clustered stage 7'-3' behind this launch sums the chunks
+        if (fold) {      // the clustered stage 7'-3' behind this launch sums the chunks
           b.f.partial_only = 1;
           c.dq_part[m] = ws;
           c.dq_nchunk[m] = (sg.T + 63) / 64;
@@ -2339,127 +2437,121 @@ int backward(const Ctx& c, const sdumc_net_grads& og, int phases = 3) {
     }
     RET(sdumc_attnpool_bwd_multi(bb, n, c.st));
     for (int m = 0; m < 3; ++m)
-      if (ca_dw_mask & (1 << m)) keys_dw_queue(c, m, 1, 2);
-    RET(early_keys());
+      if (sch.mod[m].ca_dw_grouped) keys_dw_queue(c, m, 1, 2);
     // (no flush here: a persistent launch now would hold every CU's registers while the latency-bound utterance-level stage
     //  7'-3' -- 256 co-resident workgroups -- is trying to start: measured +135 us on that stage.  The queued problems leave
     //  with the FRA2UTT ones, beside the dX products of the frame-level part.)
+    return early_keys(c, sch, early_done);
   }
-  if (!grouped) RET(fork_all(c));
+  RET(fork_all(c));
   hipEvent_t pooled[3] = {nullptr, nullptr, nullptr};   // per side lane: its pooling backward is done (partial join)
-  for (int m = 0; !grouped && m < 3; ++m) {
+  for (int m = 0; m < 3; ++m) {
+    const BwdSchedule::Mod& M = sch.mod[m];
     c.use(LANE_OF[m]);
-    RET(pool_bwd(c, 1, m, c.p(pl.d_ca_out) + (int64_t)m * V * NQ * D, c.p(pl.d_qp) + (int64_t)m * V * NQ * D));
-    if (own_lane & bgb & (1 << m)) {   // the input_proj backward has everything it needs: stay on this lane, beside 7'-3'
+    RET(pool_bwd(c, 1, m, c.p(pl.d_ca_out) + m * VQD, c.p(pl.d_qp) + m * VQD));
+    if (M.early && M.early_lane != 3) {   // the input_proj backward has everything it needs: stay on this lane, beside 7'-3'
       pooled[LANE_OF[m]] = next_event(c);
       if (hipEventRecord(pooled[LANE_OF[m]], c.st) != hipSuccess) return SDUMC_ELAUNCH;
       RET(keys_gemm_bwd(c, m, 1, 2));
-    } else if (bgb & (1 << m)) {       // same, through the background lane
+    } else if (M.early) {                 // same, through the background lane
       RET(link(c, LANE_OF[m], 3));
       c.use(3);
       RET(keys_gemm_bwd(c, m, 1, 2));
-      RET(record_early(m));
+      RET(record_early(c, m, early_done));
     }
   }
   c.use(0);
-  for (int lane = 1; !grouped && lane <= 2; ++lane) {
+  for (int lane = 1; lane <= 2; ++lane) {
     if (pooled[lane]) {
       if (hipStreamWaitEvent(c.sts[0], pooled[lane], 0) != hipSuccess) return SDUMC_ELAUNCH;
     } else {
       RET(link(c, lane, 0));
     }
   }
-  if (chain) {
-    // 7'-3' in one launch; dW of these layers queued for lane 3
-    const sdumc_chain_args ca = chain_args(c, false, &og, true);
-    mark(c.st, 7);
-    RET(chain_launch(c, ca, 3));
-    mark(c.st, 8);
-    const int M7 = V * NQ;
-    {
-      sdumc_gemm gw = G_(SDUMC_TN, D, D, M7, 3);
-      for (int m = 0; m < 3; ++m) {
-        gw.A[m] = c.p(pl.d_qp) + (int64_t)m * M7 * D;
-        gw.B[m] = c.p(pl.q);
-        gw.C[m] = c.G + pm.ca_q[m].w;
-        gw.colsum_a[m] = c.G + pm.ca_q[m].b;
-      }
-      gw.lda = gw.ldb = gw.ldc = D;
-      c.deferred.push_back(gw);
+  return SDUMC_OK;
+}
+
+// the mask-sum of stream s of modality m: dx = sum of the (up to) four masked paths into the projected features
+sdumc_dropsum dx_mask_sum(const Ctx& c, int m, int s) {
+  const Plan& pl = c.pl;
+  const int T = pl.T[m][s];
+  sdumc_dropsum ds;
+  memset(&ds, 0, sizeof(ds));
+  ds.samples = pl.B;
+  ds.T = T;
+  ds.dx = c.p(pl.dx[m][s]);
+  int nt = 0;
+  for (int k = 0; k < 2; ++k)
+    for (int ss = 0; ss < pl.S; ++ss) {
+      if (m == 1 && ss != s) continue;
+      int64_t roff = 0;  // virtual-row offset of stream ss inside modality m
+      for (int q = 0; q < ss; ++q) roff += (int64_t)pl.B * pl.T[m][q];
+      ds.g[nt] = c.act(pl.dxd[k][m], roff * D);
+      ds.drop[nt] = in_drop(c, k, m, T, ss, roff);   // row space of this term = stream ss alone
+      ds.stream_idx[nt] = 0;
+      ++nt;
     }
-    GroupPtrs qq = {c.p(pl.d_q), D, NQ * D, c.p(pl.qin), (int64_t)V * D, D, nullptr, 0, 0};
-    RET(lin_bwd_grouped(c, pm.query, 7, V, qq));
-    RET(lin_bwd(c, pm.fc_att, c.p(pl.d_alpha), 3, c.p(pl.att2), D, V, nullptr, 0, 0));
-    RET(lin_bwd(c, pm.att3, c.p(pl.d_att2), D, c.p(pl.att1), D, V, nullptr, 0, 0));
-    RET(lin_bwd(c, pm.att0, c.p(pl.d_att1), D, c.p(pl.u), 3 * D, V, nullptr, 0, 0));
-    GroupPtrs q3 = {c.p(pl.d_u), D, 3 * D, c.p(pl.u1), (int64_t)V * D, D, nullptr, 0, 0};
-    RET(lin_bwd_grouped(c, pm.umlp3, 3, V, q3));
-    GroupPtrs q0 = {c.p(pl.d_u1), (int64_t)V * D, D, c.p(pl.hpre), (int64_t)V * D, D, nullptr, 0, 0};
-    RET(lin_bwd_grouped(c, pm.umlp0, 3, V, q0));
-  } else {
-  // 7'. query_proj: dW/db per modality, d_q = sum_m d_qp[m] W_q[m]
-  {
-    const int M = V * NQ;
-    sdumc_gemm gw = G_(SDUMC_TN, D, D, M, 3);
-    for (int m = 0; m < 3; ++m) {
-      gw.A[m] = c.p(pl.d_qp) + (int64_t)m * M * D;
-      gw.B[m] = c.p(pl.q);
-      gw.C[m] = c.G + pm.ca_q[m].w;
-      gw.colsum_a[m] = c.G + pm.ca_q[m].b;
-    }
-    gw.lda = gw.ldb = gw.ldc = D;
-    c.deferred.push_back(gw);
-      for (int m = 0; m < 3; ++m) {
-      sdumc_gemm gx = G_(SDUMC_NN, M, D, D);
-      gx.A[0] = c.p(pl.d_qp) + (int64_t)m * M * D;
-      gx.lda = D;
-      gx.B[0] = c.P + pm.ca_q[m].w;
-      gx.ldb = D;
-      gx.C[0] = c.p(pl.d_q);
-      gx.ldc = D;
-      gx.accumulate = m > 0;
-      RET(run(c, gx));
-    }
+  ds.terms = nt;
+  if (c.h()) ds.bf16 = 1;          // (dx is a half-length buffer: its float offset is its start either way)
+  return ds;
+}
+
+// grouped mode: modality m's frame_dim_reshape dW = dx^T features (+ db), the streams as K segments
+sdumc_gg_problem frame_dw_problem(const Ctx& c, int m) {
+  const int din = m == 0 ? c.d.da : (m == 1 ? c.d.dt : c.d.dv);
+  sdumc_gg_problem fq;
+  memset(&fq, 0, sizeof(fq));
+  for (int s = 0; s < (m == 1 ? c.pl.S : 1); ++s) {
+    fq.A[s] = c.act(c.pl.dx[m][s]);
+    fq.B[s] = feat_in(c, m, s);
+    fq.K[s] = c.pl.B * c.pl.T[m][s];
+    fq.b_map[s] = feat_map(c, m, s);      // (a resident store's packed rows, read in place)
   }
-  // 6'. the 7 query MLPs
-  {
-    //   the external gradient of text_hidden (= q[:, 5]) joins d_q inside the same launch
-    RET(sdumc_relu_drop_bwd_add_(c.p(pl.d_q), c.p(pl.q), s_mlp, c.p(pl.d_q), 7LL * V * D, og.d_text_hidden, NQ * D, 5 * D, D,
-                                 c.st));
-    GroupPtrs qq = {c.p(pl.d_q), D, NQ * D, c.p(pl.qin), (int64_t)V * D, D, c.p(pl.d_qin), (int64_t)V * D, D};
-    RET(lin_bwd_grouped(c, pm.query, 7, V, qq));
+  fq.C = c.G + c.pm.frame[m].w;
+  fq.colsum_a = c.G + c.pm.frame[m].b;
+  fq.M = D;
+  fq.N = din;
+  fq.lda = D;
+  fq.ldb = din;
+  fq.ldc = din;
+  fq.b_scale = 1.f;
+  return fq;
+}
+// ... and per stream, where the grouped kernel does not take the shape
+int frame_dw_per_layer(const Ctx& c, int m, int s) {
+  const int din = m == 0 ? c.d.da : (m == 1 ? c.d.dt : c.d.dv), rows = c.pl.B * c.pl.T[m][s];
+  auto fill = [&](auto& g) {      // dW_frame = dx^T features; A = dx in the call's storage
+    g.lda = D;
+    g.B[0] = feat_in(c, m, s);
+    g.ldb = g.ldc = din;
+    g.C[0] = c.G + c.pm.frame[m].w;
+    g.colsum_a[0] = c.G + c.pm.frame[m].b;
+    g.accumulate = s > 0;
+  };
+  if (c.h()) {
+    sdumc_gemm_bf16 gh = GH_(SDUMC_TN, D, din, rows);
+    gh.A[0] = c.ph(c.pl.dx[m][s]);
+    fill(gh);
+    return run_h(c, gh);
   }
-  if (!gg_utt(c)) RET(flush_dw(c));   // batch 2: query_proj, the query MLPs (grouped mode: they wait for batch 3)
-  // 5'. fusion algebra (d_alpha already holds the second-level contribution)
-  RET(sdumc_fusion_bwd(c.p(pl.u), c.p(pl.alpha), c.p(pl.d_qin), c.p(pl.d_u), c.p(pl.d_alpha), V, c.st));
-  // 4'. fc_att, attention_mlp
-  RET(lin_bwd(c, pm.fc_att, c.p(pl.d_alpha), 3, c.p(pl.att2), D, V, c.p(pl.d_att2), D, 0, c.p(pl.att2), s_mlp));
-  RET(lin_bwd(c, pm.att3, c.p(pl.d_att2), D, c.p(pl.att1), D, V, c.p(pl.d_att1), D, 0, c.p(pl.att1), s_mlp));
-  //   d_u = (fusion part + att0 part) masked by u: the accumulate runs first, then the mask
-  RET(lin_bwd(c, pm.att0, c.p(pl.d_att1), D, c.p(pl.u), 3 * D, V, c.p(pl.d_u), 3 * D, 1, c.p(pl.u), s_mlp));
-  // 3'. audio/text/video_mlp
-  {
-    GroupPtrs q3 = {c.p(pl.d_u), D, 3 * D, c.p(pl.u1), (int64_t)V * D, D, c.p(pl.d_u1), (int64_t)V * D, D,
-                    c.p(pl.u1), s_mlp};
-    RET(lin_bwd_grouped(c, pm.umlp3, 3, V, q3));
-    GroupPtrs q0 = {c.p(pl.d_u1), (int64_t)V * D, D, c.p(pl.hpre), (int64_t)V * D, D, c.p(pl.d_hpre), (int64_t)V * D, D};
-    RET(lin_bwd_grouped(c, pm.umlp0, 3, V, q0));
-  }
-  }   // !chain
-  // batch 3: fc_att, attention_mlp, audio/text/video_mlp.  Grouped mode with the frame-level part following in this call:
-  // they stay queued and ride with the FRA2UTT input_proj dW in one launch (below).
-  if (!(ggf && (phases & 2))) RET(flush_dw(c));
-  // the dW GEMMs of this part ran on lane 3: after this link [0, pm.early) is final on the caller's stream.  When the
-  // frame-level part follows in the same call the link at its end does the same job.
-  if (!(phases & 2)) RET(link(c, 3, 0));
-  }   // phases & 1
-  if (!(phases & 2)) return SDUMC_OK;
-  // 2'+1'. three independent per-modality chains, one per lane:
-  //   fra2utt_m pooling backward (the shared context vector's gradient = sum of the per-sample dq)
-  //   -> input_proj backward of both sites (grouped) -> dx = sum of the (up to) four masked paths into the
-  //   projected features -> frame_dim_reshape_m: dW = dx^T feat with db fused
+  sdumc_gemm g = G_(SDUMC_TN, D, din, rows);
+  g.A[0] = c.p(c.pl.dx[m][s]);
+  fill(g);
+  g.bf16 = c.d.bf16 && (din % 4 == 0) ? 1 : 0;
+  return run(c, g);
+}
+
+// 2'+1'. three independent per-modality chains, one per lane:
+//   fra2utt_m pooling backward (the shared context vector's gradient = sum of the per-sample dq)
+//   -> input_proj backward of both sites (grouped) -> dx = sum of the (up to) four masked paths into the
+//   projected features -> frame_dim_reshape_m: dW = dx^T feat with db fused
+int bwd_frame(const Ctx& c, const BwdSchedule& sch, const hipEvent_t* early_done) {
+  const Plan& pl = c.pl;
+  const ParamMap& pm = c.pm;
+  const int V = pl.V;
   RET(fork_all(c));
   for (int m = 0; m < 3; ++m) {       // pass 1: the pooling backward of every modality (produces dz of the FRA2UTT site)
+    const BwdSchedule::Mod& M = sch.mod[m];
     c.use(LANE_OF[m]);
     float* dq = c.p(pl.dq_fra) + (int64_t)m * V * D;
     // (the context vector is one query shared by every sample: its gradient, the sum over the samples' dq, leaves the pooling
@@ -2468,13 +2560,13 @@ int backward(const Ctx& c, const sdumc_net_grads& og, int phases = 3) {
     RET(pool_bwd(c, 0, m, c.p(pl.d_hpre) + (int64_t)m * V * D, dq, ctx_grad));
     if (!ctx_grad) RET(colsum(c, dq, V, D, D, c.G + pm.fra_ctx[m], 0));
     mark(c.st, 12 + 5 * m);      // (debug marks 12..26: this modality's lane, frame-level backward)
-    if (fra_dw_mask & (1 << m)) {
+    if (M.fra_dw_grouped) {
       keys_dw_queue(c, m, 0, 1);
-      if (!(ca_dw_mask & (1 << m)) && !(bgb & (1 << m))) keys_dw_queue(c, m, 1, 2);   // (the Cross_Attention one, when it did not leave in phase 0)
+      if (M.ca_dw_late) keys_dw_queue(c, m, 1, 2);
       if (!c.capturing) RET(link(c, LANE_OF[m], 3));   // lane 3 (the grouped launch below) needs this lane's dz
     }
   }
-  if (ggf) {   // every queued utterance-level dW and the input_proj dW: one launch on lane 3, beside the dX products below
+  if (sch.dw_grouped) {   // every queued utterance-level dW and the input_proj dW: one launch on lane 3, beside the dX products below
     c.use(0);
     // (under hipGraph capture three lanes -> lane 3 -> lane 0 is the dependency pattern hipStreamEndCapture cannot take on this
     //  stack: the lanes meet on the caller's stream instead and fork again)
@@ -2482,130 +2574,38 @@ int backward(const Ctx& c, const sdumc_net_grads& og, int phases = 3) {
     RET(flush_dw(c));
     if (c.capturing) RET(fork_all(c));
   }
-  const bool sum_in_dx_m[3] = {dxsum(c, 0), dxsum(c, 1), dxsum(c, 2)};      // the rows launches add keep . dxd straight into dx: no mask-sum launch, and the FRA2UTT site's
-                                        // launch (which adds onto dx) has to follow the modality's early Cross_Attention one
-  auto await_early = [&](int m) -> int {
-    if (!(bgb & ~own_lane & (1 << m))) return SDUMC_OK;   // dxd of this modality's Cross_Attention site (issued early on lane 3)
-    if (early_done[m]) return hipStreamWaitEvent(c.st, early_done[m], 0) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-    return link(c, 3, LANE_OF[m]);
-  };
   for (int m = 0; m < 3; ++m) {       // pass 2: dX of the key projections, the mask-sum, the frame projection's dW
+    const BwdSchedule::Mod& M = sch.mod[m];
     c.use(LANE_OF[m]);
-    const bool sum_in_dx = sum_in_dx_m[m];
-    if (sum_in_dx) RET(await_early(m));
-    {
-      const int k1 = (bgb & (1 << m)) ? 1 : 2;
-      // which of this modality's key-projection dW products are already on their way in a grouped launch
-      const bool fra_q = (fra_dw_mask & (1 << m)) != 0;
-      const bool ca_q = k1 == 2 && (((ca_dw_mask | fra_dw_mask) & (1 << m)) != 0);
-      // bit m: modality m's key-projection dW (off the dz -> dX -> mask-sum -> frame dW chain) runs on lane 3 (ungrouped modes).
-      // (re-measured with the clustered utterance-level kernels: fp32 1.923 ms with none on lane 3 vs 1.930 with audio's;
-      //  bf16 storage 1.148 vs 1.128 -- so the default follows the mode)
-      const int dw_off = c.h() ? 1 : 0;
-      if (fra_q) {
-        if (k1 == 2 && !ca_q) RET(keys_gemm_bwd(c, m, 1, 2, 1));     // (never in practice: both sites are groupable or neither)
-        RET(keys_gemm_bwd(c, m, 0, k1, 2));
-      } else if (c.multi && !c.capturing && (dw_off & (1 << m))) {
-        RET(link(c, LANE_OF[m], 3));
-        c.use(3);
-        RET(keys_gemm_bwd(c, m, 0, k1, 1));
-        c.use(LANE_OF[m]);
-        RET(keys_gemm_bwd(c, m, 0, k1, 2));
-      } else {
-        RET(keys_gemm_bwd(c, m, 0, k1));
-      }
+    // dx_sum: the FRA2UTT site's launch (which adds onto dx) has to follow the modality's early Cross_Attention one
+    if (M.dx_sum) RET(await_early(c, sch, m, early_done));
+    if (M.fra_dw_grouped) {      // the key-projection dW products are on their way in a grouped launch
+      if (M.k1 == 2 && !M.ca_dw_grouped && !M.ca_dw_late) RET(keys_gemm_bwd(c, m, 1, 2, 1));     // (never: plan_backward queues both sites or neither)
+      RET(keys_gemm_bwd(c, m, 0, M.k1, 2));
+    } else if (M.dw_on_lane3) {
+      RET(link(c, LANE_OF[m], 3));
+      c.use(3);
+      RET(keys_gemm_bwd(c, m, 0, M.k1, 1));
+      c.use(LANE_OF[m]);
+      RET(keys_gemm_bwd(c, m, 0, M.k1, 2));
+    } else {
+      RET(keys_gemm_bwd(c, m, 0, M.k1));
     }
     mark(c.st, 13 + 5 * m);
-    if (!sum_in_dx) RET(await_early(m));
-    sdumc_gg_problem fq;          // grouped mode: this modality's frame_dim_reshape dW, the streams as K segments
-    memset(&fq, 0, sizeof(fq));
-    // grouped or per-layer is decided ONCE per modality: the grouped problem overwrites its output (accumulate = 0) after the
-    // lanes have joined, so a modality whose streams took different paths would lose the per-layer stream's contribution
-    bool frame_grouped = ggf && (c.h() || (din[m] & 3) == 0);
-    for (int s = 0; s < (m == 1 ? S : 1); ++s) {
-      const float* in_s = m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]);
-      if (reinterpret_cast<uintptr_t>(in_s) & 15) frame_grouped = false;
-    }
-    for (int s = 0; s < (m == 1 ? S : 1); ++s) {
-      const int T = pl.T[m][s];
-      sdumc_dropsum ds;
-      memset(&ds, 0, sizeof(ds));
-      ds.samples = B;
-      ds.T = T;
-      ds.dx = c.p(pl.dx[m][s]);
-      int nt = 0;
-      for (int k = 0; k < 2; ++k)
-        for (int ss = 0; ss < S; ++ss) {
-          if (m == 1 && ss != s) continue;
-          int64_t roff = 0;  // virtual-row offset of stream ss inside modality m
-          for (int q = 0; q < ss; ++q) roff += (int64_t)B * pl.T[m][q];
-          ds.g[nt] = c.h() ? reinterpret_cast<const float*>(c.ph(pl.dxd[k][m], roff * D)) : c.p(pl.dxd[k][m]) + roff * D;
-          ds.drop[nt] = in_drop(c, k, m, T, ss, roff);   // row space of this term = stream ss alone
-          ds.stream_idx[nt] = 0;
-          ++nt;
-        }
-      ds.terms = nt;
-      if (c.h()) ds.bf16 = 1;          // (dx is a half-length buffer: its float offset is its start either way)
+    if (!M.dx_sum) RET(await_early(c, sch, m, early_done));
+    for (int s = 0; s < (m == 1 ? pl.S : 1); ++s) {
       if (s == 0) mark(c.st, 14 + 5 * m);     // (after the wait for the early key-projection backward)
-      if (!sum_in_dx) RET(sdumc_dropsum_bwd(&ds, c.st));
+      if (!M.dx_sum) {
+        const sdumc_dropsum ds = dx_mask_sum(c, m, s);
+        RET(sdumc_dropsum_bwd(&ds, c.st));
+      }
       if (s == 0) mark(c.st, 15 + 5 * m);
-      const float* in = m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]);
-      const int rows = B * T;
-      if (c.h() && frame_grouped) {
-        fq.A[s] = reinterpret_cast<const float*>(c.ph(pl.dx[m][s]));
-        fq.B[s] = in;
-        fq.K[s] = rows;
-        fq.b_map[s] = feat_map(c, m, s);      // (a resident store's packed bf16 rows, read in place)
-        continue;
-      }
-      if (c.h() && c.io.row_map[0]) return SDUMC_EINVAL;      // (only the grouped launch fetches its rows through a map)
-      if (c.h()) {     // dW_frame = dx^T features on bf16 storage
-        sdumc_gemm_bf16 gh = GH_(SDUMC_TN, D, din[m], rows);
-        gh.A[0] = c.ph(pl.dx[m][s]);
-        gh.lda = D;
-        gh.B[0] = in;
-        gh.ldb = din[m];
-        gh.C[0] = c.G + pm.frame[m].w;
-        gh.ldc = din[m];
-        gh.colsum_a[0] = c.G + pm.frame[m].b;
-        gh.accumulate = s > 0;
-        RET(run_h(c, gh));
-        continue;
-      }
-      if (frame_grouped) {
-        fq.A[s] = c.p(pl.dx[m][s]);
-        fq.B[s] = in;
-        fq.K[s] = rows;
-        fq.b_map[s] = feat_map(c, m, s);      // (a resident store's packed rows, read in place)
-        continue;
-      }
-      if (c.io.row_map[0]) return SDUMC_EINVAL;      // (only the grouped launch fetches its rows through a map)
-      sdumc_gemm g = G_(SDUMC_TN, D, din[m], rows);
-      g.A[0] = c.p(pl.dx[m][s]);
-      g.lda = D;
-      g.B[0] = in;
-      g.ldb = din[m];
-      g.C[0] = c.G + pm.frame[m].w;
-      g.ldc = din[m];
-      g.colsum_a[0] = c.G + pm.frame[m].b;
-      g.accumulate = s > 0;
-      g.bf16 = c.d.bf16 && (din[m] % 4 == 0) ? 1 : 0;
-      RET(run(c, g));
+      if (!M.frame_dw_grouped) RET(frame_dw_per_layer(c, m, s));
     }
-    if (fq.K[0] > 0) {
-      fq.C = c.G + pm.frame[m].w;
-      fq.colsum_a = c.G + pm.frame[m].b;
-      fq.M = D;
-      fq.N = din[m];
-      fq.lda = D;
-      fq.ldb = din[m];
-      fq.ldc = din[m];
-      fq.b_scale = 1.f;
-      // (measured and dropped, round 5: the text slot's frame dW -- its dx is final long before audio's -- as a launch of its own on
-      //  text's lane, beside the other modalities' dX launches: 1.425-1.431 against 1.390-1.395 ms; a persistent launch in the middle
-      //  of the backward holds the CUs the dX chain is waiting for)
-      (c.h() ? c.ggh : c.gg).push_back(fq);
-    }
+    // (measured and dropped, round 5: the text slot's frame dW -- its dx is final long before audio's -- as a launch of its own on
+    //  text's lane, beside the other modalities' dX launches: 1.425-1.431 against 1.390-1.395 ms; a persistent launch in the middle
+    //  of the backward holds the CUs the dX chain is waiting for)
+    if (M.frame_dw_grouped) (c.h() ? c.ggh : c.gg).push_back(frame_dw_problem(c, m));
   }
   c.use(0);
   for (int m = 0; m < 3; ++m) mark(c.sts[LANE_OF[m]], 16 + 5 * m);
@@ -2615,8 +2615,24 @@ int backward(const Ctx& c, const sdumc_net_grads& og, int phases = 3) {
   // every modality's dx is there
   if (!c.gg.empty() || !c.ggh.empty()) RET(flush_dw_on(c, 0, 0, 1));
   mark(c.st, 41);
-  RET(link(c, 3, 0));   // the dW launches of lane 3
-  return SDUMC_OK;
+  return link(c, 3, 0);   // the dW launches of lane 3
+}
+
+int backward(const Ctx& c, const sdumc_net_grads& og, const BwdSchedule& sch) {
+  RET(sch.rc);
+  hipEvent_t early_done[3] = {nullptr, nullptr, nullptr};
+  if (sch.utterance) {
+    // every live gradient tensor is overwritten below when all five output gradients are given
+    if (!og.d_vals || !og.d_fused || !og.d_rnc || !og.d_text_hidden || !og.d_cross_text) RET(sdumc_fill(c.G, 0.f, c.pm.live, c.st));
+    RET(bwd_heads(c, og, sch));
+    RET(bwd_cross_pool(c, sch, early_done));
+    RET(bwd_stage_a(c, og, sch));
+    if (sch.flush3_after_utt) RET(flush_dw(c));
+    // the dW GEMMs of this part ran on lane 3: after this link [0, pm.early) is final on the caller's stream.  When the
+    // frame-level part follows in the same call the link at its end does the same job.
+    if (!sch.frame) RET(link(c, 3, 0));
+  }
+  return sch.frame ? bwd_frame(c, sch, early_done) : SDUMC_OK;
 }
 
 // hyper != nullptr: also the Adam bias-correction update of this step (adam.hip's adam_hyper_kernel, same double
@@ -2751,6 +2767,15 @@ extern "C" size_t sdumc_net_workspace_bytes(const sdumc_net_dims* d) {
 }
 
 namespace {
+// plan, workspace and lanes of one network-level call (the caller holds the SplitScope of c.io)
+int ctx_init(Ctx& c) {
+  if (!make_plan(c.d, c.pl)) return SDUMC_EINVAL;
+  if (c.io.workspace_bytes < (size_t)c.pl.cur * sizeof(float)) return SDUMC_ENOMEM;
+  c.W = static_cast<float*>(c.io.workspace);
+  c.P = c.io.params;
+  c.init_lanes();
+  return SDUMC_OK;
+}
 // join_bits: order the middle's fill of the other keep-bits set (lane 3, issued behind the last lane-3 -> caller link of forward())
 // before `stream` on return.  sdumc_train_step leaves that to its backward's final join; a forward on its own must not return with
 // lane 3 still reading rng_state / writing bits_next behind the caller's back (and, under capture, with an unjoined branch).
@@ -2758,11 +2783,7 @@ int net_forward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, void* stre
   RET(check_io(d, io));
   const SplitScope split_scope(io);
   Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
-  if (!make_plan(*d, c.pl)) return SDUMC_EINVAL;
-  if (io->workspace_bytes < (size_t)c.pl.cur * sizeof(float)) return SDUMC_ENOMEM;
-  c.W = static_cast<float*>(io->workspace);
-  c.P = io->params;
-  c.init_lanes();
+  RET(ctx_init(c));
   RET(forward(c));
   if (join_bits && (bits_pregen(c) || io->prefetch)) RET(link(c, 3, 0));
   return SDUMC_OK;
@@ -2772,34 +2793,24 @@ extern "C" int sdumc_net_forward(const sdumc_net_dims* d, const sdumc_net_io* io
   return net_forward_impl(d, io, stream, true);
 }
 
-extern "C" int sdumc_net_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g,
-                                  void* stream) {
+namespace {
+// the schedule is decided -- and a batch it cannot serve rejected -- before anything of the call is enqueued
+int net_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g, int phases, void* stream) {
   RET(check_io(d, io));
   const SplitScope split_scope(io);
-  if (!g || !g->grads || (reinterpret_cast<uintptr_t>(g->grads) & 15)) return SDUMC_EINVAL;
+  if (!g || !g->grads || (reinterpret_cast<uintptr_t>(g->grads) & 15) || phases == 0) return SDUMC_EINVAL;      // (0: a phase other than 0 / 1)
   Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
-  if (!make_plan(*d, c.pl)) return SDUMC_EINVAL;
-  if (io->workspace_bytes < (size_t)c.pl.cur * sizeof(float)) return SDUMC_ENOMEM;
-  c.W = static_cast<float*>(io->workspace);
-  c.P = io->params;
+  RET(ctx_init(c));
   c.G = g->grads;
-  c.init_lanes();
-  return backward(c, *g);
+  return backward(c, *g, plan_backward(c, phases));
 }
-
+}  // namespace
+extern "C" int sdumc_net_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g, void* stream) {
+  return net_backward_impl(d, io, g, 3, stream);
+}
 extern "C" int sdumc_net_backward_phase(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g,
                                         int32_t phase, void* stream) {
-  RET(check_io(d, io));
-  const SplitScope split_scope(io);
-  if (!g || !g->grads || (reinterpret_cast<uintptr_t>(g->grads) & 15) || phase < 0 || phase > 1) return SDUMC_EINVAL;
-  Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
-  if (!make_plan(*d, c.pl)) return SDUMC_EINVAL;
-  if (io->workspace_bytes < (size_t)c.pl.cur * sizeof(float)) return SDUMC_ENOMEM;
-  c.W = static_cast<float*>(io->workspace);
-  c.P = io->params;
-  c.G = g->grads;
-  c.init_lanes();
-  return backward(c, *g, 1 << phase);
+  return net_backward_impl(d, io, g, phase < 0 || phase > 1 ? 0 : 1 << phase, stream);
 }
 extern "C" int64_t sdumc_param_early_count(int32_t da, int32_t dt, int32_t dv) { return build_params(da, dt, dv).early; }
 
@@ -2934,8 +2945,6 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   sdumc_net_io nio = *io;
   nio.workspace = base + sl.net;
   nio.workspace_bytes = sl.total - sl.net;
-  mark(static_cast<hipStream_t>(stream), 0);
-  RET(net_forward_impl(d, &nio, stream, false));
   const size_t V = (size_t)d->B * 2;
   float* dout = reinterpret_cast<float*>(base + sl.dout);
   sdumc_net_grads g;
@@ -2945,11 +2954,20 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   g.d_text_hidden = g.d_rnc + RD * V;
   g.d_cross_text = g.d_text_hidden + D * V;
   g.grads = reinterpret_cast<float*>(base + sl.grads);
+  // the backward's schedule first: a batch it cannot serve is rejected before the forward, the loss or a fork is enqueued
+  const SplitScope split_scope(&nio);
+  Ctx bc{*d, nio, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
+  RET(ctx_init(bc));
+  bc.G = g.grads;
+  const BwdSchedule sch = plan_backward(bc, 3);
+  RET(sch.rc);
+  mark(static_cast<hipStream_t>(stream), 0);
+  RET(net_forward_impl(d, &nio, stream, false));
   // the Adam bias-correction update rides in the loss's last launch, the dropout call counter in the Adam launch
   bool total_pending = false;
   RET(loss_backward_impl(d, &nio, cfg, &g, base + sl.loss, sl.net - sl.loss, stream, cfg->hyper, &total_pending));
   mark(static_cast<hipStream_t>(stream), 5);
-  RET(sdumc_net_backward(d, &nio, &g, stream));
+  RET(backward(bc, g, sch));
   mark(static_cast<hipStream_t>(stream), 9);
   sdumc_total_loss tl;
   tl.losses = cfg->losses;

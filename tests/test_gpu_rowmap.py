@@ -170,3 +170,188 @@ def test_row_map_argument_contract(env):
             ops.gemm_group_tn([dict(A=dx, B=X, b_map=amap, K=64)])
     finally:
         lib.sdumc_set_split_(prev)
+
+
+# ---- a row-mapped batch the backward's schedule cannot serve (plan_backward's rc) is rejected before anything of the call runs ----
+# The frame projections' weight gradient fetches mapped rows only in the grouped launch, and the grouped launch takes 16-byte aligned
+# operands: a packed fp32 audio tensor at a float-aligned but not 16-byte-aligned address is a batch check_io accepts (the forward reads
+# the planes, never the fp32 tensor) and the backward cannot run.  So is, in fp32 storage, a context whose split option keeps the plane
+# GEMMs of the forward (SDUMC_SPLIT_WIDE) and turns the grouped launch's split arithmetic off (SDUMC_SPLIT_GROUP): only that kernel of
+# the grouped launch reads maps.
+_REASONS = ("misaligned", "split")
+_SPLIT_NO_GROUP = 14      # every family but the grouped weight-gradient launch
+
+
+def _unservable(streams, seed, reason, ctx):
+    """the batch and context state of `reason`; returns (batch, undo)"""
+    if reason == "split":
+        ctx.set_option("split", _SPLIT_NO_GROUP)
+        return _resident_batch(streams, seed), lambda: ctx.set_option("split", None)
+    return _resident_batch(streams, seed, misalign_audio=True), lambda: None
+_RB, _RT, _RD = 2, (9, 5, 7, 6), (64, 128, 64, 128)      # B; padded frames and widths of audio, text, video, feat4
+
+
+def _resident_batch(streams, seed, misalign_audio=False):
+    """the (audio, text, video[, feat4]) slots of one batch: packed store tensors with planes and row maps, and the padded copies"""
+    from sdumc_amd import engine
+    n = 3 if streams == 1 else 4
+    out = dict(packed=[], planes=[], maps=[], rows=[], padded=[])
+    for i in range(n):
+        X, starts, lens, rows = _store(5, _RT[i], _RD[i], seed + i)
+        amap, _, Tp = _batch_map(starts, lens, rows, _RB, seed + 10 + i)
+        amap = torch.cat([amap.view(_RB, Tp), torch.full((_RB, _RT[i] - Tp), rows, dtype=torch.int32)], 1).reshape(-1)
+        out["padded"].append(X[amap.cuda().long()].view(_RB, _RT[i], _RD[i]).contiguous())
+        out["planes"].append(engine.p3_split_into(X, engine._planes_buffer(X.shape[0], _RD[i], X.device)))
+        if i == 0 and misalign_audio:
+            buf = torch.zeros(X.numel() + 4, device=X.device)
+            Xm = buf[1:1 + X.numel()].view_as(X)
+            Xm.copy_(X)
+            if Xm.data_ptr() % 16 != 4:
+                pytest.fail("test set-up: the allocator returned a block that is not 16-byte aligned")
+            X = Xm
+        out["packed"].append(X)
+        out["maps"].append(_padded(amap))
+        out["rows"].append(int(X.shape[0]))
+    return out
+
+
+def _flat_params():
+    from oracle import sdumc_oracle as O
+    from sdumc_amd import engine
+    lay = engine.ParamLayout.get(*_RD[:3])
+    flat = torch.zeros(lay.total)
+    P = O.init_params(_RD, seed=1)
+    for k, v in lay.views(flat).items():
+        v.copy_(P[k])
+    return flat.cuda()
+
+
+def _bind_store(step, rb, seed):
+    from sdumc_amd import engine
+    labels = torch.randn(_RB, generator=torch.Generator().manual_seed(seed)).cuda()
+    step._bind(engine._Source(tuple(rb["packed"]), tuple(rb["planes"]), rb["maps"], tuple(rb["rows"]), labels))
+
+
+def _map_io(call, rb):
+    """points a NetCall built on the padded copies at the packed store tensors, their planes and the row maps"""
+    io, ptr = call.io, torch.Tensor.data_ptr
+    io.audio, io.text[0], io.video = ptr(rb["packed"][0]), ptr(rb["packed"][1]), ptr(rb["packed"][2])
+    io.audio_p3, io.text_p3[0], io.video_p3 = ptr(rb["planes"][0]), ptr(rb["planes"][1]), ptr(rb["planes"][2])
+    if len(rb["packed"]) == 4:
+        io.text[1], io.text_p3[1] = ptr(rb["packed"][3]), ptr(rb["planes"][3])
+    for i, (m, r) in enumerate(zip(rb["maps"], rb["rows"])):
+        io.row_map[i], io.store_rows[i] = ptr(m), r
+
+
+def _net_call(flat, rb, streams, train, ctx):
+    from sdumc_amd import engine
+    rng = engine.RngState(5, flat.device) if train else None
+    pad = rb["padded"]
+    return engine.NetCall(flat, pad[0], [pad[1]] + ([pad[3]] if streams == 2 else []), pad[2], train, rng, planes=True, ctx=ctx)
+
+
+@pytest.mark.parametrize("reason", _REASONS)
+def test_unservable_row_mapped_train_step_is_rejected_before_anything_runs_and_the_context_stays_usable(env, reason):
+    """sdumc_train_step on a row-mapped batch whose frame dW cannot take the grouped launch: SDUMC_EINVAL with the outputs, the loss
+    record, the whole step workspace (gradient bucket included), the parameters, the Adam state and the dropout counter untouched --
+    no forward, no loss stage, no fork.  The same context then runs a valid row-mapped step bit for bit like a context that never saw
+    the rejected call (no lane left forked, no event left recorded)."""
+    _lib, ops = env
+    from sdumc_amd import engine
+    good = _resident_batch(2, 40)
+    steps = []
+    for rejected_first in (True, False):
+        flat = _flat_params()
+        ctx = engine.ExecContext()
+        step = engine.TrainStep(flat, _RB, _RT, _RD, seed=3, planes=True, ctx=ctx)
+        if rejected_first:
+            bad, undo = _unservable(2, 40, reason, ctx)
+            _bind_store(step, bad, 7)
+            outs = (step.vals, step.fused, step.rnc, step.text_hidden, step.cross_text, step.losses, step.grads)
+            for t in outs:
+                t.fill_(-77.0)
+            step.adam_m.fill_(0.25)
+            step.adam_v.fill_(0.5)
+            state = (flat, step.adam_m, step.adam_v, step.hyper, step.rng.t, step.workspace)
+            before = [t.clone() for t in state]
+            torch.cuda.synchronize()
+            with pytest.raises(_lib.SdumcError, match="SDUMC_EINVAL"):
+                step.launch()
+            torch.cuda.synchronize()
+            for t in outs:
+                assert bool((t == -77.0).all()), "a launch of the rejected step wrote an output"
+            for t, b in zip(state, before):
+                assert torch.equal(t, b), "the rejected step changed state"
+            undo()
+            step.adam_m.zero_()
+            step.adam_v.zero_()
+            step.grads.zero_()
+        _bind_store(step, good, 7)
+        losses = step.run().clone()
+        torch.cuda.synchronize()
+        steps.append((losses, flat, step.adam_m, step.adam_v, step.hyper))
+    assert bool(torch.isfinite(steps[0][0]).all()) and float(steps[0][2].abs().max()) > 0
+    for a, b in zip(*steps):
+        assert torch.equal(a, b), "a step after the rejected call differs from one on a fresh context"
+
+
+@pytest.mark.parametrize("reason", _REASONS)
+@pytest.mark.parametrize("streams", [1, 2])
+def test_unservable_row_mapped_backward_is_rejected_before_anything_runs(env, streams, reason):
+    """sdumc_net_backward, and BOTH phases of sdumc_net_backward_phase (the rejection is a property of the frame-level part, and the
+    first phase already returns it), after a successful forward: SDUMC_EINVAL, gradient bucket and workspace untouched."""
+    _lib, ops = env
+    from sdumc_amd import engine
+    lib = _lib.lib
+    ctx = engine.ExecContext()
+    rb, undo = _unservable(streams, 50, reason, ctx)
+    flat = _flat_params()
+    call = _net_call(flat, rb, streams, True, ctx)
+    _map_io(call, rb)
+    outs = call.forward()
+    g = torch.Generator(device="cuda").manual_seed(2)
+    og = [torch.randn(t.shape, device="cuda", generator=g) for t in outs]
+    grads = torch.full((call.layout.live,), -77.0, device="cuda")
+    ng = _lib.NetGrads()
+    ng.d_vals, ng.d_fused, ng.d_rnc, ng.d_text_hidden, ng.d_cross_text = (t.data_ptr() for t in og)
+    ng.grads = grads.data_ptr()
+    torch.cuda.synchronize()
+    ws = call.workspace.clone()
+    args = (C.byref(call.dims), C.byref(call.io), C.byref(ng))
+    calls = [lambda: lib.sdumc_net_backward(*args, _lib.current_stream()),
+             lambda: lib.sdumc_net_backward_phase(*args, 0, _lib.current_stream()),
+             lambda: lib.sdumc_net_backward_phase(*args, 1, _lib.current_stream())]
+    for fn in calls:
+        with pytest.raises(_lib.SdumcError, match="SDUMC_EINVAL"):
+            _lib.check(fn(), "backward")
+        torch.cuda.synchronize()
+        assert bool((grads == -77.0).all()) and torch.equal(call.workspace, ws), "a launch of the rejected backward ran"
+    # the context is usable: the aligned form of the same batch runs, and its bucket is finite and non-trivial
+    undo()
+    ok = _resident_batch(streams, 50)
+    _map_io(call, ok)
+    call.forward()
+    _lib.check(calls[0](), "sdumc_net_backward")
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(grads).all()) and float(grads.abs().max()) > 0
+
+
+@pytest.mark.parametrize("reason", _REASONS)
+@pytest.mark.parametrize("streams", [1, 2])
+def test_forward_still_accepts_the_batch_the_backward_rejects(env, streams, reason):
+    """eval-mode sdumc_net_forward reads the planes through the maps and never the fp32 tensors: on the batch the backward rejects it
+    gives, bit for bit, the outputs of the padded copy of the same batch."""
+    _lib, ops = env
+    from sdumc_amd import engine
+    ctx = engine.ExecContext()
+    rb, _ = _unservable(streams, 60, reason, ctx)
+    flat = _flat_params()
+    call = _net_call(flat, rb, streams, False, ctx)
+    want = [t.clone() for t in call.forward()]
+    _map_io(call, rb)
+    for t in (call.vals, call.fused, call.rnc, call.text_hidden, call.cross_text):
+        t.fill_(-77.0)
+    got = call.forward()
+    torch.cuda.synchronize()
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
