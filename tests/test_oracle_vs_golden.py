@@ -187,3 +187,81 @@ def test_blocks_default_width_1024(golden):
     close(o, g["fra_train_out"], 5e-6); close(a, g["fra_train_att"], 5e-6)
     o, a = O.cross_attention(P, 0, q, x, d)
     close(o, g["ca_train_out"], 5e-6); close(a, g["ca_train_att"], 5e-6)
+
+
+# ---- oracle/rnc_reference.py: the float64 restatement with intermediates that the GPU loss-kernel tests compare against ------------
+class _TwoViews:
+    """features[:, v] of RnCLoss for any split of the rows: lets rnc_loss, written for [B, 2, d], run over an odd number of rows."""
+
+    def __init__(self, *views):
+        self.views = views
+
+    def __getitem__(self, idx):
+        return self.views[idx[1]]
+
+
+class _Labels:
+    def __init__(self, y):
+        self.y = y
+
+    def repeat(self, *_):
+        return self.y
+
+
+@pytest.mark.parametrize("n", [6, 96, 257])
+def test_rnc_reference_matches_rnc_loss_and_autograd(n):
+    """Two independent float64 evaluations (fp32 labels in both, so the same membership): the oracle's literal restatement of
+    RnCLoss.forward differentiated by autograd, and rnc_reference's closed forms.  1e-12 relative, far above float64 rounding at
+    these sizes and far below anything an fp32 kernel is held to."""
+    from oracle.rnc_reference import rnc_reference
+    from tests.loss_bars import rnc_case
+    f32, y = rnc_case(n, 64, "straddle", 2.0)
+    f = f32.double().requires_grad_()
+    h = (n + 1) // 2
+    l = O.rnc_loss(_TwoViews(f[:h], f[h:]), _Labels(y.reshape(-1, 1)))
+    l.backward()
+    r = rnc_reference(f32, y, 2.0)
+    assert abs(float(r.loss) - float(l.detach())) <= 1e-12 * abs(float(l.detach()))
+    assert float((r.df - f.grad).abs().max()) <= 1e-12 * float(f.grad.abs().max())
+    assert torch.equal(r.dist.diagonal(), torch.zeros(n, dtype=torch.float64))
+    assert torch.equal(r.G.diagonal(), torch.zeros(n, dtype=torch.float64))
+    # anchors= gives the same rows
+    rows = [0, n - 1, n // 2]
+    p = rnc_reference(f32, y, 2.0, anchors=rows)
+    for name in ("dist", "rowloss", "G", "D", "S"):
+        assert torch.equal(getattr(p, name), getattr(r, name)[torch.tensor(rows)]), name
+    assert p.loss is None and p.df is None
+
+
+def test_rnc_reference_matches_reference_goldens(golden):
+    g = golden("losses")
+    from oracle.rnc_reference import rnc_reference
+    for tag in ("rnc", "rnctie"):
+        f = T(g[f"{tag}_f"])
+        r = rnc_reference(torch.cat([f[:, 0], f[:, 1]]).contiguous(), T(g[f"{tag}_y"]).repeat(2, 1).reshape(-1))
+        close(r.loss, g[tag])
+        close(r.df, np.concatenate([g[f"{tag}_df"][:, 0], g[f"{tag}_df"][:, 1]]), 1e-5)
+
+
+@pytest.mark.parametrize("n", [96, 258])
+def test_rnc_bars_notice_one_flipped_membership(n):
+    """Keeps the bars of tests/loss_bars.py honest: with the threshold-straddling labels, for EVERY anchor the membership decision
+    (k, j) whose fp32 operands lie closest together is inverted in the float64 reference; the flip must move some element of rowloss or G
+    of that anchor by more than 4 x that element's bar.  A kernel that decides one membership differently from fp32 torch therefore
+    cannot stay inside the bars of tests/test_gpu_loss_kernels.py (same cases, same bars)."""
+    from oracle.rnc_reference import closest_membership, rnc_reference
+    from tests.loss_bars import rnc_case, rnc_row_bars
+    dim, t = 64, 2.0
+    f32, y = rnc_case(n, dim, "straddle", t)
+    worst = float("inf")
+    for i in range(n):
+        k, j, gap = closest_membership(y, i)
+        assert gap < 2e-5, "straddling labels put a decision next to the threshold for every anchor"
+        base = rnc_reference(f32, y, t, anchors=[i])
+        flipped = rnc_reference(f32, y, t, anchors=[i], flip={i: (k, j)})
+        _, bar_rl, bar_g = rnc_row_bars(base, dim, t)
+        ratio = max(float(((flipped.rowloss - base.rowloss).abs() / bar_rl).max()),
+                    float(((flipped.G - base.G).abs() / bar_g.clamp_min(1e-300)).max()))
+        worst = min(worst, ratio)
+    print(f"n={n}: smallest (movement of the best element) / bar over all anchors = {worst:.1f}")
+    assert worst > 4.0
