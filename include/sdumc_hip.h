@@ -569,6 +569,29 @@ int sdumc_rnc_fwd_bwd(const float* feats, const float* labels, int32_t n, int32_
 int sdumc_rnc_fwd_bwd_rep(const float* feats, const float* labels_half, int32_t n, int32_t dim, float temperature,
                           float weight, int32_t row0, int32_t rows_local, float* loss_out, float* dfeats,
                           float* workspace, void* stream);
+/* SupConLoss (loss.py:143-240; forward :153-240): supervised contrastive loss over class labels, SimCLR without them.
+ * feats [N, dim], N = bsz * n_views rows VIEW-MAJOR (row v * bsz + b = view v of sample b: the reference's
+ * cat(unbind(features, 1)) of :191).  Anchors: all N rows (contrast_all = 1, contrast_mode 'all') or the first bsz
+ * (0, 'one').  Logits = dot / temperature minus the row maximum over every column; the self column is left out of the
+ * denominator and of the positives; an anchor with fewer than 1e-6 positives divides by 1; the value is
+ * -(temperature / base_temperature) * the mean over the anchors.
+ * Positives: labels == NULL and mask == NULL: same sample (:180-181); labels [bsz] floats: label_mode 0 = equal labels
+ * (torch.eq, :186), 1 = equal rintf(label) (the seven classes of a MOSEI sentiment score); mask [bsz, bsz] floats: the
+ * weight of sample j among the positives of sample i (may be asymmetric; tiled as :210).  Both given: SDUMC_EINVAL.
+ * normalize = 1: every row is first divided by max(|row|, 1e-12) (F.normalize(x, dim=-1)); dfeats is still the gradient
+ * w.r.t. the rows AS GIVEN (the projection is applied here, no normalised copy is written).  On un-normalised 64-wide
+ * rows with temperature 0.07 the reference itself returns NaN (every off-diagonal exp underflows: 0 * log 0), and so
+ * does this entry.
+ * loss_out (device scalar) is WRITTEN with the unweighted value; dfeats [N, dim] (may be NULL) is overwritten with
+ * weight * dLoss/dfeats.  fp32 in and out, fp64 between; two launches, fixed summation order, no atomics.
+ * Built limits: 2 <= N <= 2048, 1 <= dim <= 1024 (any dim, any N in the range); beyond them, and for n_views < 1,
+ * temperature <= 0, base_temperature <= 0, a mode outside 0/1 or a NULL / not 8-byte aligned workspace:
+ * SDUMC_EINVAL before anything is launched.  workspace >= sdumc_supcon_workspace_bytes(bsz, n_views, contrast_all). */
+size_t sdumc_supcon_workspace_bytes(int32_t bsz, int32_t n_views, int32_t contrast_all);
+int sdumc_supcon_fwd_bwd(const float* feats, const float* labels, const float* mask, int32_t bsz, int32_t n_views,
+                         int32_t dim, int32_t contrast_all, int32_t label_mode, int32_t normalize, double temperature,
+                         double base_temperature, float weight, float* loss_out, float* dfeats, void* workspace,
+                         void* stream);
 /* The five batch-local terms of main :137-148 in two launches: MSELoss(vals_s, labels) for both streams and the
  * three RMSELoss pairs (text_hidden, cross_text, fused; stream 1 vs stream 0, teacher side detached for the
  * first two).  All tensors are the [2B, ...] stream-major network outputs; weights5 = (full_mse, missing_mse,
@@ -1060,6 +1083,18 @@ typedef struct sdumc_step_cfg {
   const float* rnc_feats_global;  /* [2*B_global, 64] = cat(r_stream0 of all ranks, r_stream1 of all ranks) */
   const float* rnc_labels_global; /* [2*B_global] */
   int32_t rnc_row0[2];   /* rows of this rank's stream-0 / stream-1 features in the gathered matrix */
+  /* The contrastive criterion over the [2B, 64] rnc rows (losses[6], weights[5]): SDUMC_CONTRAST_RNC (0 = a zeroed
+   * struct) RnCLoss with `temperature`; SDUMC_CONTRAST_SUPCON SupConLoss (loss.py:143-240) with the two streams as the
+   * two views of a sample, contrast_mode 'all', positives from `labels` (supcon_label_mode 0: equal labels, 1: equal
+   * rintf(label)), supcon_temperature (> 0) and supcon_base_temperature (0 means 0.07).  The rows are L2-normalised
+   * inside the kernel (the driver's Proj, main :61-69): on the raw rows the reference's SupConLoss is NaN, so there is
+   * no un-normalised option here.  Anything else, or SUPCON together with rnc_feats_global (the data-parallel exchange
+   * carries RnC records only): SDUMC_EINVAL before a launch.
+   * (These four sit in front of `distill`, which stays the struct's last field; all zero = today's step.) */
+  int32_t contrast;
+  int32_t supcon_label_mode;
+  float supcon_temperature;
+  float supcon_base_temperature;
   /* The criterion of the three distillation pairs text_hidden, cross_text, fused (main :148 and its commented-out tail):
    * SDUMC_DISTILL_RMSE (0 = a zeroed struct) RMSELoss, _COSINE CosineSimilarityLoss4Seq, _KL KLLoss; anything else:
    * SDUMC_EINVAL before a launch.  losses[3..5] hold the chosen criterion's values.  Cosine and KL are sums over rows
@@ -1070,6 +1105,8 @@ typedef struct sdumc_step_cfg {
 #define SDUMC_DISTILL_RMSE 0
 #define SDUMC_DISTILL_COSINE 1
 #define SDUMC_DISTILL_KL 2
+#define SDUMC_CONTRAST_RNC 0
+#define SDUMC_CONTRAST_SUPCON 1
 
 size_t sdumc_loss_workspace_bytes(const sdumc_net_dims* d, int32_t B_global);
 /* local sums of squared differences of the three RMSE pairs -> ssd_out float[3] (for the all-reduce) */

@@ -154,7 +154,9 @@ class StepCfg(C.Structure):
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
                 ("losses", C.c_void_p),
                 ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
-                ("rnc_labels_global", C.c_void_p), ("rnc_row0", C.c_int32 * 2), ("distill", C.c_int32)]
+                ("rnc_labels_global", C.c_void_p), ("rnc_row0", C.c_int32 * 2),
+                ("contrast", C.c_int32), ("supcon_label_mode", C.c_int32), ("supcon_temperature", C.c_float),
+                ("supcon_base_temperature", C.c_float), ("distill", C.c_int32)]
 
 
 # sdumc_step_cfg.distill: the criterion of the three distillation pairs (SDUMC_DISTILL_* of include/sdumc_hip.h)
@@ -165,6 +167,36 @@ def distill_code(name):
     if not isinstance(name, str) or name not in DISTILL:
         raise SdumcError(f"distill must be one of {sorted(DISTILL)}, not {name!r}")
     return DISTILL[name]
+
+
+# sdumc_step_cfg.contrast: the contrastive criterion over the rnc rows (SDUMC_CONTRAST_*); .supcon_label_mode: which labels count as
+# one class for SupCon ('eq': equal labels, 'round': equal rint(label), the seven classes of a MOSEI sentiment score)
+CONTRAST = {"rnc": 0, "supcon": 1}
+CONTRAST_CLASSES = {"eq": 0, "round": 1}
+
+
+def contrast_code(name, classes="eq"):
+    """-> (SDUMC_CONTRAST_* code, label mode)"""
+    if not isinstance(name, str) or name not in CONTRAST:
+        raise SdumcError(f"contrast must be one of {sorted(CONTRAST)}, not {name!r}")
+    if not isinstance(classes, str) or classes not in CONTRAST_CLASSES:
+        raise SdumcError(f"contrast_classes must be one of {sorted(CONTRAST_CLASSES)}, not {classes!r}")
+    return CONTRAST[name], CONTRAST_CLASSES[classes]
+
+
+def contrast_cfg(cfg, contrast, temperature, classes):
+    """Fill a StepCfg's contrastive fields: 'rnc' (temperature None = the reference's 2.0) or 'supcon' (None = 0.07)."""
+    code, mode = contrast_code(contrast, classes)
+    if temperature is not None and not (isinstance(temperature, (int, float)) and temperature > 0):
+        raise SdumcError(f"contrast_temperature must be a positive number or None, not {temperature!r}")
+    if code == CONTRAST["rnc"]:
+        cfg.temperature = 2.0 if temperature is None else float(temperature)
+    else:
+        cfg.temperature = 2.0
+        cfg.supcon_temperature = 0.07 if temperature is None else float(temperature)
+        cfg.supcon_base_temperature = 0.07
+        cfg.supcon_label_mode = mode
+    cfg.contrast = code
 
 
 GATHER_MAX_SEGS = 8
@@ -288,6 +320,10 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdumc_ce_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdumc_supcon_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sdumc_supcon_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "sdumc_rnc_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "sdumc_rnc_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

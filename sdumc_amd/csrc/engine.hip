@@ -2830,6 +2830,14 @@ extern "C" int sdumc_loss_ssd(const sdumc_net_dims* d, const sdumc_net_io* io, f
 namespace {
 int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg, const sdumc_net_grads* g,
                        void* scratch, size_t scratch_bytes, void* stream, float* hyper, bool* total_pending = nullptr);
+// the contrastive criterion of a step: known, and SupCon neither under the data-parallel exchange (it carries RnC records only)
+// nor with a temperature or label mode its kernel would refuse after the distillation launches
+bool contrast_ok(const sdumc_step_cfg* cfg) {
+  if (cfg->contrast == SDUMC_CONTRAST_RNC) return true;
+  if (cfg->contrast != SDUMC_CONTRAST_SUPCON) return false;
+  return !cfg->rnc_feats_global && cfg->supcon_temperature > 0.f && cfg->supcon_base_temperature >= 0.f &&
+         cfg->supcon_label_mode >= 0 && cfg->supcon_label_mode <= 1;
+}
 }
 extern "C" int sdumc_loss_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
                                    const sdumc_net_grads* g, void* scratch, size_t scratch_bytes, void* stream) {
@@ -2846,10 +2854,16 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   if (!g->d_vals || !g->d_fused || !g->d_rnc || !g->d_text_hidden || !g->d_cross_text) return SDUMC_EINVAL;
   if (!cfg->labels || !cfg->losses) return SDUMC_EINVAL;
   if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;
+  if (!contrast_ok(cfg)) return SDUMC_EINVAL;
+  const bool supcon = cfg->contrast == SDUMC_CONTRAST_SUPCON;
   hipStream_t st = as_stream(stream);
   const int B = d->B, Bg = cfg->B_global > 0 ? cfg->B_global : B;
   const LossScratch ls = loss_scratch(*d, cfg->B_global, static_cast<float*>(scratch));
   if (scratch_bytes < ls.total_floats * sizeof(float)) return SDUMC_ENOMEM;
+  // SupCon's scratch is the RnC region (2 n^2 + 4 n floats of its 5 n^2 + 2 n, n = 2B); beyond its built limits: before a launch
+  if (supcon && (2 * B > 2048 || (reinterpret_cast<uintptr_t>(ls.rnc_ws) & 7) ||
+                 sdumc_supcon_workspace_bytes(B, 2, 1) > sdumc_rnc_workspace_bytes(2 * Bg)))
+    return SDUMC_EINVAL;
   float* dv = const_cast<float*>(g->d_vals);
   float* df = const_cast<float*>(g->d_fused);
   float* dr = const_cast<float*>(g->d_rnc);
@@ -2859,7 +2873,7 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   const float* w = cfg->weights;
   // single GPU (no global sums / features handed in): the distillation terms and RnC share their two passes (loss.hip)
   bool done = false;
-  if (!cfg->rnc_feats_global && !cfg->ssd_global && Bg == B) {
+  if (!supcon && !cfg->rnc_feats_global && !cfg->ssd_global && Bg == B) {
     const int rc = sdumc_losses_fused_(B, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, io->rnc, RD,
                                        cfg->temperature, w, dv, dth, dct, df, dr, L, ls.ssd_ws, ls.rnc_ws,
                                        total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2, cfg->distill,
@@ -2877,7 +2891,12 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   RET(sdumc_distill_crit_(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
                           cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, cfg->distill, stream));
   // RnCLoss over cat(r_stream0, r_stream1) with labels repeated (main :134,:140; loss.py:282-283)
-  if (cfg->rnc_feats_global) {
+  if (supcon) {
+    // SupConLoss instead (loss.py:143-240): the two streams are the two views of a sample, rows normalised in the kernel
+    RET(sdumc_supcon_fwd_bwd(io->rnc, cfg->labels, nullptr, B, 2, RD, 1, cfg->supcon_label_mode, 1, (double)cfg->supcon_temperature,
+                             cfg->supcon_base_temperature > 0.f ? (double)cfg->supcon_base_temperature : 0.07, w[5], L + 6, dr,
+                             ls.rnc_ws, st));
+  } else if (cfg->rnc_feats_global) {
     if (!cfg->rnc_labels_global) return SDUMC_EINVAL;
     RET(sdumc_rnc_fwd_bwd(cfg->rnc_feats_global, cfg->rnc_labels_global, 2 * Bg, RD, cfg->temperature, w[5],
                           cfg->rnc_row0[0], B, L + 6, dr, ls.rnc_ws, st));
@@ -2939,6 +2958,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   RET(check_io(d, io));
   if (!cfg || d->streams != 2 || !cfg->adam_m || !cfg->adam_v || !cfg->hyper) return SDUMC_EINVAL;
   if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;   // before anything is launched
+  if (!contrast_ok(cfg) || (cfg->contrast == SDUMC_CONTRAST_SUPCON && 2 * d->B > 2048)) return SDUMC_EINVAL;
   const StepLayout sl = step_layout(*d);
   if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   char* base = static_cast<char*>(io->workspace);

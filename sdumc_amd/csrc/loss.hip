@@ -1084,6 +1084,209 @@ extern "C" int sdumc_rnc_mask(const float* labels, int32_t n, uint8_t* mask, voi
   return SDUMC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// SupConLoss (loss.py:143-240).  N = bsz * n_views contrast rows, view-major; A anchors = the first N ('all') or bsz ('one') rows.
+// With T = 0.07 the logits span ~ +-14 and fp32 logits alone cost ~1e-6 of the gradient, which is the whole budget (the
+// reference's own fp32-vs-fp64 gap): inputs and outputs are fp32, everything between them is fp64 -- N^2 * D fp64 multiply-adds,
+// microseconds at the step's N = 128.  Workspace (doubles): G[A*N] = dLoss/dlogit | nrm[N] row norms | rowval[A].
+//   pass 1, workgroup i: i < A: logits of anchor i against every row (one wavefront per contrast row, lanes over channels,
+//           butterfly sum), row maximum, denominator without the self column, positives -> rowval[i], G[i][*]; every i: nrm[i].
+//   pass 2, workgroup r < N: dL/dxhat_r = (1/T) sum_j (G[r][j] + G[j][r]) xhat_j, then the projection of F.normalize; workgroup N:
+//           the mean of rowval.  Every sum has one fixed order; nothing is accumulated across workgroups.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int SUPCON_MAX_N = 2048, SUPCON_MAX_D = 1024;
+constexpr double SUPCON_NORM_EPS = 1e-12;   // F.normalize's eps
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double block_sum_256_d(double v, double* red /*[4]*/) {
+  v = wave_sum_d(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+__device__ __forceinline__ double block_max_256_d(double v, double* red /*[4]*/) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+struct SupconArgs {
+  const float* f;        // [N, D]
+  const float* labels;   // [bsz] or null
+  const float* mask;     // [bsz, bsz] or null
+  int bsz, N, A, D, label_mode, normalize;
+  double inv_t, scale;   // 1 / T, T / base_T
+  float weight;
+  double *G, *nrm, *rowval;
+  float* loss_out;
+  float* df;             // [N, D] or null
+};
+// the weight of contrast row j among the positives of anchor i, self column included (the caller masks it): loss.py:180-188, :210
+__device__ __forceinline__ double supcon_pos(const SupconArgs& a, int i, int j) {
+  const int bi = i % a.bsz, bj = j % a.bsz;
+  if (a.mask) return (double)a.mask[(size_t)bi * a.bsz + bj];
+  if (!a.labels) return bi == bj ? 1.0 : 0.0;
+  const float yi = a.labels[bi], yj = a.labels[bj];
+  return (a.label_mode == 1 ? rintf(yi) == rintf(yj) : yi == yj) ? 1.0 : 0.0;
+}
+__device__ __forceinline__ double supcon_inv_norm(const SupconArgs& a, double nrm) {
+  return a.normalize ? 1.0 / fmax(nrm, SUPCON_NORM_EPS) : 1.0;
+}
+
+__global__ __launch_bounds__(256) void supcon_row_kernel(const SupconArgs a) {
+  extern __shared__ double smd[];   // xi[D] | lg[N]
+  __shared__ double red[4];
+  double* xi = smd;
+  double* lg = smd + a.D;
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = a.N, D = a.D;
+  const float* fi = a.f + (size_t)i * D;
+  double q = 0.0;
+  for (int c = lane; c < D; c += 64) {
+    const double v = (double)fi[c];
+    q += v * v;
+  }
+  const double nrm_i = sqrt(wave_sum_d(q));   // (the same bits in every wavefront)
+  if (tid == 0) a.nrm[i] = nrm_i;
+  if (i >= a.A) return;                       // contrast_mode 'one': the later views are no anchors
+  const double inv_i = supcon_inv_norm(a, nrm_i);
+  for (int c = tid; c < D; c += 256) xi[c] = (double)fi[c] * inv_i;
+  __syncthreads();
+  for (int j = wave; j < N; j += 4) {
+    const float* fj = a.f + (size_t)j * D;
+    double s = 0.0, qj = 0.0;
+    for (int c = lane; c < D; c += 64) {
+      const double v = (double)fj[c];
+      s += xi[c] * v;
+      qj += v * v;
+    }
+    s = wave_sum_d(s);
+    qj = wave_sum_d(qj);
+    if (lane == 0) lg[j] = s * supcon_inv_norm(a, sqrt(qj)) * a.inv_t;
+  }
+  __syncthreads();
+  double mx = -INFINITY;
+  for (int j = tid; j < N; j += 256) mx = fmax(mx, lg[j]);   // over every column, the anchor's own included (loss.py:206)
+  mx = block_max_256_d(mx, red);
+  double den = 0.0;
+  for (int j = tid; j < N; j += 256) den += j == i ? 0.0 : exp(lg[j] - mx);
+  den = block_sum_256_d(den, red);
+  const double logden = log(den);
+  // positives: m * log_prob over every column with the self column's weight forced to 0 (0 * log_prob, as loss.py:218,:235 has it)
+  double cnt = 0.0, sp = 0.0;
+  for (int j = tid; j < N; j += 256) {
+    const double m = j == i ? 0.0 : supcon_pos(a, i, j);
+    cnt += m;
+    sp += m * ((lg[j] - mx) - logden);
+  }
+  cnt = block_sum_256_d(cnt, red);
+  sp = block_sum_256_d(sp, red);
+  const double pairs = cnt < 1e-6 ? 1.0 : cnt;   // an anchor without positives divides by 1 (loss.py:232-234)
+  if (tid == 0) a.rowval[i] = sp / pairs;
+  if (!a.df) return;
+  // d loss / d logit_ij = -(T / base_T) / (A * pairs) * (m_ij - cnt * p_ij),  p_ij = exp(logit_ij - mx) / den off the diagonal
+  const double k = -a.scale / ((double)a.A * pairs);
+  for (int j = tid; j < N; j += 256) {
+    double g = 0.0;
+    if (j != i) g = k * (supcon_pos(a, i, j) - cnt * (exp(lg[j] - mx) / den));
+    a.G[(size_t)i * N + j] = g;
+  }
+}
+
+__global__ __launch_bounds__(256) void supcon_dfeat_kernel(const SupconArgs a) {
+  extern __shared__ double smd[];   // coef[N] | g[D] | part[4][64]
+  __shared__ double red[4];
+  const int N = a.N, D = a.D, A = a.A;
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (r == N) {   // the value: -(T / base_T) * mean over anchors
+    double acc = 0.0;
+    for (int i = tid; i < A; i += 256) acc += a.rowval[i];
+    const double s = block_sum_256_d(acc, red);
+    if (tid == 0) *a.loss_out = (float)(-a.scale * s / (double)A);
+    return;
+  }
+  if (!a.df) return;
+  double* coef = smd;
+  double* g = coef + N;
+  double* part = g + D;
+  for (int j = tid; j < N; j += 256) {
+    double cj = 0.0;
+    if (r < A) cj += a.G[(size_t)r * N + j];   // r as the anchor
+    if (j < A) cj += a.G[(size_t)j * N + r];   // r as a contrast row of anchor j
+    coef[j] = cj * supcon_inv_norm(a, a.nrm[j]);
+  }
+  __syncthreads();
+  for (int c0 = 0; c0 < D; c0 += 64) {
+    const int c = c0 + lane;
+    double acc = 0.0;
+    if (c < D)
+      for (int j = wave; j < N; j += 4) acc += coef[j] * (double)a.f[(size_t)j * D + c];
+    part[wave * 64 + lane] = acc;
+    __syncthreads();
+    if (wave == 0 && c < D) g[c] = part[lane] + part[64 + lane] + part[128 + lane] + part[192 + lane];
+    __syncthreads();
+  }
+  // through xhat = x / max(|x|, eps): (g - xhat (xhat . g)) / |x| where the norm is not clamped, g / eps where it is
+  // (clamp_min passes the gradient where norm >= eps only)
+  const float* fr = a.f + (size_t)r * D;
+  const double nrm = a.nrm[r], inv = supcon_inv_norm(a, nrm);
+  double dot = 0.0;
+  if (a.normalize && nrm >= SUPCON_NORM_EPS) {
+    double acc = 0.0;
+    for (int c = tid; c < D; c += 256) acc += (double)fr[c] * inv * g[c];
+    dot = block_sum_256_d(acc, red);
+  }
+  const double w = (double)a.weight * a.inv_t;
+  for (int c = tid; c < D; c += 256) a.df[(size_t)r * D + c] = (float)(w * inv * (g[c] - (double)fr[c] * inv * dot));
+}
+}  // namespace
+
+static int supcon_anchors(int32_t bsz, int32_t n_views, int32_t contrast_all) { return contrast_all ? bsz * n_views : bsz; }
+
+extern "C" size_t sdumc_supcon_workspace_bytes(int32_t bsz, int32_t n_views, int32_t contrast_all) {
+  if (bsz < 1 || n_views < 1 || (int64_t)bsz * n_views > SUPCON_MAX_N) return 0;
+  const size_t N = (size_t)bsz * n_views, A = (size_t)supcon_anchors(bsz, n_views, contrast_all);
+  return (A * N + N + A) * sizeof(double);
+}
+
+extern "C" int sdumc_supcon_fwd_bwd(const float* feats, const float* labels, const float* mask, int32_t bsz, int32_t n_views,
+                                    int32_t dim, int32_t contrast_all, int32_t label_mode, int32_t normalize, double temperature,
+                                    double base_temperature, float weight, float* loss_out, float* dfeats, void* workspace,
+                                    void* stream) {
+  if (!feats || !loss_out || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 7)) return SDUMC_EINVAL;
+  if (labels && mask) return SDUMC_EINVAL;
+  if (bsz < 1 || n_views < 1 || dim < 1 || dim > SUPCON_MAX_D) return SDUMC_EINVAL;
+  if ((int64_t)bsz * n_views < 2 || (int64_t)bsz * n_views > SUPCON_MAX_N) return SDUMC_EINVAL;
+  if (!(temperature > 0.0) || !(base_temperature > 0.0)) return SDUMC_EINVAL;
+  if (label_mode < 0 || label_mode > 1 || contrast_all < 0 || contrast_all > 1 || normalize < 0 || normalize > 1) return SDUMC_EINVAL;
+  SupconArgs a;
+  a.f = feats; a.labels = labels; a.mask = mask;
+  a.bsz = bsz; a.N = bsz * n_views; a.A = supcon_anchors(bsz, n_views, contrast_all); a.D = dim;
+  a.label_mode = label_mode; a.normalize = normalize;
+  a.inv_t = 1.0 / temperature; a.scale = temperature / base_temperature;
+  a.weight = weight;
+  a.G = static_cast<double*>(workspace);
+  a.nrm = a.G + (size_t)a.A * a.N;
+  a.rowval = a.nrm + a.N;
+  a.loss_out = loss_out; a.df = dfeats;
+  hipStream_t st = as_stream(stream);
+  // LDS: at most (1024 + 2048) and (2048 + 1024 + 256) doubles = 24 / 26 KiB: under the 64 KiB a kernel gets without an attribute
+  hipLaunchKernelGGL(supcon_row_kernel, dim3(a.N), dim3(256), (size_t)(a.D + a.N) * sizeof(double), st, a);
+  SDUMC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(supcon_dfeat_kernel, dim3(a.N + 1), dim3(256), (size_t)(a.N + a.D + 256) * sizeof(double), st, a);
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
+}
+
 // One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
 // this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
 // with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,

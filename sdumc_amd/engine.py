@@ -362,8 +362,12 @@ class TrainStep(_OptStateMixin):
 
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
-                 bits_next=True, distill='rmse'):
-        """distill: the criterion of the three distillation pairs (text_hidden, cross_text, fused; main :148): 'rmse' (the
+                 bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq'):
+        """contrast: the contrastive criterion over the [2B, 64] rnc rows (losses[6]): 'rnc' (Rank-N-Contrast, main :140 as it
+        stands) or 'supcon' (SupConLoss, loss.py:143-240: the two streams are the two views of a sample, rows L2-normalised in
+        the kernel, positives = samples of one class: contrast_classes 'eq' equal labels, 'round' equal rint(label));
+        contrast_temperature: None = the criterion's own default (2.0 / 0.07).
+        distill: the criterion of the three distillation pairs (text_hidden, cross_text, fused; main :148): 'rmse' (the
         reference's line as it stands), 'cosine' (CosineSimilarityLoss4Seq) or 'kl' (KLLoss); losses[3:6] hold its values.
         share: an object with .params .rng .adam_m .adam_v .hyper .losses (another TrainStep over the SAME flat_params, or
         FusedTrainer's run state) whose optimiser state this step uses instead of allocating its own -- steps of different
@@ -375,6 +379,8 @@ class TrainStep(_OptStateMixin):
         Ta, Tt, Tv, T4 = T
         distill_code = _lib.distill_code(distill)
         self.distill = distill
+        _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)      # (rejected before any device work)
+        self.contrast, self.contrast_temperature, self.contrast_classes = contrast, contrast_temperature, contrast_classes
         self.layout = ParamLayout.get(dims[0], dims[1], dims[2])
         dev = flat_params.device
         _require_cuda(flat_params)
@@ -452,7 +458,7 @@ class TrainStep(_OptStateMixin):
         io.ctx = ctx.handle if ctx is not None else None
         for i, w in enumerate(weights):
             cfg.weights[i] = w
-        cfg.temperature = 2.0
+        _lib.contrast_cfg(cfg, contrast, contrast_temperature, contrast_classes)      # (temperature: 2.0 unless asked otherwise)
         cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay = betas[0], betas[1], eps, weight_decay
         cfg.adam_m, cfg.adam_v = ptr(self.adam_m), ptr(self.adam_v)
         cfg.hyper, cfg.losses = ptr(self.hyper), ptr(self.losses)
@@ -729,8 +735,9 @@ class FusedTrainer:
     (sdumc_net_io.prefetch) -- and every step tells the engine the next batch's shape, so that the next keep-bits are laid out for it."""
 
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
-                 inplace=True, distill='rmse', **step_kwargs):
+                 inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', **step_kwargs):
         """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        contrast: 'rnc' | 'supcon', contrast_temperature, contrast_classes: its contrastive criterion (TrainStep).
         capacity = (B_max, (T_audio, T_text, T_video, T_feat4) maxima) of the run: ONE arena then backs every batch shape
         (no per-shape workspace, the per-shape step is a few ctypes structs and tensor views: cache as many as you like) and
         `step_from_store` / `run_epoch` assemble batches straight into it.  Without it every cached shape owns its workspace.
@@ -740,9 +747,12 @@ class FusedTrainer:
         through per-batch row maps (4 bytes per frame; sdumc_net_io.row_map)."""
         _lib.distill_code(distill)
         self.distill = distill
+        _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)
+        self.contrast = (contrast, contrast_temperature, contrast_classes)
         _require_cuda(flat_params)
         self.params, self.dims, self.max_cached = flat_params, tuple(dims), max(1, int(max_cached))
-        self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill)
+        self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill, contrast=contrast, contrast_temperature=contrast_temperature,
+                       contrast_classes=contrast_classes)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         self.state = _RunState(flat_params, lay.live, lr, seed)     # (params, rng, adam_m, adam_v, hyper, losses)
         self._steps = {}          # shape -> TrainStep, insertion order = recency
@@ -763,7 +773,7 @@ class FusedTrainer:
             self.kw.update(planes=False, bits_next=False)
 
     def _get(self, B, T):
-        key = (B,) + tuple(T) + (self.distill,)      # the criterion is part of the key: one cache never mixes criteria
+        key = (B,) + tuple(T) + self.contrast + (self.distill,)      # the criteria are part of the key: one cache never mixes them
         ts = self._steps.pop(key, None)
         if ts is None:
             while len(self._steps) >= self.max_cached:

@@ -1,14 +1,14 @@
 """Drop-in replacements of the six loss callables the driver builds (main_frame_val_text_missing.py:310-315,
 toolkit/utils/loss.py): MSELoss (:19-33), RMSELoss (:37-51), RnCLoss (:271-315), CosineSimilarityLoss4Seq (:100-119),
-KLLoss (:74-97), CELoss (:6-16).  Same constructor and call signatures, 0-dim results with grad; value and
-gradient come from the HIP kernels (sdumc_amd/csrc/loss.hip)."""
+KLLoss (:74-97), CELoss (:6-16), and of the file's second contrastive criterion, SupConLoss (:143-240).  Same constructor
+and call signatures, 0-dim results with grad; value and gradient come from the HIP kernels (sdumc_amd/csrc/loss.hip)."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from ._lib import SdumcError
 
-__all__ = ["MSELoss", "RMSELoss", "RnCLoss", "CosineSimilarityLoss4Seq", "KLLoss", "CELoss"]
+__all__ = ["MSELoss", "RMSELoss", "RnCLoss", "CosineSimilarityLoss4Seq", "KLLoss", "CELoss", "SupConLoss"]
 
 
 def _flat2(pred, target):
@@ -175,3 +175,60 @@ class CELoss(nn.Module):
         if pred.dim() != 2 or target.numel() != pred.shape[0]:
             raise SdumcError(f"CELoss: pred [N, C] and N targets, not {tuple(pred.shape)} and {tuple(target.shape)}")
         return _CE.apply(pred, target)
+
+
+class _SupCon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, labels, mask, opts):
+        bsz, views = features.shape[0], features.shape[1]
+        # the contrast rows are view-major: cat(unbind(features, 1)) (loss.py:191)
+        feats = features.transpose(0, 1).contiguous().float().view(bsz * views, -1)
+        loss, df = ops.supcon_fwd_bwd(feats, bsz, views, labels=labels, mask=mask, need_grad=ctx.needs_input_grad[0], **opts)
+        ctx.save_for_backward(df)
+        ctx.shape = features.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (df,) = ctx.saved_tensors
+        if df is None:
+            return None, None, None, None
+        bsz, views = ctx.shape[0], ctx.shape[1]
+        return (df.view(views, bsz, -1).transpose(0, 1) * g).reshape(ctx.shape), None, None, None
+
+
+class SupConLoss(nn.Module):
+    """loss.py:143-240: supervised contrastive loss over class labels (or an explicit [bsz, bsz] mask), SimCLR when neither
+    is given.  features [bsz, n_views, ...].  The reference is only usable on L2-normalised rows (on raw 64-wide rows every
+    off-diagonal exp underflows at temperature 0.07 and it returns NaN, as this class then does); the keyword-only
+    extension normalize=True applies F.normalize(x, dim=-1) to every row inside the kernel, gradient through it included."""
+
+    def __init__(self, temperature=0.07, contrast_mode='all', base_temperature=0.07, *, normalize=False):
+        super().__init__()
+        self.temperature = temperature
+        self.contrast_mode = contrast_mode
+        self.base_temperature = base_temperature
+        self.normalize = bool(normalize)
+
+    def forward(self, features, labels=None, mask=None):
+        if len(features.shape) < 3:
+            raise ValueError('`features` needs to be [bsz, n_views, ...],'
+                             'at least 3 dimensions are required')
+        if len(features.shape) > 3:
+            features = features.reshape(features.shape[0], features.shape[1], -1)
+        batch_size = features.shape[0]
+        if labels is not None and mask is not None:
+            raise ValueError('Cannot define both `labels` and `mask`')
+        if labels is not None:
+            labels = labels.contiguous().view(-1)
+            if labels.shape[0] != batch_size:
+                raise ValueError('Num of labels does not match num of features')
+        if self.contrast_mode not in ('one', 'all'):
+            raise ValueError('Unknown mode: {}'.format(self.contrast_mode))
+        _dev(features, *(t for t in (labels, mask) if t is not None))
+        if mask is not None and tuple(mask.shape) != (batch_size, batch_size):
+            raise SdumcError(f"SupConLoss: mask [{batch_size}, {batch_size}], not {tuple(mask.shape)}")
+        opts = dict(temperature=float(self.temperature), base_temperature=float(self.base_temperature),
+                    contrast_all=self.contrast_mode == 'all', normalize=self.normalize)
+        return _SupCon.apply(features, None if labels is None else labels.float(),
+                             None if mask is None else mask.contiguous().float(), opts)

@@ -543,6 +543,26 @@ def rnc_fwd_bwd(feats, labels, temperature=2.0, weight=1.0, row0=0, rows_local=N
     return loss, df, ws
 
 
+def supcon_fwd_bwd(feats, bsz, n_views, labels=None, mask=None, temperature=0.07, base_temperature=0.07, contrast_all=True,
+                   label_mode=0, normalize=False, weight=1.0, need_grad=True):
+    """SupConLoss (loss.py:143-240) of feats [bsz * n_views, D] VIEW-MAJOR (fp32, contiguous); labels [bsz] or mask [bsz, bsz]
+    fp32 or neither (SimCLR): loss [1], dfeats [bsz * n_views, D] (w.r.t. the rows as given, also with normalize=True)."""
+    if feats.dim() != 2 or feats.shape[0] != bsz * n_views:
+        raise _lib.SdumcError(f"sdumc_supcon_fwd_bwd: feats [{bsz} * {n_views}, D], not {tuple(feats.shape)}")
+    if labels is not None and labels.numel() != bsz:
+        raise _lib.SdumcError(f"sdumc_supcon_fwd_bwd: {bsz} labels, not {labels.numel()}")
+    if mask is not None and tuple(mask.shape) != (bsz, bsz):
+        raise _lib.SdumcError(f"sdumc_supcon_fwd_bwd: mask [{bsz}, {bsz}], not {tuple(mask.shape)}")
+    loss = torch.empty(1, device=feats.device)
+    df = torch.empty_like(feats) if need_grad else None
+    ws = torch.empty(max(8, lib.sdumc_supcon_workspace_bytes(bsz, n_views, int(bool(contrast_all)))), dtype=torch.uint8,
+                     device=feats.device)
+    check(lib.sdumc_supcon_fwd_bwd(ptr(feats), ptr(labels), ptr(mask), bsz, n_views, feats.shape[1], int(bool(contrast_all)),
+                                   label_mode, int(bool(normalize)), temperature, base_temperature, weight, ptr(loss), ptr(df),
+                                   ptr(ws), _st()), "sdumc_supcon_fwd_bwd")
+    return loss, df
+
+
 def rnc_dfeat_rows(feats, ws, row0, rows, temperature=2.0, weight=1.0):
     n, dim = feats.shape
     df = torch.empty(rows, dim, device=feats.device)

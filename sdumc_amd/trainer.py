@@ -213,9 +213,14 @@ class DataParallelStep:
 
     def __init__(self, flat_params, B, T, dims, weights=(0.5, 0.5, 0.1, 0.7, 0.1, 0.8), lr=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=1e-5, seed=0, exact=True, backend_factory=None, bf16=False,
-                 force_collectives=False, planes=False, distill='rmse'):
+                 force_collectives=False, planes=False, distill='rmse', contrast='rnc'):
         import collections
         import inspect
+        from ._lib import SdumcError, contrast_code
+        contrast_code(contrast)
+        if contrast != 'rnc':      # the rank exchange (sdumc_dp_record) carries RnC records only: no silent RnC, no local-only SupCon
+            raise SdumcError(f"DataParallelStep: contrast={contrast!r} is not built under data parallelism (single-GPU steps only)")
+        self.contrast = contrast
         self.rank, self.world = _world()
         # force_collectives: issue every collective even at world size 1 (a one-rank RCCL communicator): the only way to
         # exercise the RCCL code path -- communicator stream ordering, the async early-slice handle -- on a 1-GPU box.
