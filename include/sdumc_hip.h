@@ -829,6 +829,31 @@ typedef struct sdumc_copy_seg {
   int32_t ld_src, ld_dst, rows, cols;
 } sdumc_copy_seg;
 int sdumc_copy2d_multi(const sdumc_copy_seg* segs, int32_t n, void* stream);
+/* Indexed row scatter of up to SDUMC_SCATTER_MAX_SEGS tensors in ONE launch:
+ *   dst_k[idx[r % B], 0:cols_k] = src_k[r, 0:cols_k]   for r < rows_k          (rows_k a multiple of B; both tensors contiguous)
+ * What an evaluation epoch over a resident feature store does after every eval-mode forward: the reference's validation / test
+ * passes append each batch's predictions and embeddings to host lists (main_frame_val_text_missing.py:156-163,
+ * main_frame_val_text_missing_inference.py:166-175); here the forward's five stream-major outputs ([2B, w]: rows [0, B) the full
+ * stream, rows [B, 2B) the text-missing one) go to per-stream result tensors [N, w] at the rows the batch's utterances have in the
+ * store (idx = the batch's index vector, device int64 [B], as sdumc_gather_desc.idx), so the results are in store order whatever
+ * order the sampler visits them in, and nothing is copied to the host per batch.
+ * mark (optional, uint8 [segs[0].dst_rows]): mark[idx[b]] = 1 for b < B -- the visited set.
+ * A segment moves 16 bytes per lane when cols % 4 == 0 and both base addresses are 16-byte aligned, one float per lane otherwise
+ * (cols = 1, odd widths, a view that starts mid-buffer).  Plain stores, no atomics: with distinct indices every destination element
+ * is written once, so a repeated launch gives the same bits.  Rows are addressed with 64 bits.  The indices must be distinct and in
+ * [0, dst_rows) -- the caller checks (DeviceFeatureStore.plan_epoch does, on the host); a row whose index is not in that range is
+ * skipped, never written out of bounds.
+ * SDUMC_EINVAL, before anything is launched: n < 1 or > SDUMC_SCATTER_MAX_SEGS, segs / idx NULL, B < 1, a segment with src or dst
+ * NULL or not 4-byte aligned, rows < 1, cols < 1, rows % B != 0, dst_rows < 1 or dst_rows * cols beyond 2^61 elements. */
+#define SDUMC_SCATTER_MAX_SEGS 10
+typedef struct sdumc_scatter_seg {
+  const float* src;   /* [rows, cols] */
+  float* dst;         /* [dst_rows, cols] */
+  int32_t rows, cols;
+  int64_t dst_rows;
+} sdumc_scatter_seg;
+int sdumc_scatter_rows_multi(const sdumc_scatter_seg* segs, int32_t n, const int64_t* idx, int32_t B, uint8_t* mark,
+                             void* stream);
 /* dst[r, 0:cols] = src[r, 0:cols] for r < rows, with leading dimensions */
 /* dst[r, 0:cols] += src[r, 0:cols] */
 int sdumc_axpy2d(const float* src, int32_t ld_src, float* dst, int32_t ld_dst, int32_t rows, int32_t cols, void* stream);

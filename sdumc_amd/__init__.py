@@ -1,0 +1,11 @@
+"""sdumc_amd: import the submodule you need (engine, data, evaluate, model, ...); nothing loads the HIP library before that.
+eval_epoch / EvalResult are also reachable from the package itself (resolved on first use)."""
+_LAZY = {"eval_epoch": "evaluate", "EvalResult": "evaluate"}
+__all__ = sorted(_LAZY)
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

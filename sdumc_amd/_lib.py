@@ -254,6 +254,13 @@ class CopySeg(C.Structure):
                 ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
+SCATTER_MAX_SEGS = 10
+
+
+class ScatterSeg(C.Structure):      # sdumc_scatter_seg: dst[idx[r % B], 0:cols] = src[r, 0:cols]
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("dst_rows", C.c_int64)]
+
+
 ADAM_MAX_SEGS = 96
 
 
@@ -268,6 +275,7 @@ class AdamTable(C.Structure):      # one launch's kernel argument (filled by sdu
 
 _SIGS = {
     "sdumc_copy2d_multi": (C.c_int, [C.POINTER(CopySeg), C.c_int32, C.c_void_p]),
+    "sdumc_scatter_rows_multi": (C.c_int, [C.POINTER(ScatterSeg), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sdumc_profile_enable": (C.c_int, [C.c_int]),
     "sdumc_profile_report": (C.c_int, [C.POINTER(ProfEntry), C.c_int]),
     "sdumc_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(Gemm)]),

@@ -75,8 +75,9 @@ class EpochPlan:
     loop -- a pageable upload per step costs the host a synchronisation with the previous step), the host-side offsets into it and the
     padded shape (B, (T_audio, T_text, T_video, T_feat4)) of every batch."""
 
-    def __init__(self, idx_d, offsets, shapes):
+    def __init__(self, idx_d, offsets, shapes, idx_h=None):
         self.idx_d, self.offsets, self.shapes = idx_d, offsets, shapes
+        self.idx_h = idx_h      # the same indices on the host, when the plan's maker kept them (host-side checks read these)
 
     def __len__(self):
         return len(self.shapes)
@@ -215,7 +216,8 @@ class DeviceFeatureStore:
         for i in idxs:
             ii = i.numpy()
             shapes.append((int(ii.size), tuple(int(self._len_np[m][ii].max()) for m in self.MODS)))
-        return EpochPlan(torch.cat(idxs).to(self.device), [int(o) for o in offsets[:-1]], shapes)
+        idx_h = torch.cat(idxs)
+        return EpochPlan(idx_h.to(self.device), [int(o) for o in offsets[:-1]], shapes, idx_h)
 
     def gather_desc(self, idx_ptr, B, T, outs, labels_out, lengths_out=None, planes_out=None, maps_out=None):
         """The sdumc_gather_batch descriptor of one batch: idx_ptr = device address of its int64 [B] index vector, T its padded frame

@@ -1,0 +1,292 @@
+"""Evaluation epochs over a resident feature store: the validation and test passes of the reference driver
+(main_frame_val_text_missing.py:333-353 calls train_or_eval_model three times per epoch; :151-166 is the eval branch -- both streams,
+no_grad, model.eval(); main_frame_val_text_missing_inference.py:100-215 is the same loop with the embeddings kept).
+
+`eval_epoch` is to those passes what FusedTrainer.run_epoch is to the training pass: the epoch's index vectors are uploaded once, the
+first batch is assembled in front of the first forward, and forward i (sdumc_net_forward, train = 0, both streams in one call: the
+audio / video frame projections run once) carries the assembly of batch i + 1 on its background lane (sdumc_net_io.prefetch).  With a
+store the training epoch would read in place, no padded copy of a batch exists: the forward reads the packed tensors through row maps.
+After every forward ONE launch (sdumc_scatter_rows_multi) moves the batch's stream-major outputs to the rows its utterances have in
+the store, so the results line up with store.names / store.vals whatever order the sampler used, and nothing crosses to the host
+inside the loop.  The metrics stay on the host (metric.py): [N] vectors cross once per epoch.
+
+Evaluation owns its device memory (_EvalArena): workspace, outputs, two sets of row maps / labels / lengths (and input buffers when
+batches are gathered).  It reads the flat parameters and nothing else of a training run -- no step workspace, no keep-bits, no
+Philox counter (rng_state = NULL) -- so a training run is bit for bit the same with or without evaluation epochs in between."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, engine
+from ._lib import lib, check, ptr
+
+D, H, NQ, RNC_DIM = _lib.D, _lib.H, _lib.NQ, _lib.RNC_DIM
+# the forward's outputs beside vals, in sdumc_net_io's order: name, trailing shape, (full, missing) keys of checkpoint.run_inference
+EMBEDDINGS = (("fused", (H,), ("full_rep", "missing_rep")),
+              ("rnc", (RNC_DIM,), ("full_rnc", "missing_rnc")),
+              ("text_hidden", (D,), ("text_rep_query_full", "text_rep_query_missing")),
+              ("cross_text", (NQ, H), ("text_rep_full", "text_rep_missing")))
+
+
+def check_epoch_indices(batches, n):
+    """Host-side check of an epoch's index vectors against a store of n utterances: every index in [0, n) and none visited twice
+    (the scatter writes every result row once; a second visit would race with the first).  Returns the concatenated int64 tensor."""
+    idxs = [torch.as_tensor(b, dtype=torch.int64).reshape(-1).cpu() for b in batches]
+    if not idxs or any(i.numel() == 0 for i in idxs):
+        raise _lib.SdumcError("eval_epoch: no batches, or an empty batch")
+    flat = torch.cat(idxs)
+    if int(flat.min()) < 0 or int(flat.max()) >= n:
+        raise _lib.SdumcError(f"eval_epoch: sample index out of range [0, {n})")
+    u, counts = torch.unique(flat, return_counts=True)
+    if u.numel() != flat.numel():
+        raise _lib.SdumcError(f"eval_epoch: index {int(u[counts > 1][0])} appears more than once in the epoch")
+    return flat
+
+
+class EvalResult:
+    """Results of one evaluation epoch in STORE order (row i = utterance i of the store): preds [2, N] (row 0 the full stream, row 1
+    the text-missing one), seen [N] (uint8 / bool: visited this epoch), embeddings None or {'fused' [2, N, 128], 'rnc' [2, N, 64],
+    'text_hidden' [2, N, 256], 'cross_text' [2, N, 7, 128]}.  Rows not visited hold NaN.  Device or CPU tensors."""
+
+    def __init__(self, preds, seen, embeddings=None):
+        self.preds, self.seen, self.embeddings = preds, seen, embeddings
+
+    @classmethod
+    def empty(cls, n, device, embeddings=False):
+        emb = None
+        if embeddings:
+            emb = {name: torch.empty((2, n) + shape, device=device) for name, shape, _ in EMBEDDINGS}
+        return cls(torch.empty(2, n, device=device), torch.empty(n, dtype=torch.uint8, device=device), emb)
+
+    def fits(self, n, device, embeddings):
+        return (self.preds.shape == (2, n) and self.preds.device == torch.device(device) and self.seen.numel() == n
+                and self.seen.element_size() == 1 and (self.embeddings is not None) == bool(embeddings))
+
+    def reset(self):
+        """NaN everywhere, nothing seen: once per epoch, in front of its first batch"""
+        self.preds.fill_(float("nan"))
+        self.seen.zero_()
+        for t in (self.embeddings or {}).values():
+            t.fill_(float("nan"))
+        return self
+
+    def _visited(self):
+        rows = np.flatnonzero(self.seen.cpu().numpy().reshape(-1) != 0)
+        if rows.size == 0:
+            raise _lib.SdumcError("EvalResult: no row was visited")
+        return rows
+
+    def results(self, store):
+        """The dictionary checkpoint.run_inference returns (same keys, array shapes and embedding names), over the visited rows in
+        store order, names from store.names, labels from store.vals; plus val_mse_full (main :170; = val_mse).  One device -> host
+        copy per tensor."""
+        rows = self._visited()
+        preds = self.preds.cpu().numpy()
+        labels = torch.as_tensor(store.vals).cpu().numpy().astype(np.float32).reshape(-1)[rows]
+        out = {"val_preds_full": preds[0][rows].reshape(-1, 1), "val_preds_missing": preds[1][rows].reshape(-1, 1),
+               "val_labels": labels}
+        for name, _, keys in EMBEDDINGS if self.embeddings is not None else ():
+            t = self.embeddings[name].cpu().numpy()
+            out[keys[0]], out[keys[1]] = t[0][rows], t[1][rows]
+        out["names"] = [store.names[i] for i in rows.tolist()]
+        out["val_mse"] = float(np.mean((labels - out["val_preds_full"].reshape(-1)) ** 2))
+        out["val_mse_full"] = out["val_mse"]
+        out["val_mse_missing"] = float(np.mean((labels - out["val_preds_missing"].reshape(-1)) ** 2))
+        return out
+
+    def metrics(self, store):
+        """{'full': eval_mosei_metric(...), 'missing': ...} of the visited rows (main :366-367), on the host."""
+        from .metric import eval_mosei_metric
+        rows = self._visited()
+        preds = self.preds.cpu().numpy()
+        labels = torch.as_tensor(store.vals).cpu().numpy().reshape(-1)[rows]
+        names = [store.names[i] for i in rows.tolist()]
+        return {"full": eval_mosei_metric(preds[0][rows], labels, names), "missing": eval_mosei_metric(preds[1][rows], labels, names)}
+
+
+class _EvalArena:
+    """Device memory of evaluation, sized for the largest batch seen so far: the eval workspace, the forward's five [2 B, w] outputs
+    and two engine._InputSet (row maps, labels, lengths; padded input buffers and planes only once a batch is gathered)."""
+
+    def __init__(self, dev, B, T, fdims, dtype, nbytes):
+        self.B, self.T = int(B), tuple(int(t) for t in T)
+        self._fdims = fdims
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        V = 2 * self.B
+        self.outs = [torch.empty(V * k, device=dev) for k in (1, H, RNC_DIM, D, NQ * H)]
+        rows = [self.B * t for t in self.T]
+        self.sets = [engine._InputSet([r * d for r, d in zip(rows, fdims)], self.B, dtype, dev, rows) for _ in range(2)]
+
+    def fits(self, B, T, nbytes):
+        return B <= self.B and all(t <= c for t, c in zip(T, self.T)) and nbytes <= self.workspace.numel()
+
+    def ensure_planes(self):
+        for st in self.sets:
+            if st.planes is None:
+                st.planes = [engine._planes_buffer(r, d, self.workspace.device) for r, d in zip(st._rows, self._fdims)]
+
+
+class Evaluator:
+    """The state `eval_epoch` keeps across epochs for one parameter buffer: the arena and the per-shape dims."""
+
+    def __init__(self, flat_params, dims, bf16=False, inplace=True, planes=None, prefetch_workgroups=0):
+        engine._require_cuda(flat_params)
+        self.params, self.dims, self.bf16 = flat_params, tuple(int(d) for d in dims), bf16
+        lay = engine.ParamLayout.get(*self.dims[:3])
+        if flat_params.numel() != lay.total:
+            raise _lib.SdumcError("flat parameter buffer has the wrong size")
+        self.inplace = bool(inplace)
+        self.prefetch_workgroups = int(prefetch_workgroups)
+        self._fdims = (self.dims[0], self.dims[1], self.dims[2], self.dims[1])
+        self.feature_dtype = torch.bfloat16 if engine.bf16_mode(bf16, self.dims) == 2 else torch.float32
+        self._planes_ok = planes is not False and engine.planes_wanted(True, self.dims, bf16)
+        self.arena = None
+        self._dims = {}       # (B, T) -> (sdumc_net_dims, workspace bytes)
+
+    def _in_place(self, store):
+        """as FusedTrainer._in_place: fp32 storage and a store with planes, or bf16 storage and a bf16 store (widths % 128 == 0)"""
+        if not self.inplace:
+            return False
+        if self.feature_dtype == torch.bfloat16:
+            return store.packed['audio'].dtype == torch.bfloat16 and all(d % 128 == 0 for d in self.dims[:3])
+        return store.packed_p3 is not None and self._planes_ok
+
+    def _shape(self, shape):
+        """eval dims of one (B, T) and the workspace they need; a shape the engine refuses raises"""
+        e = self._dims.get(shape)
+        if e is None:
+            B, T = shape
+            d = engine.make_dims(B, 2, T[0], T[2], (T[1], T[3]), self.dims, False, 0, bf16=self.bf16)
+            nb = lib.sdumc_net_workspace_bytes(C.byref(d))
+            if nb == 0:
+                raise _lib.SdumcError(f"eval_epoch: the engine refuses the batch shape B={B}, T={T}")
+            e = self._dims[shape] = (d, int(nb))
+        return e
+
+    def _io(self, store, k, inplace, planes, key_padding):
+        a, st = self.arena, self.arena.sets[k]
+        io = _lib.NetIO()
+        if inplace:
+            feats = [store.packed[m] for m in store.MODS]
+            p3 = [store.packed_p3[m] for m in store.MODS] if self.feature_dtype == torch.float32 else None
+            for i, m in enumerate(st.ensure_maps()):
+                io.row_map[i], io.store_rows[i] = ptr(m), int(feats[i].shape[0])
+        else:
+            feats, p3 = st.inputs, (st.planes if planes else None)
+        io.audio, io.text[0], io.video, io.text[1] = (ptr(t) for t in feats)
+        if p3 is not None:
+            io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in p3)
+        io.params, io.rng_state = ptr(self.params), None
+        io.workspace, io.workspace_bytes = ptr(a.workspace), a.workspace.numel()
+        io.vals, io.fused, io.rnc, io.text_hidden, io.cross_text = (ptr(t) for t in a.outs)
+        if key_padding:
+            for i, t in enumerate(st.lengths):
+                io.lengths[i] = ptr(t)
+        io.prefetch_workgroups = self.prefetch_workgroups
+        return io
+
+    def _desc(self, store, plan, i, inplace, planes, key_padding):
+        st = self.arena.sets[i & 1]
+        B, T = plan.shapes[i]
+        lens = st.lengths if key_padding else None
+        if inplace:
+            return store.gather_desc(plan.idx_ptr(i), B, T, None, st.labels, lens, maps_out=st.ensure_maps())
+        return store.gather_desc(plan.idx_ptr(i), B, T, st.inputs, st.labels, lens, st.planes if planes else None)
+
+    def _segments(self, res, B, embeddings):
+        """the scatter's segment table for batches of B: rows [0, B) of every output to stream 0's result, rows [B, 2 B) to stream 1's"""
+        pairs = [(self.arena.outs[0], res.preds, 1)]
+        if embeddings:
+            pairs += [(self.arena.outs[j + 1], res.embeddings[name], int(np.prod(shape))) for j, (name, shape, _) in enumerate(EMBEDDINGS)]
+        n = res.preds.shape[1]
+        segs = (_lib.ScatterSeg * (2 * len(pairs)))()
+        for j, (src, dst, w) in enumerate(pairs):
+            for s in range(2):
+                sg = segs[2 * j + s]
+                sg.src, sg.dst = src.data_ptr() + 4 * s * B * w, dst.data_ptr() + 4 * s * n * w
+                sg.rows, sg.cols, sg.dst_rows = B, w, n
+        return segs
+
+    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None):
+        from .data import EpochPlan
+        n_store = len(store)
+        # ---- host-side checks: nothing is enqueued (and nothing of `out` is touched) before all of them have passed ----
+        if isinstance(batches, EpochPlan):
+            plan = batches
+            host = getattr(plan, "idx_h", None)
+            host = plan.idx_d.cpu() if host is None else host
+            bounds = list(plan.offsets) + [int(host.numel())]
+            check_epoch_indices([host[a:b] for a, b in zip(bounds, bounds[1:])], n_store)
+        else:
+            batches = [torch.as_tensor(b, dtype=torch.int64).reshape(-1) for b in batches]
+            check_epoch_indices(batches, n_store)
+            plan = None
+        if store.packed['audio'].device != self.params.device:
+            raise _lib.SdumcError("eval_epoch: the store and the parameters live on different devices")
+        inplace = self._in_place(store)
+        if not inplace and store.packed['audio'].dtype != self.feature_dtype:
+            raise _lib.SdumcError("eval_epoch: gathering needs a store that holds the features in the storage mode's dtype "
+                                  "(a bf16 store for bf16 storage, an fp32 store otherwise)")
+        if tuple(store.get_featdim()) != self._fdims:
+            raise _lib.SdumcError(f"eval_epoch: the store's feature widths {store.get_featdim()} are not {self._fdims}")
+        if out is not None and not (isinstance(out, EvalResult) and out.fits(n_store, self.params.device, embeddings)):
+            raise _lib.SdumcError("eval_epoch: out= is not a result of this store's size, device and embeddings setting")
+        if plan is None:
+            plan = store.plan_epoch(batches)
+        shapes = set(plan.shapes)
+        need = max(self._shape(s)[1] for s in shapes)
+        Bmax, Tmax = max(B for B, _ in shapes), tuple(max(T[i] for _, T in shapes) for i in range(4))
+        # ---- memory ----
+        a = self.arena
+        if a is None or not a.fits(Bmax, Tmax, need):
+            if a is not None:
+                Bmax, Tmax, need = max(Bmax, a.B), tuple(max(t, c) for t, c in zip(Tmax, a.T)), max(need, a.workspace.numel())
+            a = self.arena = _EvalArena(self.params.device, Bmax, Tmax, self._fdims, self.feature_dtype, need)
+        planes = False
+        if not inplace and store.packed_p3 is not None and self._planes_ok:
+            a.ensure_planes()
+            planes = True
+        res = (out if out is not None else EvalResult.empty(n_store, self.params.device, embeddings)).reset()
+        ios = [self._io(store, k, inplace, planes, key_padding) for k in range(2)]
+        segs, mark, st = {}, ptr(res.seen), _lib.current_stream()
+        # ---- the epoch: no host synchronisation from here on ----
+        n = len(plan)
+        g = self._desc(store, plan, 0, inplace, planes, key_padding)
+        check(lib.sdumc_gather_batch(C.byref(g), 0, st), "sdumc_gather_batch")
+        nxt = self._shape(plan.shapes[0])[0]
+        for i in range(n):
+            d, io, B = nxt, ios[i & 1], plan.shapes[i][0]
+            sg = segs.get(B)
+            if sg is None:
+                sg = segs[B] = self._segments(res, B, embeddings)
+            pf = None
+            if i + 1 < n:
+                nxt = self._shape(plan.shapes[i + 1])[0]
+                pf = self._desc(store, plan, i + 1, inplace, planes, key_padding)
+            io.prefetch = C.addressof(pf) if pf is not None else None
+            try:
+                check(lib.sdumc_net_forward(C.byref(d), C.byref(io), st), "sdumc_net_forward")
+            finally:
+                io.prefetch = None
+            check(lib.sdumc_scatter_rows_multi(sg, len(sg), plan.idx_ptr(i), B, mark, st), "sdumc_scatter_rows_multi")
+        self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers and scatters)
+        return res
+
+
+_evaluator = None      # eval_epoch's state: ONE evaluator (the last parameter buffer / mode asked for), so its arena is kept across epochs
+
+
+def eval_epoch(flat_params, dims, store, batches, *, bf16=False, key_padding=False, embeddings=False, inplace=True, out=None,
+               prefetch_workgroups=0):
+    """One evaluation pass over `batches` (index vectors into `store`, or a data.EpochPlan -- any subset of the store, any order, no
+    index twice) with the parameters `flat_params`: both streams in eval mode, -> EvalResult in store order.
+    bf16: the storage mode, as engine.TrainStep; key_padding=True hands the valid frame counts to the attention poolings (extension,
+    default off = the reference); embeddings=True also keeps the four embeddings of each stream; inplace=False gathers padded copies
+    even where the store could be read in place; out= reuses a previous result's tensors."""
+    global _evaluator
+    dims = tuple(int(d) for d in dims)
+    key = (flat_params.data_ptr(), flat_params.device, dims, engine.bf16_mode(bf16, dims), bool(inplace), int(prefetch_workgroups))
+    if _evaluator is None or _evaluator[0] != key:
+        _evaluator = (key, Evaluator(flat_params, dims, bf16=bf16, inplace=inplace, prefetch_workgroups=prefetch_workgroups))
+    return _evaluator[1].eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out)

@@ -603,6 +603,35 @@ def adam_multi(params, grads, m, v, state_offsets, hyper, beta1=0.9, beta2=0.999
                                grad_scale, _st()), "sdumc_adam_multi")
 
 
+def scatter_segments(srcs, dsts):
+    """The ctypes segment table of scatter_rows_multi: srcs[k] [rows_k, ...] -> dsts[k] [N_k, ...], both contiguous fp32 with the same
+    row width (kept by a caller that scatters the same tensors again and again)."""
+    if len(srcs) != len(dsts) or not 1 <= len(srcs) <= _lib.SCATTER_MAX_SEGS:
+        raise _lib.SdumcError(f"scatter_rows_multi: 1 .. {_lib.SCATTER_MAX_SEGS} (source, destination) pairs")
+    segs = (_lib.ScatterSeg * len(srcs))()
+    for s, src, dst in zip(segs, srcs, dsts):
+        for t in (src, dst):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < 1 or t.shape[0] < 1:
+                raise _lib.SdumcError("scatter_rows_multi: contiguous fp32 tensors with at least one row")
+        cols = src.numel() // src.shape[0]
+        if dst.numel() != dst.shape[0] * cols:
+            raise _lib.SdumcError("scatter_rows_multi: source and destination rows differ in width")
+        s.src, s.dst, s.rows, s.cols, s.dst_rows = src.data_ptr(), dst.data_ptr(), src.shape[0], cols, dst.shape[0]
+    return segs
+
+
+def scatter_rows_multi(srcs, dsts, idx, mark=None, segs=None):
+    """dsts[k][idx[r % B]] = srcs[k][r] for every row r of every pair, in one launch (idx: device int64 [B], distinct, in range --
+    the caller's duty); mark (optional uint8 / bool [N]): mark[idx[b]] = 1."""
+    if segs is None:
+        segs = scatter_segments(srcs, dsts)
+    if idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise _lib.SdumcError("scatter_rows_multi: idx must be a contiguous int64 tensor")
+    if mark is not None and (mark.element_size() != 1 or not mark.is_contiguous() or mark.numel() < segs[0].dst_rows):
+        raise _lib.SdumcError("scatter_rows_multi: mark must be a contiguous one-byte tensor with a byte per destination row")
+    check(lib.sdumc_scatter_rows_multi(segs, len(segs), ptr(idx), idx.numel(), ptr(mark), _st()), "sdumc_scatter_rows_multi")
+
+
 # ---- generic MHA / Transformer-encoder pieces (transformer.hip) ------------------------------------
 def layernorm_fwd(x, gamma, beta, eps=1e-5):
     width = x.shape[-1]
