@@ -716,6 +716,37 @@ typedef struct sdumc_gather_desc {
 } sdumc_gather_desc;
 int sdumc_gather_batch(const sdumc_gather_desc* g, int32_t max_workgroups, void* stream);
 
+/* Temporal pre-compression of a packed feature tensor on the device = func_mapping_feature (toolkit/utils/read_data.py:120-137)
+ * for every utterance of one modality at once: what feature_scale_compress, align_to_text and align_to_utt (:178-200) do per
+ * sample on the host in the dataset constructors (toolkit/data/feat_data.py:117-126, :398-407; the driver's --feat_scale and
+ * --feat_type, main_frame_val_text_missing.py:225-226).  Utterance e: source rows [src_start[e], + L), L = src_len[e]; destination
+ * rows [dst_start[e], + n), n = dst_len[e] >= 1:
+ *   L <= n: dst[j] = src[j] for j < L, zero for L <= j < n (the zero rows are frames from then on);
+ *   L >  n: q, r = divmod(L, n); pool = q, pad = 0 if r == 0, else pool = q + 1, pad = n - r (padding on the LEFT);
+ *           dst[j] = (sum over t in [0, pool) of src[j pool + t - pad]) / pool, a frame index below 0 contributing +0.
+ * Arithmetic: the sum in fp64 in frame order, ONE fp64 division by pool (never by the count of real frames), one rounding to fp32
+ * -- the reference promotes to float64 through its np.zeros padding and torch.FloatTensor rounds the result.  bf16 rows: the fp64
+ * quotient rounded to fp32, then to bf16 (the two roundings of fp32 -> .to(bfloat16)).
+ * The kernel ALSO writes destination row [dst_rows] as zeros: the store's trailing all-zero row (row maps name it).  dst therefore
+ * holds dst_rows + 1 rows, dst_rows = sum of dst_len.  dst_start must ascend (the owner of a row is found by binary search); a row
+ * no utterance owns, or whose source frames do not lie in [0, src_rows), is written as zeros -- nothing is read out of bounds.
+ * One wave per destination row, one 16-byte chunk per lane, every element offset in 64 bits; plain loads and stores only.
+ * max_workgroups > 0 caps the grid (the kernel strides), 0 = the default cap of 2048 workgroups.
+ * SDUMC_EINVAL, before anything is launched: desc or one of its six pointers NULL, src / dst not 16-byte aligned, a table not
+ * aligned to its element, cols < 1 or cols % 4 != 0 (cols % 8 != 0 for bf16), n_utts / src_rows / dst_rows < 1, bf16 not 0 or 1. */
+typedef struct sdumc_pool_desc {
+  const void* src;           /* [src_rows (+ anything), cols] fp32, or bf16 when bf16 = 1 */
+  void* dst;                 /* [dst_rows + 1, cols], same element type */
+  const int64_t* src_start;  /* device [n_utts] */
+  const int32_t* src_len;    /* device [n_utts] */
+  const int64_t* dst_start;  /* device [n_utts], ascending */
+  const int32_t* dst_len;    /* device [n_utts], every entry >= 1 */
+  int64_t src_rows, dst_rows;
+  int32_t n_utts, cols;
+  int32_t bf16;              /* 0: fp32 rows, 1: bf16 rows */
+} sdumc_pool_desc;
+int sdumc_pool_frames(const sdumc_pool_desc* p, int32_t max_workgroups, void* stream);
+
 /* ------------------------------------------------------------------------
  * Generic fairseq-style multi-head attention and the pieces of the pre-LN Transformer encoder
  * (toolkit/models/modules/transformers_encoder/, all three files).

@@ -213,6 +213,12 @@ class GatherBatch(C.Structure):
                 ("labels_all", C.c_void_p), ("labels_out", C.c_void_p), ("total", C.c_int64)]
 
 
+class PoolFrames(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_start", C.c_void_p), ("src_len", C.c_void_p),
+                ("dst_start", C.c_void_p), ("dst_len", C.c_void_p), ("src_rows", C.c_int64), ("dst_rows", C.c_int64),
+                ("n_utts", C.c_int32), ("cols", C.c_int32), ("bf16", C.c_int32)]
+
+
 class Softmax(C.Structure):
     _fields_ = [("batch", C.c_int32), ("heads", C.c_int32), ("tq", C.c_int32), ("tk", C.c_int32),
                 ("scale", C.c_float), ("mask", C.c_void_p), ("scores", C.c_void_p), ("probs_drop", C.c_void_p),
@@ -358,6 +364,7 @@ _SIGS = {
     "sdumc_gather_pad_idx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "sdumc_gather_batch": (C.c_int, [C.POINTER(GatherBatch), C.c_int32, C.c_void_p]),
+    "sdumc_pool_frames": (C.c_int, [C.POINTER(PoolFrames), C.c_int32, C.c_void_p]),
     "sdumc_fill": (C.c_int, [C.c_void_p, C.c_float, C.c_int64, C.c_void_p]),
     "sdumc_rng_advance": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "sdumc_dropout_bits": (C.c_int, [C.POINTER(Dropout), C.c_int32, C.c_void_p, C.c_void_p]),

@@ -70,6 +70,85 @@ def unpack(data, device):
             data[-2].float().to(device, non_blocking=True), data[-1])
 
 
+FEAT_TYPES = ('utt', 'frm_align', 'frm_unalign')      # --feat_type (main_frame_val_text_missing.py:225)
+_SRC = ('audio', 'text', 'video', 'feat4')
+
+
+def map_feature(feature, dst_len):
+    """[L, d] -> float32 [dst_len, d]: the reference's func_mapping_feature (read_data.py:120-137), quirks included.
+    L <= dst_len: the rows, then zero rows (frames from then on).  L > dst_len: q, r = divmod(L, dst_len); pool = q and no padding if
+    r == 0, else pool = q + 1 and dst_len - r zero frames in FRONT; row j = the sum of frames [j pool, (j + 1) pool) of the padded
+    sequence divided by pool (never by the count of real frames).  Summed in float64 in frame order, one division, one rounding to
+    float32: what the reference's float64 promotion (its np.zeros padding) followed by torch.FloatTensor computes, bit for bit."""
+    x = np.asarray(feature)
+    n = int(dst_len)
+    if x.ndim != 2 or n < 1:
+        from ._lib import SdumcError
+        raise SdumcError(f"map_feature: a [T, d] feature and dst_len >= 1, not shape {x.shape} and {dst_len!r}")
+    L, d = x.shape
+    if L <= n:
+        out = np.zeros((n, d), dtype=np.float32)
+        out[:L] = x
+        return out
+    q, r = divmod(L, n)
+    pool, pad = (q, 0) if r == 0 else (q + 1, n - r)
+    xp = np.concatenate([np.zeros((pad, d)), x.astype(np.float64)]).reshape(n, pool, d)
+    acc = xp[:, 0, :].copy()
+    for t in range(1, pool):
+        acc += xp[:, t, :]
+    return (acc / pool).astype(np.float32)
+
+
+def _resample_steps(feat_scale, feat_type):
+    """Validated (feat_scale, feat_type) -> the passes in the reference's order (feat_data.py:117-126: feat_scale first, feat_type
+    after it, so frm_align aligns to the COMPRESSED text length).  A pass is an integer k > 1, 'frm_align' or 'utt'."""
+    from ._lib import SdumcError
+    if isinstance(feat_scale, bool) or not isinstance(feat_scale, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(feat_scale) or feat_scale != int(feat_scale) or feat_scale < 1:
+        raise SdumcError(f"feat_scale must be an integer >= 1, not {feat_scale!r}")
+    if feat_type not in FEAT_TYPES:
+        raise SdumcError(f"feat_type must be one of {FEAT_TYPES}, not {feat_type!r}")
+    steps = [int(feat_scale)] if int(feat_scale) > 1 else []
+    if feat_type != 'frm_unalign':
+        steps.append(feat_type)
+    return steps
+
+
+def _target_lengths(lens, step):
+    """lens: the four modalities' frame counts (audio, text, video, feat4), integer arrays [N] -> the same after one pass."""
+    lens = [np.asarray(l, dtype=np.int64) for l in lens]
+    if step == 'utt':
+        return [np.ones_like(l) for l in lens]
+    if step == 'frm_align':
+        return [lens[1], lens[1], lens[1], lens[3]]      # audio, text, video to the text length; feat4 keeps its own
+    return [-(-l // step) for l in lens]                  # ceil(L / k), every modality on its own
+
+
+def resample_instances(instances, feat_scale=1, feat_type='frm_unalign'):
+    """The reference's --feat_scale / --feat_type on the host: feature_scale_compress, then align_to_text or align_to_utt
+    (read_data.py:178-200, applied in that order by the dataset constructors, feat_data.py:117-126) -> new instance dicts that
+    collate() and DeviceFeatureStore(...) accept (float32 [T', d] arrays; every other key is carried over).
+    feat_scale = k: every modality to ceil(T / k) frames, feat4 (the text slot of stream 1) by the same rule.  'frm_align': audio,
+    text and video to the utterance's text length, feat4 keeps its own.  'utt': one frame per modality.  'frm_unalign': nothing.
+    Every route is map_feature's float64 rule.  That includes 'utt', which stays [1, d]: the reference's align_to_utt is np.mean of
+    the float32 array (pairwise float32 sums, a 1-D float32 result) and so LESS exact than this route; the two agree to the
+    reference's own float32 rounding.  With both options the result of the first pass is rounded to float32 before the second (an
+    instance, like a store, holds float32), where the reference hands its float64 arrays on unrounded: at most 2^-24 of the pooled
+    magnitude apart.  DeviceFeatureStore.resampled computes the same on the device."""
+    steps = _resample_steps(feat_scale, feat_type)
+    out = [dict(inst) for inst in instances]
+    for inst in out:
+        for m in _SRC:
+            x = np.asarray(inst[m], dtype=np.float32)
+            inst[m] = x[np.newaxis, :] if x.ndim == 1 else x
+    for step in steps:
+        for inst in out:
+            tgt = _target_lengths([[inst[m].shape[0]] for m in _SRC], step)
+            for m, n in zip(_SRC, tgt):
+                inst[m] = map_feature(inst[m], int(n[0]))
+    return out
+
+
 class EpochPlan:
     """The batches of one epoch as the device sees them: ONE index tensor uploaded once (no per-batch host -> device copy inside the
     loop -- a pageable upload per step costs the host a synchronisation with the previous step), the host-side offsets into it and the
@@ -156,6 +235,60 @@ class DeviceFeatureStore:
             _lib.check(_lib.lib.sdumc_p3_split(_lib.ptr(src), d, _lib.ptr(dst), 6 * d, src.shape[0], d, _lib.current_stream()), "sdumc_p3_split")
             self.packed_p3[m] = dst
         return self
+
+    def resampled(self, feat_scale=1, feat_type='frm_unalign', planes=None):
+        """The reference's --feat_scale / --feat_type (feature_scale_compress, align_to_text, align_to_utt: read_data.py:178-200,
+        applied in the dataset constructors, feat_data.py:117-126) on the resident store: a NEW store with fewer (or aligned) frames
+        per utterance, pooled on the device by sdumc_pool_frames -- one HBM-bound pass per modality, no feature byte crosses PCIe.
+        Semantics and arithmetic are resample_instances': feat_scale first, feat_type after it (two passes when both are given).
+        Same names, vals, emos, device and storage dtype; new packed / start / length tables (computed on the host, uploaded once).
+        planes: None = as the source (rebuilt with make_planes()), True / False overrides.  The source is left untouched;
+        feat_scale == 1 with 'frm_unalign' returns self.  Bad arguments raise SdumcError before anything is enqueued."""
+        _lib = self._lib
+        steps = _resample_steps(feat_scale, feat_type)
+        if not steps:
+            return self
+        want_planes = (self.packed_p3 is not None) if planes is None else bool(planes)
+        if want_planes and any(t.dtype != torch.float32 for t in self.packed.values()):
+            raise _lib.SdumcError("planes: the store holds bf16 features (the bf16-storage step reads them as they are)")
+        if want_planes and any(self.dim[m] % 64 for m in self.MODS):
+            raise _lib.SdumcError("planes: feature widths must be multiples of 64")
+        store = self
+        for step in steps:
+            store = store._pooled(_target_lengths([store._len_np[m] for m in self.MODS], step))
+        if want_planes:
+            store.make_planes()
+        return store
+
+    def _pooled(self, targets):
+        """A new store (no planes) whose modality m holds targets[k][e] frames of utterance e: one sdumc_pool_frames launch each."""
+        C, _lib = self._C, self._lib
+        new = type(self).__new__(type(self))
+        new._C, new._lib, new.device = C, _lib, self.device
+        new.names, new.vals, new.emos = list(self.names), self.vals, self.emos
+        new.packed, new.start, new.length, new.dim = {}, {}, {}, dict(self.dim)
+        new.packed_p3 = None
+        for m, tgt in zip(self.MODS, targets):
+            tgt = np.asarray(tgt, dtype=np.int64)
+            rows = int(tgt.sum())
+            if tgt.shape != self._len_np[m].shape or int(tgt.min()) < 1 or rows >= 2 ** 31 - 1:
+                raise _lib.SdumcError(f"resample: bad target lengths for '{m}'")
+            new.start[m] = torch.from_numpy(np.concatenate([[0], np.cumsum(tgt)[:-1]]).astype(np.int64))
+            new.length[m] = torch.from_numpy(tgt.astype(np.int32))
+        new._device_tables()
+        for m in self.MODS:
+            src = self.packed[m]
+            rows = int(new.length[m].sum())
+            dst = torch.empty(rows + 1, self.dim[m], dtype=src.dtype, device=self.device)
+            p = _lib.PoolFrames()
+            p.src, p.dst = _lib.ptr(src), _lib.ptr(dst)
+            p.src_start, p.src_len = _lib.ptr(self.start_d[m]), _lib.ptr(self.length_d[m])
+            p.dst_start, p.dst_len = _lib.ptr(new.start_d[m]), _lib.ptr(new.length_d[m])
+            p.src_rows, p.dst_rows = int(src.shape[0]) - 1, rows
+            p.n_utts, p.cols, p.bf16 = len(self), self.dim[m], int(src.dtype == torch.bfloat16)
+            _lib.check(_lib.lib.sdumc_pool_frames(C.byref(p), 0, _lib.current_stream()), "sdumc_pool_frames")
+            new.packed[m] = dst
+        return new
 
     @property
     def nbytes(self):
