@@ -1102,6 +1102,40 @@ int32_t sdumc_debug_plan_table(const sdumc_net_dims* d, char* buf, size_t buflen
 size_t sdumc_net_workspace_bytes(const sdumc_net_dims* d);
 int sdumc_net_forward(const sdumc_net_dims* d, const sdumc_net_io* io, void* stream);
 
+/* The attention maps of a completed EVAL-mode sdumc_net_forward, per frame and in STORE order (csrc/attn_export.hip).  The
+ * reference returns the softmax-over-time weights of its six poolings per stream from both modules (vector_attention, model :68,
+ * :95), collects them in forward (attention_masks, model :291) and carries the loop that plots them per utterance in its inference
+ * script (main_frame_val_text_missing_inference.py:92, :125, :176-181).  The engine computes and normalises them in its workspace on
+ * every route (pair / multi partial + combine; K3; the clustered stages' fold; fp32 and bf16 storage: the weights are fp32 in
+ * both), so this entry only COPIES: it rebuilds the workspace plan from `d` (as sdumc_debug_plan_table), finds the weights inside
+ * io->workspace and writes, for stream s, modality m, batch sample b and frame t < length[idx[b]], row start[idx[b]] + t of
+ * dst[s][m]:
+ *   column 0      the FRA2UTT_new weight of that frame
+ *   columns 1..7  the seven Cross_Attention weights, in multi_query order (fused, at, tv, av, audio, text, video; model :332)
+ * Frames t >= length (the collater's padding) are not exported; rows of utterances not in the batch are not touched; an idx outside
+ * [0, n_utt) is skipped, never written.  ONE launch, plain 16-byte stores, 64-bit row addressing, no atomics: a repeated launch
+ * gives the same bits.  No host synchronisation.
+ * Ordering: stream-ordered behind the forward on `stream`; the workspace holds these weights only until the next forward into it,
+ * so the call goes between forward i and forward i + 1 -- where sdumc_scatter_rows_multi goes.  Train-mode weights are computed under
+ * dropout and are not what the reference plots: export after eval-mode forwards.
+ * Semantics: without sdumc_net_io.lengths (the reference's behaviour) the softmax runs over the batch's PADDED length and the padded
+ * frames take part, so an utterance's exported weights depend on the batch it was evaluated in and sum to at most 1 over its valid
+ * frames -- what the reference's vector_attention[:, :len] would show.  With lengths (key padding) they sum to 1 and do not depend
+ * on the batch.
+ * SDUMC_EINVAL, before anything is launched: d / io / e / e->idx / io->workspace NULL; n_utt < 1; dims the engine refuses
+ * (sdumc_net_workspace_bytes == 0); for a (stream, modality) the dims contain: a NULL start / length table or destination, a
+ * destination not 16-byte aligned, dst_rows < 1; streams == 1 with a non-NULL dst[1][*].  SDUMC_ENOMEM: io->workspace_bytes below
+ * sdumc_net_workspace_bytes(d). */
+typedef struct sdumc_attn_export {
+  const int64_t* idx;          /* device int64 [B]: the batch's index vector (as sdumc_gather_desc.idx) */
+  const int64_t* start[4];     /* store-wide tables, device: first packed row of every utterance; audio, text, video, feat4 */
+  const int32_t* length[4];    /* store-wide tables, device: frames of every utterance */
+  int64_t n_utt;               /* utterances in the store (an idx outside [0, n_utt) is skipped, never written) */
+  float* dst[2][3];            /* [stream][audio, text-slot, video]: [dst_rows, 8] fp32; stream 1's text slot is feat4 */
+  int64_t dst_rows[2][3];      /* packed rows of that modality in the store (without the trailing zero row) */
+} sdumc_attn_export;
+int sdumc_net_export_attention(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_attn_export* e, void* stream);
+
 typedef struct sdumc_net_grads {
   const float* d_vals;        /* gradients w.r.t. the five outputs, same shapes; NULL = zero */
   const float* d_fused;

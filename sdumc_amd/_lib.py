@@ -267,6 +267,11 @@ class ScatterSeg(C.Structure):      # sdumc_scatter_seg: dst[idx[r % B], 0:cols]
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("dst_rows", C.c_int64)]
 
 
+class AttnExport(C.Structure):      # sdumc_attn_export: a completed eval-mode forward's attention weights -> store-ordered [rows, 8] tensors
+    _fields_ = [("idx", C.c_void_p), ("start", C.c_void_p * 4), ("length", C.c_void_p * 4), ("n_utt", C.c_int64),
+                ("dst", (C.c_void_p * 3) * 2), ("dst_rows", (C.c_int64 * 3) * 2)]
+
+
 ADAM_MAX_SEGS = 96
 
 
@@ -403,6 +408,7 @@ _SIGS = {
     "sdumc_net_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_net_bits_next_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_net_forward": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.c_void_p]),
+    "sdumc_net_export_attention": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(AttnExport), C.c_void_p]),
     "sdumc_net_backward": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(NetGrads), C.c_void_p]),
     "sdumc_net_backward_phase": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(NetGrads), C.c_int32, C.c_void_p]),
     "sdumc_param_early_count": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),

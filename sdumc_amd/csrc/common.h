@@ -173,6 +173,16 @@ int sdumc_p3_split_frag_multi_(const float* P, void* dst, const int64_t* src_off
                                const int32_t* cols, int n, void* stream);
 int sdumc_chain_transpose_(const float* src, float* dst, const int64_t* offs, const int32_t* outs, const int32_t* ins, int n,
                            void* stream);
+// engine.hip, for attn_export.hip: where the workspace plan of `d` keeps the attention weights.  attn[k][m] = float offset of site
+// kind k (0 FRA2UTT_new, 1 Cross_Attention) of modality m (audio, text slot, video) inside sdumc_net_io.workspace; T[m][s] = padded
+// frames of stream s; total = floats of the whole plan.  SDUMC_EINVAL: dims the engine refuses.  Host only, no HIP call.
+struct sdumc_attn_layout {
+  int32_t B, S;
+  int32_t T[3][2];
+  int64_t attn[2][3];
+  int64_t total;
+};
+int sdumc_plan_attn_layout_(const sdumc_net_dims* d, struct sdumc_attn_layout* out);
 }
 
 // ---------------------------------------------------------------------------

@@ -529,6 +529,7 @@ extern "C" int sdumc_preload_gemm_group_(void);
 extern "C" int sdumc_preload_gemm_rows_(void);
 extern "C" int sdumc_preload_gemm_bf16_(void);
 extern "C" int sdumc_preload_attn_pool_(void);
+extern "C" int sdumc_preload_attn_export_(void);
 extern "C" int sdumc_preload_elementwise_(void);
 extern "C" int sdumc_preload_loss_(void);
 extern "C" int sdumc_preload_adam_(void);
@@ -552,6 +553,7 @@ void preload_code_objects() {
     ok = sdumc_preload_gemm_rows_() == SDUMC_OK && ok;
     ok = sdumc_preload_gemm_bf16_() == SDUMC_OK && ok;
     ok = sdumc_preload_attn_pool_() == SDUMC_OK && ok;
+    ok = sdumc_preload_attn_export_() == SDUMC_OK && ok;
     ok = sdumc_preload_elementwise_() == SDUMC_OK && ok;
     ok = sdumc_preload_loss_() == SDUMC_OK && ok;
     ok = sdumc_preload_adam_() == SDUMC_OK && ok;
@@ -3057,6 +3059,20 @@ extern "C" int32_t sdumc_debug_plan_table(const sdumc_net_dims* d, char* buf, si
   if (!buf || s.size() + 1 > buflen) return -(int32_t)(s.size() + 1);
   memcpy(buf, s.c_str(), s.size() + 1);
   return (int32_t)s.size();
+}
+
+// attn_export.hip (sdumc_net_export_attention): the attention weights' place in the plan of `d`
+extern "C" int sdumc_plan_attn_layout_(const sdumc_net_dims* d, sdumc_attn_layout* out) {
+  Plan p;
+  if (!d || !out || !make_plan(*d, p)) return SDUMC_EINVAL;
+  out->B = p.B;
+  out->S = p.S;
+  for (int m = 0; m < 3; ++m)
+    for (int s = 0; s < 2; ++s) out->T[m][s] = p.T[m][s];
+  for (int k = 0; k < 2; ++k)
+    for (int m = 0; m < 3; ++m) out->attn[k][m] = p.attn[k][m];
+  out->total = p.cur;
+  return SDUMC_OK;
 }
 
 // gradient bucket of the most recent sdumc_train_step inside its workspace (for tests / DP all-reduce)

@@ -881,16 +881,17 @@ class FusedTrainer:
         self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers)
         return n
 
-    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None):
+    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
         """One evaluation pass (main :151-166: both streams, eval mode) over `batches` of `store` with the trainer's parameters, in its
         storage mode and with its inplace / planes choices -> evaluate.EvalResult in store order.  Evaluation owns its memory
-        (evaluate.Evaluator, made on first use and kept): it touches nothing of the training run but reads the parameters."""
+        (evaluate.Evaluator, made on first use and kept): it touches nothing of the training run but reads the parameters.
+        attention=True also keeps the per-frame attention maps (EvalResult.attention; evaluate.eval_epoch has the semantics)."""
         if getattr(self, "_evaluator", None) is None:
             from .evaluate import Evaluator
             kw = self._arena_kw
             self._evaluator = Evaluator(self.params, self.dims, bf16=kw["bf16"], inplace=self.inplace, planes=kw["planes"],
                                         prefetch_workgroups=kw["prefetch_workgroups"])
-        return self._evaluator.eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out)
+        return self._evaluator.eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out, attention=attention)
 
     def step(self, audio, text, video, feat4, labels, lengths=None):
         """One optimisation step on one batch of any shape; returns the device loss vector

@@ -12,7 +12,12 @@ inside the loop.  The metrics stay on the host (metric.py): [N] vectors cross on
 
 Evaluation owns its device memory (_EvalArena): workspace, outputs, two sets of row maps / labels / lengths (and input buffers when
 batches are gathered).  It reads the flat parameters and nothing else of a training run -- no step workspace, no keep-bits, no
-Philox counter (rng_state = NULL) -- so a training run is bit for bit the same with or without evaluation epochs in between."""
+Philox counter (rng_state = NULL) -- so a training run is bit for bit the same with or without evaluation epochs in between.
+
+attention=True keeps what the reference's inference pass plots per utterance (vector_attention of FRA2UTT_new / Cross_Attention,
+model :68, :95; attention_masks, model :291; main_frame_val_text_missing_inference.py:176-181): ONE more launch per batch
+(sdumc_net_export_attention, between the forward and the scatter) copies the six poolings' normalised softmax-over-time weights of
+both streams out of the forward's workspace to per-frame tensors in store order (EvalResult.attention)."""
 import ctypes as C
 
 import numpy as np
@@ -27,6 +32,24 @@ EMBEDDINGS = (("fused", (H,), ("full_rep", "missing_rep")),
               ("rnc", (RNC_DIM,), ("full_rnc", "missing_rnc")),
               ("text_hidden", (D,), ("text_rep_query_full", "text_rep_query_missing")),
               ("cross_text", (NQ, H), ("text_rep_full", "text_rep_missing")))
+# the attention maps: per stream, the modalities its three pooling pairs read (stream 1's text slot is feat4); every tensor
+# [packed rows of that modality, ATTN_COLS]: column 0 FRA2UTT_new's weight, columns 1..7 Cross_Attention's in multi_query order
+ATTENTION = (("full", ("audio", "text", "video")), ("missing", ("audio", "feat4", "video")))
+ATTN_COLS = 1 + NQ
+MODS = ("audio", "text", "video", "feat4")
+
+
+def attention_rows(store):
+    """{modality: packed rows (frames of all utterances, without the trailing zero row)} of a store -- from its host tables"""
+    return {m: int(torch.as_tensor(store.length[m]).sum()) for m in MODS}
+
+
+def _rows_dict(rows):
+    if rows is None:
+        raise _lib.SdumcError("EvalResult: attention=True needs rows= (evaluate.attention_rows(store), or the four row counts)")
+    if not isinstance(rows, dict):
+        rows = dict(zip(MODS, rows))
+    return {m: int(rows[m]) for m in MODS}
 
 
 def check_epoch_indices(batches, n):
@@ -47,21 +70,35 @@ def check_epoch_indices(batches, n):
 class EvalResult:
     """Results of one evaluation epoch in STORE order (row i = utterance i of the store): preds [2, N] (row 0 the full stream, row 1
     the text-missing one), seen [N] (uint8 / bool: visited this epoch), embeddings None or {'fused' [2, N, 128], 'rnc' [2, N, 64],
-    'text_hidden' [2, N, 256], 'cross_text' [2, N, 7, 128]}.  Rows not visited hold NaN.  Device or CPU tensors."""
+    'text_hidden' [2, N, 256], 'cross_text' [2, N, 7, 128]}, attention None or {'full': {'audio', 'text', 'video'}, 'missing':
+    {'audio', 'feat4', 'video'}} of [rows_m, 8] tensors, rows_m = the frames of all utterances of that modality in store order
+    (row start[i] + t = frame t of utterance i; column 0 the FRA2UTT_new weight, columns 1..7 the Cross_Attention weights in
+    multi_query order: fused, at, tv, av, audio, text, video).  Rows not visited hold NaN.  Device or CPU tensors."""
 
-    def __init__(self, preds, seen, embeddings=None):
-        self.preds, self.seen, self.embeddings = preds, seen, embeddings
+    def __init__(self, preds, seen, embeddings=None, attention=None):
+        self.preds, self.seen, self.embeddings, self.attention = preds, seen, embeddings, attention
 
     @classmethod
-    def empty(cls, n, device, embeddings=False):
-        emb = None
+    def empty(cls, n, device, embeddings=False, attention=False, rows=None):
+        """attention=True: rows = attention_rows(store) (or the four row counts, audio / text / video / feat4)"""
+        emb = att = None
         if embeddings:
             emb = {name: torch.empty((2, n) + shape, device=device) for name, shape, _ in EMBEDDINGS}
-        return cls(torch.empty(2, n, device=device), torch.empty(n, dtype=torch.uint8, device=device), emb)
+        if attention:
+            rows = _rows_dict(rows)
+            att = {s: {m: torch.empty(rows[m], ATTN_COLS, device=device) for m in mods} for s, mods in ATTENTION}
+        return cls(torch.empty(2, n, device=device), torch.empty(n, dtype=torch.uint8, device=device), emb, att)
 
-    def fits(self, n, device, embeddings):
-        return (self.preds.shape == (2, n) and self.preds.device == torch.device(device) and self.seen.numel() == n
-                and self.seen.element_size() == 1 and (self.embeddings is not None) == bool(embeddings))
+    def fits(self, n, device, embeddings, attention=False, rows=None):
+        ok = (self.preds.shape == (2, n) and self.preds.device == torch.device(device) and self.seen.numel() == n
+              and self.seen.element_size() == 1 and (self.embeddings is not None) == bool(embeddings)
+              and (self.attention is not None) == bool(attention))
+        if ok and attention:
+            rows = _rows_dict(rows)
+            ok = all(s in self.attention and m in self.attention[s] and self.attention[s][m].shape == (rows[m], ATTN_COLS)
+                     and self.attention[s][m].device == torch.device(device) and self.attention[s][m].dtype == torch.float32
+                     and self.attention[s][m].is_contiguous() for s, mods in ATTENTION for m in mods)
+        return ok
 
     def reset(self):
         """NaN everywhere, nothing seen: once per epoch, in front of its first batch"""
@@ -69,7 +106,34 @@ class EvalResult:
         self.seen.zero_()
         for t in (self.embeddings or {}).values():
             t.fill_(float("nan"))
+        for d in (self.attention or {}).values():
+            for t in d.values():
+                t.fill_(float("nan"))
         return self
+
+    def attention_of(self, store, i):
+        """The attention maps of ONE utterance -- i = its index in the store, or its name -- as views: {'full': {'audio' [T_a, 8],
+        'text' [T_t, 8], 'video' [T_v, 8]}, 'missing': {'audio', 'feat4' [T_f4, 8], 'video'}}, sliced by the store's start / length
+        tables.  Raises when the epoch kept no attention maps or did not visit the utterance."""
+        if self.attention is None:
+            raise _lib.SdumcError("EvalResult: this epoch kept no attention maps (eval_epoch(..., attention=True))")
+        if isinstance(i, str):
+            try:
+                i = store.names.index(i)
+            except ValueError:
+                raise _lib.SdumcError(f"EvalResult: no utterance named {i!r} in the store") from None
+        i = int(i)
+        if not 0 <= i < self.seen.numel():
+            raise _lib.SdumcError(f"EvalResult: utterance index {i} out of range [0, {self.seen.numel()})")
+        if int(self.seen.reshape(-1)[i]) == 0:
+            raise _lib.SdumcError(f"EvalResult: utterance {i} was not visited in this epoch")
+        out = {}
+        for s, mods in ATTENTION:
+            out[s] = {}
+            for m in mods:
+                a, n = int(store.start[m][i]), int(store.length[m][i])
+                out[s][m] = self.attention[s][m][a:a + n]
+        return out
 
     def _visited(self):
         rows = np.flatnonzero(self.seen.cpu().numpy().reshape(-1) != 0)
@@ -208,7 +272,19 @@ class Evaluator:
                 sg.rows, sg.cols, sg.dst_rows = B, w, n
         return segs
 
-    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None):
+    def _export(self, store, res):
+        """the export's descriptor for one epoch (idx is set per batch): the store's device tables, the result's six tensors"""
+        e = _lib.AttnExport()
+        for k, m in enumerate(MODS):
+            e.start[k], e.length[k] = ptr(store.start_d[m]), ptr(store.length_d[m])
+        e.n_utt = len(store)
+        for s, (name, mods) in enumerate(ATTENTION):
+            for j, m in enumerate(mods):
+                t = res.attention[name][m]
+                e.dst[s][j], e.dst_rows[s][j] = ptr(t), int(t.shape[0])
+        return e
+
+    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
         from .data import EpochPlan
         n_store = len(store)
         # ---- host-side checks: nothing is enqueued (and nothing of `out` is touched) before all of them have passed ----
@@ -230,8 +306,11 @@ class Evaluator:
                                   "(a bf16 store for bf16 storage, an fp32 store otherwise)")
         if tuple(store.get_featdim()) != self._fdims:
             raise _lib.SdumcError(f"eval_epoch: the store's feature widths {store.get_featdim()} are not {self._fdims}")
-        if out is not None and not (isinstance(out, EvalResult) and out.fits(n_store, self.params.device, embeddings)):
-            raise _lib.SdumcError("eval_epoch: out= is not a result of this store's size, device and embeddings setting")
+        rows = attention_rows(store) if attention else None
+        if attention and min(rows.values()) < 1:
+            raise _lib.SdumcError("eval_epoch: attention=True needs a store with at least one frame per modality")
+        if out is not None and not (isinstance(out, EvalResult) and out.fits(n_store, self.params.device, embeddings, attention, rows)):
+            raise _lib.SdumcError("eval_epoch: out= is not a result of this store's size, device, embeddings and attention setting")
         if plan is None:
             plan = store.plan_epoch(batches)
         shapes = set(plan.shapes)
@@ -247,8 +326,9 @@ class Evaluator:
         if not inplace and store.packed_p3 is not None and self._planes_ok:
             a.ensure_planes()
             planes = True
-        res = (out if out is not None else EvalResult.empty(n_store, self.params.device, embeddings)).reset()
+        res = (out if out is not None else EvalResult.empty(n_store, self.params.device, embeddings, attention, rows)).reset()
         ios = [self._io(store, k, inplace, planes, key_padding) for k in range(2)]
+        exp = self._export(store, res) if attention else None
         segs, mark, st = {}, ptr(res.seen), _lib.current_stream()
         # ---- the epoch: no host synchronisation from here on ----
         n = len(plan)
@@ -269,6 +349,9 @@ class Evaluator:
                 check(lib.sdumc_net_forward(C.byref(d), C.byref(io), st), "sdumc_net_forward")
             finally:
                 io.prefetch = None
+            if exp is not None:      # (the workspace holds this batch's weights until the next forward into it)
+                exp.idx = plan.idx_ptr(i)
+                check(lib.sdumc_net_export_attention(C.byref(d), C.byref(io), C.byref(exp), st), "sdumc_net_export_attention")
             check(lib.sdumc_scatter_rows_multi(sg, len(sg), plan.idx_ptr(i), B, mark, st), "sdumc_scatter_rows_multi")
         self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers and scatters)
         return res
@@ -278,15 +361,22 @@ _evaluator = None      # eval_epoch's state: ONE evaluator (the last parameter b
 
 
 def eval_epoch(flat_params, dims, store, batches, *, bf16=False, key_padding=False, embeddings=False, inplace=True, out=None,
-               prefetch_workgroups=0):
+               prefetch_workgroups=0, attention=False):
     """One evaluation pass over `batches` (index vectors into `store`, or a data.EpochPlan -- any subset of the store, any order, no
     index twice) with the parameters `flat_params`: both streams in eval mode, -> EvalResult in store order.
     bf16: the storage mode, as engine.TrainStep; key_padding=True hands the valid frame counts to the attention poolings (extension,
     default off = the reference); embeddings=True also keeps the four embeddings of each stream; inplace=False gathers padded copies
-    even where the store could be read in place; out= reuses a previous result's tensors."""
+    even where the store could be read in place; out= reuses a previous result's tensors.
+    attention=True also keeps the attention maps (EvalResult.attention, EvalResult.attention_of): per stream and modality one
+    [frames of the store, 8] tensor -- column 0 FRA2UTT_new's softmax-over-time weight of the frame, columns 1..7 Cross_Attention's
+    seven (fused, at, tv, av, audio, text, video) -- written by one more launch per batch; with attention=False the epoch enqueues
+    exactly what it did without the option.  With key_padding=False (the reference) the softmax runs over the batch's PADDED
+    length and the padded frames take part: an utterance's weights then depend on the batch it was evaluated in and sum to at most
+    1 over its valid frames -- what the reference's vector_attention[:, :len] would show.  With key_padding=True they sum to 1 and
+    do not depend on the batch."""
     global _evaluator
     dims = tuple(int(d) for d in dims)
     key = (flat_params.data_ptr(), flat_params.device, dims, engine.bf16_mode(bf16, dims), bool(inplace), int(prefetch_workgroups))
     if _evaluator is None or _evaluator[0] != key:
         _evaluator = (key, Evaluator(flat_params, dims, bf16=bf16, inplace=inplace, prefetch_workgroups=prefetch_workgroups))
-    return _evaluator[1].eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out)
+    return _evaluator[1].eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out, attention=attention)
