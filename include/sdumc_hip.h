@@ -885,6 +885,47 @@ typedef struct sdumc_scatter_seg {
 } sdumc_scatter_seg;
 int sdumc_scatter_rows_multi(const sdumc_scatter_seg* segs, int32_t n, const int64_t* idx, int32_t B, uint8_t* mark,
                              void* stream);
+/* The record a TRAINING epoch keeps of each step: one call, stream-ordered behind a completed sdumc_train_step, no host
+ * synchronisation.  The reference's training pass is the same function as its evaluation pass: it appends every batch's train-mode
+ * predictions of both streams (main_frame_val_text_missing.py:156-158), returns them with their MSE (:160-178) and the driver prints
+ * train_val_mse_full / train_val_mse_missing once per epoch (:348); the inference variant keeps the four embeddings too
+ * (main_frame_val_text_missing_inference.py:166-175).  When the step returns, its losses, its stream-major outputs
+ * (sdumc_net_io.vals / fused / rnc / text_hidden / cross_text) and its raw gradients (the bucket at sdumc_step_grads_offset: Adam adds
+ * the coupled L2 term inside its own kernel, so the bucket is without it) are on the device; this call files them away.  It reads the
+ * step's memory and writes only log_row, the segments' destinations, mark and scratch: a run is bit for bit the same with or without it.
+ * Three parts, each optional by its fields:
+ *   scatter   nseg (0 .. SDUMC_SCATTER_MAX_SEGS) segments, idx, B, mark: exactly sdumc_scatter_rows_multi (the same device code and
+ *             the same segment rules); nseg = 0: none.
+ *   log row   log_row[0..7] = losses[0..7] as they stand, [8] = grad_norm, [9] = the number of non-finite gradient elements,
+ *             [10] = B, [11] = hyper[0], the learning rate the step used.
+ *   gradients grads != NULL: grad_norm = the L2 norm over all n_grads floats, accumulated in fp64 (a sum of fp32 squares cannot
+ *             overflow there) and rounded ONCE to fp32 -- so a norm beyond the fp32 range comes out as +Inf (4099 elements of 3e38:
+ *             1.9e40 in fp64, +Inf in the row); NaN and +-Inf elements propagate as in torch.linalg.vector_norm.  [9] counts the
+ *             elements that are NaN or +-Inf, exactly while n_grads < 2^24.  Fixed order: every workgroup owns a contiguous slice and
+ *             folds it in a fixed lane order to one fp64 partial in scratch; a second launch of one workgroup adds the partials in
+ *             index order and writes the row: the same input gives the same bits on every call.  16-byte loads from the first
+ *             aligned address on, whatever the base.  grads == NULL: [8] = NaN, [9] = 0, no reduce workgroups, one launch.
+ *             (A one-launch form -- a ticket in scratch, the last workgroup to arrive adds the partials -- was built and measured:
+ *             it tied with this one in the epoch, and the form without communication between workgroups was kept.)
+ * scratch: caller-owned, sdumc_epoch_record_scratch_bytes of n_grads bytes (0 for n_grads < 1), 16-byte aligned; every call writes what
+ * it reads of it, so it needs no initial value and is ready again after every call; one call at a time per scratch.  No atomics.
+ * SDUMC_EINVAL, before anything is launched: r / log_row / losses / hyper NULL or not 4-byte aligned, nseg < 0 or >
+ * SDUMC_SCATTER_MAX_SEGS, nseg > 0 with idx NULL or B < 1 or a segment sdumc_scatter_rows_multi would refuse, grads != NULL with
+ * n_grads < 1, scratch NULL, grads not 4-byte or scratch not 16-byte aligned. */
+typedef struct sdumc_epoch_rec {
+  sdumc_scatter_seg seg[SDUMC_SCATTER_MAX_SEGS];
+  int32_t nseg, B;
+  const int64_t* idx;    /* device int64 [B]: the batch's rows in the store */
+  uint8_t* mark;         /* optional, uint8 [seg[0].dst_rows] */
+  const float* losses;   /* device float[8]: sdumc_step_cfg.losses */
+  const float* hyper;    /* device float[4]: sdumc_step_cfg.hyper */
+  float* log_row;        /* device float[12] */
+  const float* grads;    /* optional: the step's gradient bucket */
+  int64_t n_grads;
+  void* scratch;
+} sdumc_epoch_rec;
+size_t sdumc_epoch_record_scratch_bytes(int64_t n_grads);
+int sdumc_epoch_record(const sdumc_epoch_rec* r, void* stream);
 /* dst[r, 0:cols] = src[r, 0:cols] for r < rows, with leading dimensions */
 /* dst[r, 0:cols] += src[r, 0:cols] */
 int sdumc_axpy2d(const float* src, int32_t ld_src, float* dst, int32_t ld_dst, int32_t rows, int32_t cols, void* stream);

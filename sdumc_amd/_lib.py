@@ -267,6 +267,15 @@ class ScatterSeg(C.Structure):      # sdumc_scatter_seg: dst[idx[r % B], 0:cols]
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32), ("dst_rows", C.c_int64)]
 
 
+LOG_COLS = 12      # sdumc_epoch_rec.log_row: losses[0..7], grad_norm, non-finite gradient elements, B, learning rate
+
+
+class EpochRec(C.Structure):        # sdumc_epoch_rec: a completed train step's outputs -> store order, its log row, its gradient norm
+    _fields_ = [("seg", ScatterSeg * SCATTER_MAX_SEGS), ("nseg", C.c_int32), ("B", C.c_int32), ("idx", C.c_void_p),
+                ("mark", C.c_void_p), ("losses", C.c_void_p), ("hyper", C.c_void_p), ("log_row", C.c_void_p),
+                ("grads", C.c_void_p), ("n_grads", C.c_int64), ("scratch", C.c_void_p)]
+
+
 class AttnExport(C.Structure):      # sdumc_attn_export: a completed eval-mode forward's attention weights -> store-ordered [rows, 8] tensors
     _fields_ = [("idx", C.c_void_p), ("start", C.c_void_p * 4), ("length", C.c_void_p * 4), ("n_utt", C.c_int64),
                 ("dst", (C.c_void_p * 3) * 2), ("dst_rows", (C.c_int64 * 3) * 2)]
@@ -287,6 +296,8 @@ class AdamTable(C.Structure):      # one launch's kernel argument (filled by sdu
 _SIGS = {
     "sdumc_copy2d_multi": (C.c_int, [C.POINTER(CopySeg), C.c_int32, C.c_void_p]),
     "sdumc_scatter_rows_multi": (C.c_int, [C.POINTER(ScatterSeg), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "sdumc_epoch_record_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "sdumc_epoch_record": (C.c_int, [C.POINTER(EpochRec), C.c_void_p]),
     "sdumc_profile_enable": (C.c_int, [C.c_int]),
     "sdumc_profile_report": (C.c_int, [C.POINTER(ProfEntry), C.c_int]),
     "sdumc_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(Gemm)]),

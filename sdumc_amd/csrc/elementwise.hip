@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "scatter_rows.h"
 
 namespace {
 
@@ -91,36 +92,10 @@ __global__ void copy2d_multi_kernel(const CopySegs cs) {
 }
 
 // dst_k[idx[r % B], :] = src_k[r, :]: one launch puts the outputs of an eval-mode forward (stream-major [2B, w]) at the rows the
-// batch's utterances have in the store (sdumc_scatter_rows_multi).  blockIdx.y = segment; a lane moves 16 bytes where the segment's
-// width and base addresses allow it (vec, decided by the entry), one float otherwise.  64-bit row addressing; an index outside
-// [0, dst_rows) is skipped.
-struct ScatterSegs {
-  sdumc_scatter_seg s[SDUMC_SCATTER_MAX_SEGS];
-  uint8_t vec[SDUMC_SCATTER_MAX_SEGS];
-  const int64_t* idx;
-  uint8_t* mark;
-  int32_t B;
-};
+// batch's utterances have in the store (sdumc_scatter_rows_multi).  blockIdx.y = segment; the body (and the argument rules of the
+// entry) live in scatter_rows.h, shared with the training epoch's record launch (epoch_record.hip).
 __global__ __launch_bounds__(256) void scatter_rows_multi_kernel(const ScatterSegs ss) {
-  const sdumc_scatter_seg& sg = ss.s[blockIdx.y];
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
-  if (blockIdx.y == 0 && ss.mark)
-    for (int64_t b = tid; b < ss.B; b += nthr) {
-      const int64_t e = ss.idx[b];
-      if ((uint64_t)e < (uint64_t)sg.dst_rows) ss.mark[e] = 1;
-    }
-  const int lpr = ss.vec[blockIdx.y] ? sg.cols >> 2 : sg.cols;      // lanes per row
-  const int64_t n = (int64_t)sg.rows * lpr;
-  for (int64_t i = tid; i < n; i += nthr) {
-    const int64_t r = i / lpr;
-    const int c = (int)(i - r * lpr);
-    const int64_t e = ss.idx[r % ss.B];
-    if ((uint64_t)e >= (uint64_t)sg.dst_rows) continue;
-    if (ss.vec[blockIdx.y])
-      st4(sg.dst + (e * sg.cols + 4 * c), ld4(sg.src + (r * sg.cols + 4 * c)));
-    else
-      sg.dst[e * sg.cols + c] = sg.src[r * sg.cols + c];
-  }
+  scatter_rows_segment(ss, blockIdx.y, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 // out[b, t, :] = packed[start[b] + t, :] for t < len[b], 0 beyond: the collater's right-zero-padding
@@ -605,22 +580,9 @@ extern "C" int sdumc_copy2d_multi(const sdumc_copy_seg* segs, int32_t n, void* s
 
 extern "C" int sdumc_scatter_rows_multi(const sdumc_scatter_seg* segs, int32_t n, const int64_t* idx, int32_t B, uint8_t* mark,
                                         void* stream) {
-  if (!segs || n < 1 || n > SDUMC_SCATTER_MAX_SEGS || !idx || B < 1) return SDUMC_EINVAL;
   ScatterSegs ss;
-  memset(&ss, 0, sizeof(ss));
-  int64_t mx = B;      // lanes of the widest segment (the mark pass needs B)
-  for (int i = 0; i < n; ++i) {
-    const sdumc_scatter_seg& sg = segs[i];
-    if (!sg.src || !sg.dst || sg.rows < 1 || sg.cols < 1 || sg.rows % B != 0) return SDUMC_EINVAL;
-    if (sg.dst_rows < 1 || sg.dst_rows > ((int64_t)1 << 61) / sg.cols) return SDUMC_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(sg.src) | reinterpret_cast<uintptr_t>(sg.dst)) & 3) return SDUMC_EINVAL;
-    ss.s[i] = sg;
-    ss.vec[i] = (sg.cols % 4 == 0 && !((reinterpret_cast<uintptr_t>(sg.src) | reinterpret_cast<uintptr_t>(sg.dst)) & 15)) ? 1 : 0;
-    mx = std::max<int64_t>(mx, (int64_t)sg.rows * (ss.vec[i] ? sg.cols / 4 : sg.cols));
-  }
-  ss.idx = idx;
-  ss.mark = mark;
-  ss.B = B;
+  int64_t mx = 0;      // lanes of the widest segment (the mark pass needs B)
+  if (scatter_segs_fill(&ss, segs, n, idx, B, mark, &mx) != SDUMC_OK) return SDUMC_EINVAL;
   hipLaunchKernelGGL(scatter_rows_multi_kernel, dim3(std::min<unsigned>(nblk(mx), 256u), n), dim3(256), 0, as_stream(stream), ss);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;

@@ -5,6 +5,7 @@ happens in libsdumc_hip.so; there is no CPU or torch fallback.
 """
 import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -855,11 +856,18 @@ class FusedTrainer:
         """Every batch of `batches` (index vectors into `store`, or a data.EpochPlan), in order: main :89-150's loop.  The first batch
         is assembled in front of the first step; from then on step i assembles batch i + 1 in the other input set while it runs.
         on_step(i, losses) is called after step i has been ENQUEUED (losses = the device vector the step will write: clone it to keep
-        it).  Returns the number of steps."""
-        if self.arena is None or len(self.arena.sets) < 2:
-            raise _lib.SdumcError("run_epoch needs FusedTrainer(capacity=..., sets=2)")
+        it).  Returns the number of steps.  (train_epoch is the same loop with the epoch's record kept.)"""
+        self._need_sets("run_epoch")
         from .data import EpochPlan
-        plan = batches if isinstance(batches, EpochPlan) else store.plan_epoch(batches)
+        return self._epoch(store, batches if isinstance(batches, EpochPlan) else store.plan_epoch(batches), key_padding, on_step)
+
+    def _need_sets(self, what):
+        if self.arena is None or len(self.arena.sets) < 2:
+            raise _lib.SdumcError(f"{what} needs FusedTrainer(capacity=..., sets=2)")
+
+    def _epoch(self, store, plan, key_padding, on_step, record=None):
+        """The loop of run_epoch and train_epoch over a data.EpochPlan.  record(i, ts) is called right after step i has been enqueued
+        (ts = the step that ran it), before on_step."""
         n = len(plan)
         # the arena must hold the epoch's largest batch BEFORE the first descriptor is built (growing it invalidates every cached step);
         # the per-shape step objects themselves are made one step ahead of the GPU, inside the loop: the host runs ahead of the device
@@ -876,10 +884,65 @@ class FusedTrainer:
             nxt = self._get(*plan.shapes[i + 1]) if i + 1 < n else None
             pf = self._gather_desc(store, plan.idx_ptr(i + 1), nxt, (i + 1) & 1, key_padding, planes, inplace) if nxt is not None else None
             losses = self._launch(ts, next_step=nxt, prefetch=pf)
+            if record is not None:
+                record(i, ts)
             if on_step is not None:
                 on_step(i, losses)
         self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers)
         return n
+
+    def train_epoch(self, store, batches, key_padding=False, on_step=None, embeddings=False, grad_norm=False, out=None):
+        """run_epoch with the epoch's record kept -> record.TrainRecord: what the reference's training pass returns (main :156-178: the
+        train-mode predictions of both streams in store order and their MSE; embeddings=True: the four embeddings too) and a log row
+        per step (the loss vector, B, the learning rate; grad_norm=True: the L2 norm of the step's raw gradient bucket -- without
+        Adam's coupled L2 term -- and its number of non-finite elements).  The same launches as run_epoch plus one per step, two with
+        grad_norm (sdumc_epoch_record), which only read what the step left: parameters, moments and dropout counter are those of run_epoch.
+        The epoch must not visit an utterance twice (checked on the host before anything is enqueued; `out` is untouched if it
+        does).  out= reuses a record (TrainRecord.fits: this store, at least this many steps, the same options)."""
+        self._need_sets("train_epoch")
+        from .evaluate import checked_plan
+        from .record import TrainRecord
+        dev, n_store = self.params.device, len(store)
+        plan, batches = checked_plan(batches, n_store)
+        n = len(plan if plan is not None else batches)
+        n_grads = ParamLayout.get(*self.dims[:3]).live if grad_norm else 0
+        if out is not None and not (isinstance(out, TrainRecord) and out.fits(n_store, n, dev, embeddings, n_grads)):
+            raise _lib.SdumcError("train_epoch: out= is not a record of this store's size and device, these many steps and these options")
+        if plan is None:
+            plan = store.plan_epoch(batches)
+        rec = (out if out is not None else TrainRecord.empty(n_store, n, dev, embeddings, n_grads)).reset()
+        descs, st = {}, _lib.current_stream()
+
+        def record(i, ts):
+            d = descs.get(ts.B)
+            if d is None or d[1] is not self.arena:
+                d = descs[ts.B] = (self._record_desc(rec, ts, embeddings, grad_norm), self.arena)
+            r = d[0]
+            r.idx, r.log_row = plan.idx_ptr(i), rec.log.data_ptr() + 4 * _lib.LOG_COLS * i
+            check(lib.sdumc_epoch_record(C.byref(r), st), "sdumc_epoch_record")
+
+        rec.steps = self._epoch(store, plan, key_padding, on_step, record)
+        return rec
+
+    def _record_desc(self, rec, ts, embeddings, grad_norm):
+        """sdumc_epoch_record's descriptor for steps of ts.B samples (idx and log_row are set per step): rows [0, B) of the arena's
+        outputs to stream 0's tensors of the record, rows [B, 2 B) to stream 1's"""
+        from .evaluate import EMBEDDINGS
+        B, n = ts.B, rec.preds.shape[1]
+        pairs = [(self.arena.outs[0], rec.preds, 1)]
+        if embeddings:
+            pairs += [(self.arena.outs[j + 1], rec.embeddings[name], math.prod(shape)) for j, (name, shape, _) in enumerate(EMBEDDINGS)]
+        r = _lib.EpochRec()
+        for j, (src, dst, w) in enumerate(pairs):
+            for s in range(2):
+                sg = r.seg[2 * j + s]
+                sg.src, sg.dst = src.data_ptr() + 4 * s * B * w, dst.data_ptr() + 4 * s * n * w
+                sg.rows, sg.cols, sg.dst_rows = B, w, n
+        r.nseg, r.B, r.mark = 2 * len(pairs), B, ptr(rec.seen)
+        r.losses, r.hyper = ptr(self.state.losses), ptr(self.state.hyper)
+        if grad_norm:
+            r.grads, r.n_grads, r.scratch = ptr(ts.grads), ts.grads.numel(), ptr(rec.scratch)
+        return r
 
     def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
         """One evaluation pass (main :151-166: both streams, eval mode) over `batches` of `store` with the trainer's parameters, in its

@@ -67,6 +67,21 @@ def check_epoch_indices(batches, n):
     return flat
 
 
+def checked_plan(batches, n):
+    """check_epoch_indices over `batches` -- index vectors, or a data.EpochPlan (its host copy of the indices when it kept one) -- before
+    anything is uploaded or enqueued -> (the plan or None, the batches as int64 tensors or None)."""
+    from .data import EpochPlan
+    if isinstance(batches, EpochPlan):
+        host = getattr(batches, "idx_h", None)
+        host = batches.idx_d.cpu() if host is None else host
+        bounds = list(batches.offsets) + [int(host.numel())]
+        check_epoch_indices([host[a:b] for a, b in zip(bounds, bounds[1:])], n)
+        return batches, None
+    batches = [torch.as_tensor(b, dtype=torch.int64).reshape(-1) for b in batches]
+    check_epoch_indices(batches, n)
+    return None, batches
+
+
 class EvalResult:
     """Results of one evaluation epoch in STORE order (row i = utterance i of the store): preds [2, N] (row 0 the full stream, row 1
     the text-missing one), seen [N] (uint8 / bool: visited this epoch), embeddings None or {'fused' [2, N, 128], 'rnc' [2, N, 64],
@@ -285,19 +300,9 @@ class Evaluator:
         return e
 
     def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
-        from .data import EpochPlan
         n_store = len(store)
         # ---- host-side checks: nothing is enqueued (and nothing of `out` is touched) before all of them have passed ----
-        if isinstance(batches, EpochPlan):
-            plan = batches
-            host = getattr(plan, "idx_h", None)
-            host = plan.idx_d.cpu() if host is None else host
-            bounds = list(plan.offsets) + [int(host.numel())]
-            check_epoch_indices([host[a:b] for a, b in zip(bounds, bounds[1:])], n_store)
-        else:
-            batches = [torch.as_tensor(b, dtype=torch.int64).reshape(-1) for b in batches]
-            check_epoch_indices(batches, n_store)
-            plan = None
+        plan, batches = checked_plan(batches, n_store)
         if store.packed['audio'].device != self.params.device:
             raise _lib.SdumcError("eval_epoch: the store and the parameters live on different devices")
         inplace = self._in_place(store)
