@@ -38,6 +38,12 @@ constexpr int PARTC = NWV * 7 * OC;   // partial-sum area of the split layers (a
 constexpr int SPIN_CAP = 400000;
 static_assert(PARTC >= NWV * 2 * H, "tail layers");
 
+// the stages' LDS layouts here: the slice-wide partial-sum area, the three modalities side by side
+template <int R> using FwdA = FwdALds<R, PARTC>;
+template <int R> using FwdB = FwdBLds<R, PARTC, 3, 0>;
+template <int R> using BwdB = BwdBLds<R, PARTC, 3>;
+template <int R> using BwdA = BwdALds<R, PARTC, 3>;
+
 struct Cl {
   uint32_t* arrive;
   uint32_t* depart;
@@ -102,21 +108,6 @@ __device__ __forceinline__ void cl_exit(Cl& cl) {
       __hip_atomic_store(cl.depart, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-}
-
-// y = drop(relu(v + bias)): `col` is the layer's global output column, bias_lds the layer's staged bias row
-__device__ __forceinline__ f32x4 fwd_val(f32x4 v, const float* bias_lds, int col, bool relu, const DropRT& drop, uint32_t vrow) {
-  v += ld4(bias_lds + col);
-  if (relu) {
-    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-  }
-  if (drop.enabled) v *= drop_mask4(drop, vrow, (uint32_t)(col >> 2));
-  return v;
-}
-__device__ __forceinline__ f32x4 mask_val(f32x4 v, f32x4 y, float sc) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = y[j] > 0.f ? v[j] * sc : 0.f;
-  return v;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -435,25 +426,13 @@ typedef float WT;   // weights stream as fp32
 template <int R>
 __device__ __forceinline__ void chain_fwd_a_cl_body(const sdumc_chain_args a, const int ncl) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* part = sm;                              // PARTC
-  float* s_hpre = part + PARTC;                  // [3][R][256]
-  float* s_u1 = s_hpre + 3 * R * D;              // [3][R][256]
-  float* s_u = s_u1 + 3 * R * D;                 // [R][768]
-  float* s_att1 = s_u + 3 * R * D;               // [R][256]
-  float* s_att2 = s_att1 + R * D;                // [R][256]
-  float* s_alpha = s_att2 + R * D;               // [R][4]
-  float* s_qin = s_alpha + R * 4;                // [7][R][256]
-  float* s_q = s_qin + 7 * R * D;                // [R][7][256]
-  float* s_bias = s_q + 7 * R * D;               // [18][256]
+  using L = FwdA<R>;
+  float *part = sm + L::part, *s_hpre = sm + L::hpre, *s_u1 = sm + L::u1, *s_u = sm + L::u, *s_att1 = sm + L::att1, *s_att2 = sm + L::att2,
+        *s_qin = sm + L::qin, *s_q = sm + L::q, *s_bias = sm + L::bias;
   CL_PROLOGUE();
   TR(0);
   const int64_t VD = (int64_t)V * D;
-  {
-    const float* bsrc[18] = {a.umlp0_b[0], a.umlp0_b[1], a.umlp0_b[2], a.umlp3_b[0], a.umlp3_b[1], a.umlp3_b[2], a.att0_b, a.att3_b,
-                             a.query_b[0], a.query_b[1], a.query_b[2], a.query_b[3], a.query_b[4], a.query_b[5], a.query_b[6],
-                             a.caq_b[0], a.caq_b[1], a.caq_b[2]};
-    for (int u = tid; u < 18 * (D / 4); u += NTHR) st4(s_bias + 4 * u, ld4(bsrc[u / (D / 4)] + 4 * (u % (D / 4))));
-  }
+  fwd_a_stage_bias(a, s_bias);
   const DropRT dbase = drop_resolve(a.drop);
   CRing ring;
   if (a.cl_mode & 2) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -534,29 +513,9 @@ __device__ __forceinline__ void chain_fwd_a_cl_body(const sdumc_chain_args a, co
   TR(8);
   reload_rows<R>(s_att2, D, a.att2, D, D, v0, V);
   __syncthreads();
-  for (int p = wave; p < 3 * R; p += NWV) {          // alpha[r][j] = att2[r] . W[j] + b[j]   (every member, redundantly)
-    const int r = p / 3, j = p - 3 * r;
-    const float s = wave_sum(dot4(ld4(s_att2 + r * D + 4 * lane), ld4(a.fc_att_w + j * D + 4 * lane)));
-    if (lane == 0) {
-      const float al = s + a.fc_att_b[j];
-      s_alpha[r * 4 + j] = al;
-      if (v0 + r < V && member == 0) a.alpha[(int64_t)(v0 + r) * 3 + j] = al;
-    }
-  }
-  __syncthreads();
-  // fusion algebra (model :305-320): fused, a+t, t+v, a+v, a, t, v   (LDS: every member; HBM: the owner of the column slice)
-  for (int u = tid; u < R * (D / 4); u += NTHR) {
-    const int r = u / (D / 4), c = 4 * (u - r * (D / 4));
-    const f32x4 ua = ld4(s_u + r * 3 * D + c), ut = ld4(s_u + r * 3 * D + D + c), uv = ld4(s_u + r * 3 * D + 2 * D + c);
-    const float aa = s_alpha[r * 4], at = s_alpha[r * 4 + 1], av = s_alpha[r * 4 + 2];
-    f32x4 o[7] = {ua * aa + ut * at + uv * av, ua * aa + ut * at, ut * at + uv * av, ua * aa + uv * av, ua, ut, uv};
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      st4(s_qin + (i * R + r) * D + c, o[i]);
-      if (v0 + r < V && c / OC == member) st4(a.qin + i * VD + (int64_t)(v0 + r) * D + c, o[i]);
-    }
-  }
-  __syncthreads();
+  // alpha and the fusion algebra: every member, redundantly (HBM: alpha by member 0, qin by the owner of the column slice)
+  fwd_a_alpha<L>(a, sm, v0, V, member == 0);
+  fwd_a_fusion<L>(a, sm, v0, V, [member](int c) { return c / OC == member; });
   // the 7 query MLPs -> multi_query [V, 7, 256] (model :324-332); text_hidden = query 5 (model :329, :370)
 #pragma unroll 1
   for (int i = 0; i < 7; ++i) {
@@ -592,8 +551,6 @@ __device__ __forceinline__ void chain_fwd_a_cl_body(const sdumc_chain_args a, co
   }
   TR(31);
 }
-// two entry points per stage: with packed FP32 VALU instructions (fp32 storage), and without (SDUMC_NO_PACKED_FP32, chain_common.h:
-// whenever bf16 MFMA kernels run beside this one, i.e. sdumc_net_dims.bf16 != 0)
 template <int R>
 __global__ __launch_bounds__(NTHR) void chain_fwd_a_cl_kernel(const sdumc_chain_args a, const int ncl) { chain_fwd_a_cl_body<R>(a, ncl); }
 
@@ -604,37 +561,17 @@ __global__ __launch_bounds__(NTHR) void chain_fwd_a_cl_kernel(const sdumc_chain_
 template <int R>
 __device__ __forceinline__ void chain_fwd_b_cl_body(const sdumc_chain_args a, const int ncl) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* part = sm;
-  float* s_x = part + PARTC;                     // [3][7R][256]  ca_out, then c1
-  float* s_c = s_x + 3 * NQ * R * D;             // [3][7R][128]
-  float* s_h = s_c + 3 * NQ * R * H;             // [R][896]
-  float* s_e1 = s_h + R * NQ * H;                // [R][256]
-  float* s_e2 = s_e1 + R * D;                    // [R][128]
-  float* s_z = s_e2 + R * H;                     // [R][128]
-  float* s_r1 = s_z + R * H;                     // [R][64]
-  float* s_small = s_r1 + R * RD;                // alpha [R][4], beta [R][8]
-  float* s_bias = s_small + 12 * R;              // cmlp0 [3][256], cmlp3 [3][128], catt0 [256], catt3 [128], rnc0 [64], rnc2 [64]
+  using L = FwdB<R>;      // x: ca_out of the three modalities, then c1
+  float *part = sm + L::part, *s_x = sm + L::x, *s_c = sm + L::c, *s_h = sm + L::h, *s_e1 = sm + L::e1, *s_e2 = sm + L::e2, *s_bias = sm + L::bias;
   CL_PROLOGUE();
   TR(0);
   const int64_t VQ = (int64_t)V * NQ;
   const int hoff = member * HC;
-  {
-    for (int u = tid; u < 3 * (D / 4); u += NTHR) st4(s_bias + 4 * u, ld4(a.cmlp0_b[u / (D / 4)] + 4 * (u % (D / 4))));
-    for (int u = tid; u < 3 * (H / 4); u += NTHR) st4(s_bias + 3 * D + 4 * u, ld4(a.cmlp3_b[u / (H / 4)] + 4 * (u % (H / 4))));
-    for (int u = tid; u < D / 4; u += NTHR) st4(s_bias + 3 * D + 3 * H + 4 * u, ld4(a.catt0_b + 4 * u));
-    for (int u = tid; u < H / 4; u += NTHR) st4(s_bias + 4 * D + 3 * H + 4 * u, ld4(a.catt3_b + 4 * u));
-    for (int u = tid; u < RD / 4; u += NTHR) {
-      st4(s_bias + 4 * D + 4 * H + 4 * u, ld4(a.rnc0_b + 4 * u));
-      st4(s_bias + 4 * D + 4 * H + RD + 4 * u, ld4(a.rnc2_b + 4 * u));
-    }
-  }
+  fwd_b_stage_bias(a, s_bias);
   const DropRT dbase = drop_resolve(a.drop);
   CRing ring;
   PF14(D, OC, a.cmlp0_w[0] + coff, D);
-  for (int u = tid; u < R * 3; u += NTHR) {
-    const int r = u / 3, j = u - 3 * r;
-    s_small[r * 4 + j] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
-  }
+  fwd_b_load_alpha<L>(a, sm, v0, V);
   // the Cross_Attention sites' combine (one grouped launch between the pooling and this stage) rides here
   if (a.ca.part[0]) fold_combine<R, NQ>(a.ca, a.ca_out, s_x, s_c, v0, V, member, dbase);      // (s_c: first written by cross_*_mlp.3)
   else for (int m = 0; m < 3; ++m) load_rows<NQ * R>(s_x + m * NQ * R * D, a.ca_out + (int64_t)m * VQ * D, D, D, v0 * NQ, V * NQ);
@@ -682,15 +619,7 @@ __device__ __forceinline__ void chain_fwd_b_cl_body(const sdumc_chain_args a, co
   TR(4);
   for (int m = 0; m < 3; ++m) reload_rows<NQ * R>(s_c + m * NQ * R * H, H, a.c + (int64_t)m * VQ * H, H, H, v0 * NQ, V * NQ);
   __syncthreads();
-  // modality-weighted sum (model :346-349): h[r][i][:] = sum_m alpha[r][m] c_m[r][i][:]
-  for (int u = tid; u < R * NQ * (H / 4); u += NTHR) {
-    const int ri = u / (H / 4), c = 4 * (u - ri * (H / 4)), r = ri / NQ;
-    const f32x4 hv = ld4(s_c + ri * H + c) * s_small[r * 4] + ld4(s_c + (NQ * R + ri) * H + c) * s_small[r * 4 + 1] +
-                     ld4(s_c + (2 * NQ * R + ri) * H + c) * s_small[r * 4 + 2];
-    st4(s_h + ri * H + c, hv);
-    if (v0 + r < V && member == 0) st4(a.h + ((int64_t)v0 * NQ + ri) * H + c, hv);
-  }
-  __syncthreads();
+  fwd_b_hsum<L>(a, sm, v0, V, member == 0);
   // cross_attention_mlp + cross_fc_att (model :352-354)
   {
     const DropRT dr = mkdrop_rt(dbase, 33, 1, D);
@@ -723,61 +652,9 @@ __device__ __forceinline__ void chain_fwd_b_cl_body(const sdumc_chain_args a, co
   TR(30);
   reload_rows<R>(s_e2, H, a.e2, H, H, v0, V);
   __syncthreads();
-  for (int p = wave; p < NQ * R; p += NWV) {          // beta[r][i] = e2[r] . W[i] + b[i]
-    const int r = p / NQ, i = p - NQ * r;
-    float s = lane < H / 4 ? dot4(ld4(s_e2 + r * H + 4 * lane), ld4(a.cfa_w + i * H + 4 * lane)) : 0.f;
-    s = wave_sum(s);
-    if (lane == 0) {
-      const float bt = s + a.cfa_b[i];
-      s_small[4 * R + r * 8 + i] = bt;
-      if (v0 + r < V) a.beta[(int64_t)(v0 + r) * NQ + i] = bt;
-    }
-  }
-  __syncthreads();
-  // cross_fused_feat (model :356-358), fc_out_v (model :364)
-  for (int u = tid; u < R * (H / 4); u += NTHR) {
-    const int r = u / (H / 4), c = 4 * (u - r * (H / 4));
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) acc += ld4(s_h + (r * NQ + i) * H + c) * s_small[4 * R + r * 8 + i];
-    st4(s_z + r * H + c, acc);
-    if (v0 + r < V) {
-      st4(a.z + (int64_t)(v0 + r) * H + c, acc);
-      if (a.o_fused) st4(a.o_fused + (int64_t)(v0 + r) * H + c, acc);
-    }
-  }
-  __syncthreads();
-  for (int r = wave; r < R; r += NWV) {
-    float s = lane < H / 4 ? dot4(ld4(s_z + r * H + 4 * lane), ld4(a.fcv_w + 4 * lane)) : 0.f;
-    s = wave_sum(s);
-    if (lane == 0 && v0 + r < V) {
-      const float y = s + a.fcv_b[0];
-      a.vals[v0 + r] = y;
-      if (a.o_vals) a.o_vals[v0 + r] = y;
-    }
-  }
-  // orgin_linear_change (model :246-250, :368): Linear -> ReLU -> Linear
-  {
-    FwdEpi e{s_bias + 4 * D + 4 * H, s_r1, RD, a.r1 + (int64_t)v0 * RD, RD, true, DropRT{}, 0u, 0u};
-    auto epi = [&](int r, int col, f32x4 v) { if (v0 + r < V) e(r, col, v); else st4(s_r1 + r * RD + col, f32x4{0.f, 0.f, 0.f, 0.f}); };
-    rows_x_matrix<R, H, RD>(s_z, H, a.rnc0_w, RD, part, epi);
-  }
-  {
-    FwdEpi e{s_bias + 4 * D + 4 * H + RD, nullptr, 0, a.r + (int64_t)v0 * RD, RD, false, DropRT{}, 0u, 0u};
-    float* ro = a.o_rnc ? a.o_rnc + (int64_t)v0 * RD : nullptr;
-    const float* b2 = s_bias + 4 * D + 4 * H + RD;
-    auto epi = [&](int r, int col, f32x4 v) {
-      if (v0 + r < V) {
-        e(r, col, v);
-        if (ro) st4(ro + (int64_t)r * RD + col, v + ld4(b2 + col));
-      }
-    };
-    rows_x_matrix<R, RD, RD>(s_r1, RD, a.rnc2_w, RD, part, epi);
-  }
+  fwd_b_tail<L>(a, sm, v0, V);
   TR(31);
 }
-// two entry points per stage: with packed FP32 VALU instructions (fp32 storage), and without (SDUMC_NO_PACKED_FP32, chain_common.h:
-// whenever bf16 MFMA kernels run beside this one, i.e. sdumc_net_dims.bf16 != 0)
 template <int R>
 __global__ __launch_bounds__(NTHR) void chain_fwd_b_cl_kernel(const sdumc_chain_args a, const int ncl) { chain_fwd_b_cl_body<R>(a, ncl); }
 
@@ -788,88 +665,22 @@ __global__ __launch_bounds__(NTHR) void chain_fwd_b_cl_kernel(const sdumc_chain_
 template <int R>
 __device__ __forceinline__ void chain_bwd_b_cl_body(const sdumc_chain_args a, const int ncl) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* part = sm;
-  float* s_g = part + PARTC;                     // [R][64]   d_rnc
-  float* s_r1 = s_g + R * RD;                    // [R][64]   saved r1, then d_r1
-  float* s_dz = s_r1 + R * RD;                   // [R][128]  d_z, then d_e2
-  float* s_h = s_dz + R * H;                     // [R][896]  saved h
-  float* s_dh = s_h + R * NQ * H;                // [R][896]
-  float* s_e2 = s_dh + R * NQ * H;               // [R][128]  saved e2
-  float* s_e1 = s_e2 + R * H;                    // [R][256]  saved e1, then d_e1
-  float* s_dc = s_e1 + R * D;                    // [3][7R][128] d_c
-  float* s_c1 = s_dc + 3 * NQ * R * H;           // [3][7R][256] saved c1, then d_c1
-  float* s_small = s_c1 + 3 * NQ * R * D;        // beta [R][8], d_beta [R][8], alpha [R][4], d_vals [R]
+  using L = BwdB<R>;      // dc, c1: the three modalities side by side
+  float *part = sm + L::part, *s_dz = sm + L::dz, *s_dh = sm + L::dh, *s_e1 = sm + L::e1, *s_dc = sm + L::dc, *s_c1 = sm + L::c1;
   CL_PROLOGUE();
   TR(0);
   const int64_t VQ = (int64_t)V * NQ;
   const float sc = a.relu_scale;
   const bool wr = member == 0;
-  float* s_beta = s_small;
-  float* s_dbeta = s_small + 8 * R;
-  float* s_alpha = s_small + 16 * R;
-  float* s_dvals = s_small + 20 * R;
 
   CRing ring;
   PF(H, OC, a.catt3_w + coff, D);
-  if (a.g_rnc) load_rows<R>(s_g, a.g_rnc, RD, RD, v0, V);
-  else for (int u = tid; u < R * RD; u += NTHR) s_g[u] = 0.f;
-  load_rows<R>(s_r1, a.r1, RD, RD, v0, V);
-  load_rows<R>(s_h, a.h, NQ * H, NQ * H, v0, V);
-  load_rows<R>(s_e2, a.e2, H, H, v0, V);
-  load_rows<R>(s_e1, a.e1, D, D, v0, V);
+  bwd_b_load_head<L>(a, sm, v0, V);
   for (int m = 0; m < 3; ++m) load_rows<NQ * R>(s_c1 + m * NQ * R * D, a.c1 + (int64_t)m * VQ * D, D, D, v0 * NQ, V * NQ);
-  for (int u = tid; u < R * 8; u += NTHR) {
-    const int r = u >> 3, i = u & 7;
-    s_beta[u] = (i < NQ && v0 + r < V) ? a.beta[(int64_t)(v0 + r) * NQ + i] : 0.f;
-    if (i < 3) s_alpha[r * 4 + i] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + i] : 0.f;
-    if (i == 0) s_dvals[r] = (a.g_vals && v0 + r < V) ? a.g_vals[v0 + r] : 0.f;
-  }
   __syncthreads();
-  // 12'. orgin_linear_change backward: d_r1 = (d_rnc W2) [r1 > 0] ; d_z = d_r1 W0 + d_vals w_v + d_fused
-  {
-    BwdEpi e{nullptr, 0, s_r1, RD, 1.0f, s_r1, RD, wr ? a.d_r1 + (int64_t)v0 * RD : nullptr, RD};
-    auto epi = [&](int r, int col, f32x4 v) { if (v0 + r < V) e(r, col, v); else st4(s_r1 + r * RD + col, f32x4{0.f, 0.f, 0.f, 0.f}); };
-    rows_x_matrix<R, RD, RD>(s_g, RD, a.rnc2_w, RD, part, epi);
-  }
-  {
-    const float* gf = a.g_fused;
-    const float* wv = a.fcv_w;
-    float* dzg = a.d_z;
-    auto epi = [&](int r, int col, f32x4 v) {
-      v += ld4(wv + col) * s_dvals[r];
-      if (gf && v0 + r < V) v += ld4(gf + (int64_t)(v0 + r) * H + col);
-      if (v0 + r >= V) v = f32x4{0.f, 0.f, 0.f, 0.f};
-      st4(s_dz + r * H + col, v);
-      if (v0 + r < V && wr) st4(dzg + (int64_t)(v0 + r) * H + col, v);
-    };
-    rows_x_matrix<R, RD, H>(s_r1, RD, a.rnc0_w, H, part, epi);
-  }
-  // zpool backward: d_h[i] = beta_i d_z ; d_beta_i = <d_z, h_i>
-  for (int u = tid; u < R * NQ * (H / 4); u += NTHR) {
-    const int ri = u / (H / 4), c = 4 * (u - ri * (H / 4)), r = ri / NQ, i = ri - r * NQ;
-    st4(s_dh + ri * H + c, ld4(s_dz + r * H + c) * s_beta[r * 8 + i]);
-  }
-  for (int p = wave; p < NQ * R; p += NWV) {
-    const int r = p / NQ, i = p - NQ * r;
-    float s = lane < H / 4 ? dot4(ld4(s_dz + r * H + 4 * lane), ld4(s_h + (r * NQ + i) * H + 4 * lane)) : 0.f;
-    s = wave_sum(s);
-    if (lane == 0) {
-      s_dbeta[r * 8 + i] = s;
-      if (v0 + r < V && wr) a.d_beta[(int64_t)(v0 + r) * NQ + i] = s;
-    }
-  }
-  __syncthreads();
-  // 11'. cross_fc_att: d_e2 = (d_beta W_cfa) [e2 > 0] s
-  for (int u = tid; u < R * (H / 4); u += NTHR) {
-    const int r = u / (H / 4), c = 4 * (u - r * (H / 4));
-    f32x4 g = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) g += ld4(a.cfa_w + i * H + c) * s_dbeta[r * 8 + i];
-    g = mask_val(g, ld4(s_e2 + r * H + c), sc);
-    if (v0 + r < V && wr) st4(a.d_e2 + (int64_t)(v0 + r) * H + c, g);
-    st4(s_dz + r * H + c, g);        // d_z is no longer needed in LDS: the slot now holds d_e2
-  }
-  __syncthreads();
+  bwd_b_rnc<L>(a, sm, v0, V, wr);
+  bwd_b_zpool<L>(a, sm, v0, V, wr);
+  bwd_b_de2<L>(a, sm, v0, V, sc, wr);
   // cross_attention_mlp.3: d_e1 = (d_e2 W) [e1 > 0] s
   {
     float* dst = a.d_e1 + (int64_t)v0 * D;
@@ -906,26 +717,7 @@ __device__ __forceinline__ void chain_bwd_b_cl_body(const sdumc_chain_args a, co
   // 10'. modality-weighted sum backward (every member; HBM by member 0)
 #pragma unroll 1
   for (int m = 0; m < 3; ++m) {
-    float* s_dcm = s_dc + m * NQ * R * H;
-    for (int u = tid; u < R * NQ * (H / 4); u += NTHR) {
-      const int ri = u / (H / 4), c = 4 * (u - ri * (H / 4)), r = ri / NQ;
-      const bool live = v0 + r < V;
-      f32x4 cm = {0.f, 0.f, 0.f, 0.f}, g = ld4(s_dh + ri * H + c);
-      if (live) cm = ld4(a.c + ((int64_t)m * VQ + (int64_t)v0 * NQ + ri) * H + c);
-      part[u] = dot4(g, cm);
-      g = g * s_alpha[r * 4 + m];
-      if (m == 1 && a.g_cross_text && live) g += ld4(a.g_cross_text + ((int64_t)v0 * NQ + ri) * H + c);
-      g = mask_val(g, cm, sc);
-      st4(s_dcm + ri * H + c, g);
-      if (live && wr) st4(a.d_c + ((int64_t)m * VQ + (int64_t)v0 * NQ + ri) * H + c, g);
-    }
-    __syncthreads();
-    for (int r = wave; r < R; r += NWV) {
-      float s = 0.f;
-      for (int k = lane; k < NQ * (H / 4); k += 64) s += part[r * NQ * (H / 4) + k];
-      s = wave_sum(s);
-      if (lane == 0 && v0 + r < V && wr) a.d_alpha[(int64_t)(v0 + r) * 3 + m] = s;
-    }
+    bwd_b_dc<L>(a, sm, s_dc + m * NQ * R * H, m, v0, V, sc, wr);
     __syncthreads();
   }
   // 9'. cross_*_mlp.3: d_c1 = (d_c W3) [c1 > 0] s
@@ -961,8 +753,6 @@ __device__ __forceinline__ void chain_bwd_b_cl_body(const sdumc_chain_args a, co
   }
   TR(31);
 }
-// two entry points per stage: with packed FP32 VALU instructions (fp32 storage), and without (SDUMC_NO_PACKED_FP32, chain_common.h:
-// whenever bf16 MFMA kernels run beside this one, i.e. sdumc_net_dims.bf16 != 0)
 template <int R>
 __global__ __launch_bounds__(NTHR) void chain_bwd_b_cl_kernel(const sdumc_chain_args a, const int ncl) { chain_bwd_b_cl_body<R>(a, ncl); }
 
@@ -972,23 +762,14 @@ __global__ __launch_bounds__(NTHR) void chain_bwd_b_cl_kernel(const sdumc_chain_
 template <int R>
 __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, const int ncl) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* part = sm;
-  float* s_x = part + PARTC;                     // [3][7R][256]  d_qp
-  float* s_dq = s_x + 3 * NQ * R * D;            // [R][7][256]
-  float* s_dqin = s_dq + NQ * R * D;             // [7][R][256]
-  float* s_u = s_dqin + NQ * R * D;              // [R][768]  saved u
-  float* s_du = s_u + 3 * R * D;                 // [R][768]
-  float* s_a2 = s_du + 3 * R * D;                // [R][256]  saved att2, then d_att2
-  float* s_a1 = s_a2 + R * D;                    // [R][256]  saved att1, then d_att1
-  float* s_u1 = s_a1 + R * D;                    // [3][R][256] saved u1, then d_u1
-  float* s_small = s_u1 + 3 * R * D;             // alpha [R][4], d_alpha [R][4]
+  using L = BwdA<R>;      // x: d_qp of the three modalities
+  float *part = sm + L::part, *s_x = sm + L::x, *s_dq = sm + L::dq, *s_dqin = sm + L::dqin, *s_u = sm + L::u, *s_du = sm + L::du, *s_a2 = sm + L::a2,
+        *s_a1 = sm + L::a1, *s_u1 = sm + L::u1;
   CL_PROLOGUE();
   TR(0);
   const int64_t VD = (int64_t)V * D, VQ = (int64_t)V * NQ;
   const float sc = a.relu_scale;
   const bool wr = member == 0;
-  float* s_alpha = s_small;
-  float* s_dalpha = s_small + 4 * R;
 
   CRing ring;
   PF14(D, OC, a.caq_w[0] + coff, D);
@@ -1021,11 +802,7 @@ __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, co
   } else {
     for (int m = 0; m < 3; ++m) load_rows<NQ * R>(s_x + m * NQ * R * D, a.d_qp + (int64_t)m * VQ * D, D, D, v0 * NQ, V * NQ);
   }
-  for (int u = tid; u < R * 3; u += NTHR) {
-    const int r = u / 3, j = u - 3 * r;
-    s_alpha[r * 4 + j] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
-    s_dalpha[r * 4 + j] = v0 + r < V ? a.d_alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
-  }
+  bwd_a_load_alpha<L>(a, sm, v0, V);
   __syncthreads();
   // 7'. query_proj: d_q = sum_m d_qp_m W_q[m]  (this member's columns, accumulated in LDS over the three modalities)
 #pragma unroll 1
@@ -1038,17 +815,10 @@ __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, co
     cxm_run<NQ * R, D, OC>(ring, s_x + m * NQ * R * D, D, a.caq_w[m] + coff, D, part, epi,
                                      [&] { if (m < 2) PF14(D, OC, a.caq_w[m + 1] + coff, D); else PF(D, OC, a.query_w[0] + coff, D); });
   }
-  // 6'. + the external gradient of text_hidden (= query 5), ReLU/dropout mask of q -> d_q (pre-activation)
-  for (int u = tid; u < R * NQ * (OC / 4); u += NTHR) {
-    const int ri = u / (OC / 4), c = coff + 4 * (u - ri * (OC / 4)), r = ri / NQ, i = ri - r * NQ;
-    f32x4 g = ld4(s_dq + ri * D + c);
-    const bool live = v0 + r < V;
-    if (i == 5 && a.g_text_hidden && live) g += ld4(a.g_text_hidden + (int64_t)(v0 + r) * D + c);
-    f32x4 y = {0.f, 0.f, 0.f, 0.f};
-    if (live) y = ld4(a.q + ((int64_t)(v0 + r) * NQ + i) * D + c);
-    g = mask_val(g, y, sc);
-    if (live) st4_dev(a.d_q + ((int64_t)(v0 + r) * NQ + i) * D + c, g);
-  }
+  // 6'. mask of q -> d_q (pre-activation): this member's columns, exchanged through HBM
+  bwd_a_mask_q<L, OC>(a, sm, v0, V, sc, coff, [](f32x4 g, float*, float* hbm, bool live) {
+    if (live) st4_dev(hbm, g);
+  });
   TR(1);
   cl_sync(cl, &s_bail);
   TR(2);
@@ -1069,41 +839,9 @@ __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, co
   TR(4);
   for (int i = 0; i < 7; ++i) reload_rows<R>(s_dqin + i * R * D, D, a.d_qin + i * VD, D, D, v0, V);
   __syncthreads();
-  // 5'. fusion algebra backward: d_u (fusion part), d_alpha += <g_m, u_m>   (every member; HBM by member 0)
-  for (int u = tid; u < R * (D / 4); u += NTHR) {
-    const int r = u / (D / 4), c = 4 * (u - r * (D / 4));
-    const f32x4 df = ld4(s_dqin + (0 * R + r) * D + c), dfat = ld4(s_dqin + (1 * R + r) * D + c),
-                dftv = ld4(s_dqin + (2 * R + r) * D + c), dfav = ld4(s_dqin + (3 * R + r) * D + c);
-    const f32x4 ga = df + dfat + dfav, gt = df + dfat + dftv, gv = df + dftv + dfav;
-    const float aa = s_alpha[r * 4], at = s_alpha[r * 4 + 1], av = s_alpha[r * 4 + 2];
-    st4(s_du + r * 3 * D + c, ga * aa + ld4(s_dqin + (4 * R + r) * D + c));
-    st4(s_du + r * 3 * D + D + c, gt * at + ld4(s_dqin + (5 * R + r) * D + c));
-    st4(s_du + r * 3 * D + 2 * D + c, gv * av + ld4(s_dqin + (6 * R + r) * D + c));
-    part[(r * 3 + 0) * (D / 4) + (c >> 2)] = dot4(ga, ld4(s_u + r * 3 * D + c));
-    part[(r * 3 + 1) * (D / 4) + (c >> 2)] = dot4(gt, ld4(s_u + r * 3 * D + D + c));
-    part[(r * 3 + 2) * (D / 4) + (c >> 2)] = dot4(gv, ld4(s_u + r * 3 * D + 2 * D + c));
-  }
-  __syncthreads();
-  for (int p = wave; p < 3 * R; p += NWV) {
-    const float s = wave_sum(part[p * (D / 4) + lane]);
-    if (lane == 0) {
-      const int r = p / 3, j = p - 3 * r;
-      const float da = s_dalpha[r * 4 + j] + s;
-      s_dalpha[r * 4 + j] = da;
-      if (v0 + r < V && wr) a.d_alpha[(int64_t)(v0 + r) * 3 + j] = da;      // final d_alpha: what the fc_att dW GEMM reads
-    }
-  }
-  __syncthreads();
-  // 4'. fc_att: d_att2 = (d_alpha W_fc) [att2 > 0] s
-  for (int u = tid; u < R * (D / 4); u += NTHR) {
-    const int r = u / (D / 4), c = 4 * (u - r * (D / 4));
-    f32x4 g = ld4(a.fc_att_w + c) * s_dalpha[r * 4] + ld4(a.fc_att_w + D + c) * s_dalpha[r * 4 + 1] +
-              ld4(a.fc_att_w + 2 * D + c) * s_dalpha[r * 4 + 2];
-    g = mask_val(g, ld4(s_a2 + r * D + c), sc);
-    st4(s_a2 + r * D + c, g);
-    if (v0 + r < V && wr) st4(a.d_att2 + (int64_t)(v0 + r) * D + c, g);
-  }
-  __syncthreads();
+  // 5'. fusion algebra backward and 4'. fc_att: d_att2 (every member; HBM by member 0)
+  bwd_a_fusion<L>(a, sm, v0, V, wr);
+  bwd_a_datt2<L>(a, sm, v0, V, sc, wr);
   //     attention_mlp.3: d_att1 = (d_att2 W) [att1 > 0] s
   {
     float* dst = a.d_att1 + (int64_t)v0 * D;
@@ -1167,25 +905,12 @@ __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, co
   }
   TR(31);
 }
-// two entry points per stage: with packed FP32 VALU instructions (fp32 storage), and without (SDUMC_NO_PACKED_FP32, chain_common.h:
-// whenever bf16 MFMA kernels run beside this one, i.e. sdumc_net_dims.bf16 != 0)
 template <int R>
 __global__ __launch_bounds__(NTHR) void chain_bwd_a_cl_kernel(const sdumc_chain_args a, const int ncl) { chain_bwd_a_cl_body<R>(a, ncl); }
 
 #undef PF
 #undef PF14
 #undef CL_PROLOGUE
-
-template <int R> constexpr size_t smem_fwd_a() { return sizeof(float) * (PARTC + 11 * R * D + 4 * R + 14 * R * D + 18 * D); }
-template <int R> constexpr size_t smem_fwd_b() { return sizeof(float) * (PARTC + 3 * NQ * R * D + 3 * NQ * R * H + R * NQ * H + R * D + 2 * R * H + R * RD + 12 * R + 4 * D + 4 * H + 2 * RD); }
-template <int R> constexpr size_t smem_bwd_b() { return sizeof(float) * (PARTC + 2 * R * RD + R * H + 2 * R * NQ * H + R * H + R * D + 3 * NQ * R * H + 3 * NQ * R * D + 24 * R); }
-template <int R> constexpr size_t smem_bwd_a() { return sizeof(float) * (PARTC + 3 * NQ * R * D + 2 * NQ * R * D + 6 * R * D + 2 * R * D + 3 * R * D + 8 * R); }
-
-template <class K>
-int set_smem(K kernel, size_t bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess
-             ? SDUMC_OK : SDUMC_ELAUNCH;
-}
 
 // per device: the clusters' counters (zero between launches), the error word, and the event that serialises cluster launches
 // of different streams
@@ -1245,14 +970,14 @@ bool cluster_prepare(ClusterDev* d) {
   std::lock_guard<std::mutex> lk(d->mu);
   if (d->attr == 0) {
     d->attr = -1;
-    if (set_smem(chain_fwd_a_cl_kernel<R>, 158 * 1024) || set_smem(chain_fwd_b_cl_kernel<R>, smem_fwd_b<R>()) ||
-        set_smem(chain_bwd_b_cl_kernel<R>, smem_bwd_b<R>()) || set_smem(chain_bwd_a_cl_kernel<R>, smem_bwd_a<R>()))
+    if (!(sdumc_set_dyn_lds(chain_fwd_a_cl_kernel<R>, 158 * 1024) && sdumc_set_dyn_lds(chain_fwd_b_cl_kernel<R>, FwdB<R>::bytes) &&
+          sdumc_set_dyn_lds(chain_bwd_b_cl_kernel<R>, BwdB<R>::bytes) && sdumc_set_dyn_lds(chain_bwd_a_cl_kernel<R>, BwdA<R>::bytes)))
       return false;
     int n[4] = {0, 0, 0, 0};
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[0], chain_fwd_a_cl_kernel<R>, NTHR, smem_fwd_a<R>()) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[1], chain_fwd_b_cl_kernel<R>, NTHR, smem_fwd_b<R>()) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[2], chain_bwd_b_cl_kernel<R>, NTHR, smem_bwd_b<R>()) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[3], chain_bwd_a_cl_kernel<R>, NTHR, smem_bwd_a<R>()) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[0], chain_fwd_a_cl_kernel<R>, NTHR, FwdA<R>::bytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[1], chain_fwd_b_cl_kernel<R>, NTHR, FwdB<R>::bytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[2], chain_bwd_b_cl_kernel<R>, NTHR, BwdB<R>::bytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[3], chain_bwd_a_cl_kernel<R>, NTHR, BwdA<R>::bytes) != hipSuccess)
       return false;
     if (n[0] < 1 || n[1] < 1 || n[2] < 1 || n[3] < 1) return false;
     d->attr = 1;
@@ -1312,14 +1037,12 @@ extern "C" int sdumc_chain_cluster_launch_(const sdumc_chain_args* ap, int which
     }
     if (hipStreamWaitEvent(st, d->done, 0) != hipSuccess) return SDUMC_ELAUNCH;
   }
-  const size_t smem_a = (a.cl_mode & 32) ? (size_t)158 * 1024 : smem_fwd_a<R>();   // (bit 5, diagnosis: the whole CU's LDS -> no LDS-using neighbour on the CU)
-  {      // (one entry point per stage: the "_np_" twins of round 4 compiled to the same code under the build-wide NOPACK flag)
-    switch (which) {
-      case 0: hipLaunchKernelGGL(chain_fwd_a_cl_kernel<R>, grid, blk, smem_a, st, a, ncl); break;
-      case 1: hipLaunchKernelGGL(chain_fwd_b_cl_kernel<R>, grid, blk, smem_fwd_b<R>(), st, a, ncl); break;
-      case 2: hipLaunchKernelGGL(chain_bwd_b_cl_kernel<R>, grid, blk, smem_bwd_b<R>(), st, a, ncl); break;
-      default: hipLaunchKernelGGL(chain_bwd_a_cl_kernel<R>, grid, blk, smem_bwd_a<R>(), st, a, ncl); break;
-    }
+  const size_t smem_a = (a.cl_mode & 32) ? (size_t)158 * 1024 : FwdA<R>::bytes;   // (bit 5, diagnosis: the whole CU's LDS -> no LDS-using neighbour on the CU)
+  switch (which) {
+    case 0: hipLaunchKernelGGL(chain_fwd_a_cl_kernel<R>, grid, blk, smem_a, st, a, ncl); break;
+    case 1: hipLaunchKernelGGL(chain_fwd_b_cl_kernel<R>, grid, blk, FwdB<R>::bytes, st, a, ncl); break;
+    case 2: hipLaunchKernelGGL(chain_bwd_b_cl_kernel<R>, grid, blk, BwdB<R>::bytes, st, a, ncl); break;
+    default: hipLaunchKernelGGL(chain_bwd_a_cl_kernel<R>, grid, blk, BwdA<R>::bytes, st, a, ncl); break;
   }
   SDUMC_CHECK_LAUNCH();
   if (d->multi && hipEventRecord(d->done, st) != hipSuccess) return SDUMC_ELAUNCH;

@@ -1,23 +1,9 @@
-// chain_common.h -- the rows-x-matrix engine shared by chain.hip (one workgroup per R samples) and chain_cluster.hip (the same
-// stages with every layer's output columns split over a cluster of workgroups).  See chain.hip for the design notes.
+// chain_common.h -- what chain.hip (one workgroup per R samples) and chain_cluster.hip (the same stages with every layer's output
+// columns split over a cluster of workgroups) share: the rows-x-matrix engine, each stage's LDS layout, and every section of the
+// network that lies between the split layers.  See chain.hip for the design notes.
+// (These kernels must not issue packed fp32 VALU operations beside bf16 MFMA neighbours: the whole library is built without
+//  them -- Makefile, NOPACK.)
 #pragma once
-
-// Packed FP32 VALU instructions (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32) and bf16 MFMAs on one CU.
-// Measured on MI355X (round 4: tools/fwd_determinism_probe.py, profiles/README.md): when a workgroup of these kernels shares a CU
-// with a workgroup of a bf16 MFMA GEMM (v_mfma_f32_32x32x16_bf16 -- the Cross_Attention key projections that run beside stage A),
-// the LOW half of some v_pk_fma_f32 results comes out wrong: 26-56 of 299 forwards differed from the fp64 truth in a few
-// even-numbered output columns of a layer; 0 of 3 x 299 without packed ops, 0 of 2 x 299 when the two kernels cannot share a CU
-// (LDS padding), 0 of 199 with fp32-MFMA neighbours.  Inputs were verified intact inside the kernel (weights in registers against
-// agent-scope reloads, the LDS copy of the input rows against global memory).
-// The whole library is now built without packed fp32 operations (Makefile, NOPACK: since the fp32 GEMMs compute their products on
-// the bf16 matrix pipe every kernel has such neighbours, and the pooling kernels showed the same symptom).  The attribute below
-// and the "_np_" entry points it marks (selected by sdumc_chain_args.no_packed_fp32) predate that flag; under it both entry points
-// of a stage compile to the same code.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define SDUMC_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define SDUMC_NO_PACKED_FP32      /* (the host pass does not know the feature) */
-#endif
 #include <type_traits>
 
 #include "common.h"
@@ -236,6 +222,22 @@ __device__ __forceinline__ void rows_x_matrix(const float* in_lds, int ld_in, co
   rxm_run<ROWS, I, O, float>(ring, in_lds, ld_in, M, ldm, part, epi, [] {});
 }
 
+// y = drop(relu(v + bias)): `col` is the layer's global output column, bias_lds the layer's staged bias row
+__device__ __forceinline__ f32x4 fwd_val(f32x4 v, const float* bias_lds, int col, bool relu, const DropRT& drop, uint32_t vrow) {
+  v += ld4(bias_lds + col);
+  if (relu) {
+    v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
+  }
+  if (drop.enabled) v *= drop_mask4(drop, vrow, (uint32_t)(col >> 2));
+  return v;
+}
+// [y > 0] * scale: the backward mask of a layer, from its saved post-dropout output y
+__device__ __forceinline__ f32x4 mask_val(f32x4 v, f32x4 y, float sc) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = y[j] > 0.f ? v[j] * sc : 0.f;
+  return v;
+}
+
 // y = drop(relu(v + bias)) -> LDS and HBM (forward layer epilogue)
 struct FwdEpi {
   const float* bias;
@@ -245,11 +247,7 @@ struct FwdEpi {
   DropRT drop;                           // drop.enabled == 0: none
   uint32_t vrow0, vrow_stride;           // dropout row of local row r = vrow0 + r * vrow_stride ... see call sites
   __device__ __forceinline__ void operator()(int r, int col, f32x4 v) const {
-    v += ld4(bias + col);
-    if (relu) {
-      v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
-    }
-    if (drop.enabled) v *= drop_mask4(drop, vrow0 + (uint32_t)r * vrow_stride, (uint32_t)(col >> 2));
+    v = fwd_val(v, bias, col, relu, drop, vrow0 + (uint32_t)r * vrow_stride);
     if (out_lds) st4(out_lds + r * ld_lds + col, v);
     if (out_g) st4(out_g + (int64_t)r * ld_g + col, v);
   }
@@ -264,13 +262,7 @@ struct BwdEpi {
   float* out_g;    int64_t ld_g;
   __device__ __forceinline__ void operator()(int r, int col, f32x4 v) const {
     if (add_lds) v += ld4(add_lds + r * ld_add + col);
-    if (y_lds) {
-      const f32x4 y = ld4(y_lds + r * ld_y + col);
-      v[0] = y[0] > 0.f ? v[0] * scale : 0.f;
-      v[1] = y[1] > 0.f ? v[1] * scale : 0.f;
-      v[2] = y[2] > 0.f ? v[2] * scale : 0.f;
-      v[3] = y[3] > 0.f ? v[3] * scale : 0.f;
-    }
+    if (y_lds) v = mask_val(v, ld4(y_lds + r * ld_y + col), scale);
     if (out_lds) st4(out_lds + r * ld_lds + col, v);
     if (out_g) st4(out_g + (int64_t)r * ld_g + col, v);
   }
@@ -284,6 +276,445 @@ __device__ __forceinline__ void load_rows(float* dst_lds, const float* src, int6
     const int r = u / q, c = u - r * q;
     st4(dst_lds + r * width + 4 * c, v0 + r < V ? ld4(src + (int64_t)(v0 + r) * ld + 4 * c) : f32x4{0.f, 0.f, 0.f, 0.f});
   }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// LDS layouts: float offsets into a stage's dynamic LDS.  One definition per stage: the kernel takes its pointers from it and the
+// host takes the launch's dynamic-LDS bytes from `bytes`.  PART = the partial-sum area (PART_FLOATS here, PARTC in
+// chain_cluster.hip); a plane count is 1 where chain.hip walks one modality at a time and 3 where chain_cluster.hip keeps the
+// three modalities side by side.
+// ------------------------------------------------------------------------------------------------------------------
+template <int R_, int PART>
+struct FwdALds {
+  static constexpr int R = R_;
+  static constexpr int part = 0;
+  static constexpr int hpre = part + PART;            // [3][R][256]
+  static constexpr int u1 = hpre + 3 * R * D;         // [3][R][256]
+  static constexpr int u = u1 + 3 * R * D;            // [R][768]
+  static constexpr int att1 = u + 3 * R * D;          // [R][256]
+  static constexpr int att2 = att1 + R * D;           // [R][256]
+  static constexpr int alpha = att2 + R * D;          // [R][4]
+  static constexpr int qin = alpha + R * 4;           // [7][R][256]
+  static constexpr int q = qin + 7 * R * D;           // [R][7][256]
+  static constexpr int bias = q + 7 * R * D;          // [18][256]: every bias of the stage (an epilogue then waits on no global load)
+  static constexpr int total = bias + 18 * D;
+  static constexpr size_t bytes = sizeof(float) * total;
+};
+// NX planes of x (ca_out; chain_cluster.hip's three also take c1 afterwards), NC1 planes of c1 of their own
+template <int R_, int PART, int NX, int NC1>
+struct FwdBLds {
+  static constexpr int R = R_;
+  static constexpr int part = 0;
+  static constexpr int x = part + PART;               // [NX][7R][256]
+  static constexpr int c1 = x + NX * NQ * R * D;      // [NC1][7R][256]
+  static constexpr int c = c1 + NC1 * NQ * R * D;     // [3][7R][128]
+  static constexpr int h = c + 3 * NQ * R * H;        // [R][896]
+  static constexpr int e1 = h + R * NQ * H;           // [R][256]
+  static constexpr int e2 = e1 + R * D;               // [R][128]
+  static constexpr int z = e2 + R * H;                // [R][128]
+  static constexpr int r1 = z + R * H;                // [R][64]
+  static constexpr int alpha = r1 + R * RD;           // [R][4]
+  static constexpr int beta = alpha + 4 * R;          // [R][8]
+  static constexpr int bias = beta + 8 * R;           // cmlp0 [3][256], cmlp3 [3][128], catt0 [256], catt3 [128], rnc0 [64], rnc2 [64]
+  static constexpr int total = bias + 4 * D + 4 * H + 2 * RD;
+  static constexpr size_t bytes = sizeof(float) * total;
+};
+// NP planes of d_c and of c1
+template <int R_, int PART, int NP>
+struct BwdBLds {
+  static constexpr int R = R_;
+  static constexpr int part = 0;
+  static constexpr int g = part + PART;               // [R][64]   d_rnc
+  static constexpr int r1 = g + R * RD;               // [R][64]   saved r1, then d_r1
+  static constexpr int dz = r1 + R * RD;              // [R][128]  d_z, then d_e2
+  static constexpr int h = dz + R * H;                // [R][896]  saved h
+  static constexpr int dh = h + R * NQ * H;           // [R][896]
+  static constexpr int e2 = dh + R * NQ * H;          // [R][128]  saved e2
+  static constexpr int e1 = e2 + R * H;               // [R][256]  saved e1, then d_e1
+  static constexpr int dc = e1 + R * D;               // [NP][7R][128] d_c
+  static constexpr int c1 = dc + NP * NQ * R * H;     // [NP][7R][256] saved c1, then d_c1
+  static constexpr int beta = c1 + NP * NQ * R * D;   // [R][8]
+  static constexpr int dbeta = beta + 8 * R;          // [R][8]
+  static constexpr int alpha = dbeta + 8 * R;         // [R][4]
+  static constexpr int dvals = alpha + 4 * R;         // [R] (+ 3 R unused)
+  static constexpr int total = dvals + 4 * R;
+  static constexpr size_t bytes = sizeof(float) * total;
+};
+// NX planes of x (d_qp)
+template <int R_, int PART, int NX>
+struct BwdALds {
+  static constexpr int R = R_;
+  static constexpr int part = 0;
+  static constexpr int x = part + PART;               // [NX][7R][256]  d_qp
+  static constexpr int dq = x + NX * NQ * R * D;      // [R][7][256]
+  static constexpr int dqin = dq + NQ * R * D;        // [7][R][256]
+  static constexpr int u = dqin + NQ * R * D;         // [R][768]  saved u
+  static constexpr int du = u + 3 * R * D;            // [R][768]
+  static constexpr int a2 = du + 3 * R * D;           // [R][256]  saved att2, then d_att2
+  static constexpr int a1 = a2 + R * D;               // [R][256]  saved att1, then d_att1
+  static constexpr int u1 = a1 + R * D;               // [3][R][256] saved u1, then d_u1
+  static constexpr int alpha = u1 + 3 * R * D;        // [R][4]
+  static constexpr int dalpha = alpha + 4 * R;        // [R][4]
+  static constexpr int total = dalpha + 4 * R;
+  static constexpr size_t bytes = sizeof(float) * total;
+};
+
+// ------------------------------------------------------------------------------------------------------------------
+// The sections of the four stages that lie between the split layers, once for both families.  L = the stage's layout, sm = the
+// base of its dynamic LDS; rows [v0, v0 + R) of V.  Every workgroup that calls a section computes all of it into LDS; `wr` says
+// whether this workgroup also writes the results to HBM (chain.hip: always; chain_cluster.hip: member 0).  All 512 threads call.
+// The summation orders are fixed (bitwise reproducible steps): do not reorder a sum here.
+// ------------------------------------------------------------------------------------------------------------------
+
+// stage A forward: the 18 bias rows of the stage -> LDS
+__device__ __forceinline__ void fwd_a_stage_bias(const sdumc_chain_args& a, float* s_bias) {
+  const float* bsrc[18] = {a.umlp0_b[0], a.umlp0_b[1], a.umlp0_b[2], a.umlp3_b[0], a.umlp3_b[1], a.umlp3_b[2], a.att0_b, a.att3_b,
+                           a.query_b[0], a.query_b[1], a.query_b[2], a.query_b[3], a.query_b[4], a.query_b[5], a.query_b[6],
+                           a.caq_b[0], a.caq_b[1], a.caq_b[2]};
+  for (int u = threadIdx.x; u < 18 * (D / 4); u += NTHR) st4(s_bias + 4 * u, ld4(bsrc[u / (D / 4)] + 4 * (u % (D / 4))));
+}
+
+// stage A forward, fc_att (model :303): alpha[r][j] = att2[r] . W[j] + b[j]; ends with a barrier
+template <class L>
+__device__ __forceinline__ void fwd_a_alpha(const sdumc_chain_args& a, float* sm, int v0, int V, bool wr) {
+  constexpr int R = L::R;
+  const float* s_att2 = sm + L::att2;
+  float* s_alpha = sm + L::alpha;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int p = wave; p < 3 * R; p += NWV) {
+    const int r = p / 3, j = p - 3 * r;
+    const float s = wave_sum(dot4(ld4(s_att2 + r * D + 4 * lane), ld4(a.fc_att_w + j * D + 4 * lane)));
+    if (lane == 0) {
+      const float al = s + a.fc_att_b[j];
+      s_alpha[r * 4 + j] = al;
+      if (v0 + r < V && wr) a.alpha[(int64_t)(v0 + r) * 3 + j] = al;
+    }
+  }
+  __syncthreads();
+}
+
+// stage A forward, fusion algebra (model :305-320): the 7 query inputs fused, a+t, t+v, a+v, a, t, v.  own(c): this workgroup
+// writes column c to HBM (chain_cluster.hip: the owner of the column slice).  Ends with a barrier.
+// (own holds its state BY VALUE: with a lambda that captured `member` by reference the compiler contracted the shared products
+//  ua * aa, ut * at, uv * av into other fmas and every clustered result changed in its last bits -- tools/chain_digest.py shows it)
+template <class L, class Own>
+__device__ __forceinline__ void fwd_a_fusion(const sdumc_chain_args& a, float* sm, int v0, int V, Own own) {
+  constexpr int R = L::R;
+  const float *s_u = sm + L::u, *s_alpha = sm + L::alpha;
+  float* s_qin = sm + L::qin;
+  const int64_t VD = (int64_t)V * D;
+  for (int u = threadIdx.x; u < R * (D / 4); u += NTHR) {
+    const int r = u / (D / 4), c = 4 * (u - r * (D / 4));
+    const f32x4 ua = ld4(s_u + r * 3 * D + c), ut = ld4(s_u + r * 3 * D + D + c), uv = ld4(s_u + r * 3 * D + 2 * D + c);
+    const float aa = s_alpha[r * 4], at = s_alpha[r * 4 + 1], av = s_alpha[r * 4 + 2];
+    f32x4 o[7] = {ua * aa + ut * at + uv * av, ua * aa + ut * at, ut * at + uv * av, ua * aa + uv * av, ua, ut, uv};
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      st4(s_qin + (i * R + r) * D + c, o[i]);
+      if (v0 + r < V && own(c)) st4(a.qin + i * VD + (int64_t)(v0 + r) * D + c, o[i]);
+    }
+  }
+  __syncthreads();
+}
+
+// stage B forward: the bias rows of the stage -> LDS
+__device__ __forceinline__ void fwd_b_stage_bias(const sdumc_chain_args& a, float* s_bias) {
+  const int tid = threadIdx.x;
+  for (int u = tid; u < 3 * (D / 4); u += NTHR) st4(s_bias + 4 * u, ld4(a.cmlp0_b[u / (D / 4)] + 4 * (u % (D / 4))));
+  for (int u = tid; u < 3 * (H / 4); u += NTHR) st4(s_bias + 3 * D + 4 * u, ld4(a.cmlp3_b[u / (H / 4)] + 4 * (u % (H / 4))));
+  for (int u = tid; u < D / 4; u += NTHR) st4(s_bias + 3 * D + 3 * H + 4 * u, ld4(a.catt0_b + 4 * u));
+  for (int u = tid; u < H / 4; u += NTHR) st4(s_bias + 4 * D + 3 * H + 4 * u, ld4(a.catt3_b + 4 * u));
+  for (int u = tid; u < RD / 4; u += NTHR) {
+    st4(s_bias + 4 * D + 4 * H + 4 * u, ld4(a.rnc0_b + 4 * u));
+    st4(s_bias + 4 * D + 4 * H + RD + 4 * u, ld4(a.rnc2_b + 4 * u));
+  }
+}
+
+// stage B forward: alpha of rows [v0, v0 + R) -> LDS [R][4]
+template <class L>
+__device__ __forceinline__ void fwd_b_load_alpha(const sdumc_chain_args& a, float* sm, int v0, int V) {
+  constexpr int R = L::R;
+  float* s_alpha = sm + L::alpha;
+  for (int u = threadIdx.x; u < R * 3; u += NTHR) {
+    const int r = u / 3, j = u - 3 * r;
+    s_alpha[r * 4 + j] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
+  }
+}
+
+// stage B forward, modality-weighted sum (model :346-349): h[r][i][:] = sum_m alpha[r][m] c_m[r][i][:]; ends with a barrier
+template <class L>
+__device__ __forceinline__ void fwd_b_hsum(const sdumc_chain_args& a, float* sm, int v0, int V, bool wr) {
+  constexpr int R = L::R;
+  const float *s_c = sm + L::c, *s_alpha = sm + L::alpha;
+  float* s_h = sm + L::h;
+  for (int u = threadIdx.x; u < R * NQ * (H / 4); u += NTHR) {
+    const int ri = u / (H / 4), c = 4 * (u - ri * (H / 4)), r = ri / NQ;
+    const f32x4 hv = ld4(s_c + ri * H + c) * s_alpha[r * 4] + ld4(s_c + (NQ * R + ri) * H + c) * s_alpha[r * 4 + 1] +
+                     ld4(s_c + (2 * NQ * R + ri) * H + c) * s_alpha[r * 4 + 2];
+    st4(s_h + ri * H + c, hv);
+    if (v0 + r < V && wr) st4(a.h + ((int64_t)v0 * NQ + ri) * H + c, hv);
+  }
+  __syncthreads();
+}
+
+// stage B forward, the tail behind cross_attention_mlp (model :354-368): beta = cross_fc_att(e2), cross_fused_feat, fc_out_v, both
+// orgin_linear_change layers.  At most 128 columns wide: one workgroup computes and writes all of it (e2 and h are in LDS).
+template <class L>
+__device__ __forceinline__ void fwd_b_tail(const sdumc_chain_args& a, float* sm, int v0, int V) {
+  constexpr int R = L::R;
+  float* part = sm + L::part;
+  const float *s_e2 = sm + L::e2, *s_h = sm + L::h, *s_bias = sm + L::bias;
+  float *s_z = sm + L::z, *s_r1 = sm + L::r1, *s_beta = sm + L::beta;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int p = wave; p < NQ * R; p += NWV) {          // beta[r][i] = e2[r] . W[i] + b[i]
+    const int r = p / NQ, i = p - NQ * r;
+    float s = lane < H / 4 ? dot4(ld4(s_e2 + r * H + 4 * lane), ld4(a.cfa_w + i * H + 4 * lane)) : 0.f;
+    s = wave_sum(s);
+    if (lane == 0) {
+      const float bt = s + a.cfa_b[i];
+      s_beta[r * 8 + i] = bt;
+      if (v0 + r < V) a.beta[(int64_t)(v0 + r) * NQ + i] = bt;
+    }
+  }
+  __syncthreads();
+  // cross_fused_feat (model :356-358), fc_out_v (model :364)
+  for (int u = tid; u < R * (H / 4); u += NTHR) {
+    const int r = u / (H / 4), c = 4 * (u - r * (H / 4));
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) acc += ld4(s_h + (r * NQ + i) * H + c) * s_beta[r * 8 + i];
+    st4(s_z + r * H + c, acc);
+    if (v0 + r < V) {
+      st4(a.z + (int64_t)(v0 + r) * H + c, acc);
+      if (a.o_fused) st4(a.o_fused + (int64_t)(v0 + r) * H + c, acc);
+    }
+  }
+  __syncthreads();
+  for (int r = wave; r < R; r += NWV) {
+    float s = lane < H / 4 ? dot4(ld4(s_z + r * H + 4 * lane), ld4(a.fcv_w + 4 * lane)) : 0.f;
+    s = wave_sum(s);
+    if (lane == 0 && v0 + r < V) {
+      const float y = s + a.fcv_b[0];
+      a.vals[v0 + r] = y;
+      if (a.o_vals) a.o_vals[v0 + r] = y;
+    }
+  }
+  // orgin_linear_change (model :246-250, :368): Linear -> ReLU -> Linear
+  {
+    FwdEpi e{s_bias + 4 * D + 4 * H, s_r1, RD, a.r1 + (int64_t)v0 * RD, RD, true, DropRT{}, 0u, 0u};
+    auto epi = [&](int r, int col, f32x4 v) { if (v0 + r < V) e(r, col, v); else st4(s_r1 + r * RD + col, f32x4{0.f, 0.f, 0.f, 0.f}); };
+    rows_x_matrix<R, H, RD>(s_z, H, a.rnc0_w, RD, part, epi);
+  }
+  {
+    FwdEpi e{s_bias + 4 * D + 4 * H + RD, nullptr, 0, a.r + (int64_t)v0 * RD, RD, false, DropRT{}, 0u, 0u};
+    float* ro = a.o_rnc ? a.o_rnc + (int64_t)v0 * RD : nullptr;
+    const float* b2 = s_bias + 4 * D + 4 * H + RD;
+    auto epi = [&](int r, int col, f32x4 v) {
+      if (v0 + r < V) {
+        e(r, col, v);
+        if (ro) st4(ro + (int64_t)r * RD + col, v + ld4(b2 + col));
+      }
+    };
+    rows_x_matrix<R, RD, RD>(s_r1, RD, a.rnc2_w, RD, part, epi);
+  }
+}
+
+// stage B backward, head loads: d_rnc, saved r1 / h / e2 / e1, beta, alpha, d_vals (rows beyond V zero).  No barrier.
+template <class L>
+__device__ __forceinline__ void bwd_b_load_head(const sdumc_chain_args& a, float* sm, int v0, int V) {
+  constexpr int R = L::R;
+  float *s_g = sm + L::g, *s_beta = sm + L::beta, *s_alpha = sm + L::alpha, *s_dvals = sm + L::dvals;
+  if (a.g_rnc) load_rows<R>(s_g, a.g_rnc, RD, RD, v0, V);
+  else for (int u = threadIdx.x; u < R * RD; u += NTHR) s_g[u] = 0.f;
+  load_rows<R>(sm + L::r1, a.r1, RD, RD, v0, V);
+  load_rows<R>(sm + L::h, a.h, NQ * H, NQ * H, v0, V);
+  load_rows<R>(sm + L::e2, a.e2, H, H, v0, V);
+  load_rows<R>(sm + L::e1, a.e1, D, D, v0, V);
+  for (int u = threadIdx.x; u < R * 8; u += NTHR) {
+    const int r = u >> 3, i = u & 7;
+    s_beta[u] = (i < NQ && v0 + r < V) ? a.beta[(int64_t)(v0 + r) * NQ + i] : 0.f;
+    if (i < 3) s_alpha[r * 4 + i] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + i] : 0.f;
+    if (i == 0) s_dvals[r] = (a.g_vals && v0 + r < V) ? a.g_vals[v0 + r] : 0.f;
+  }
+}
+
+// stage B backward, 12'. orgin_linear_change: d_r1 = (d_rnc W2) [r1 > 0] ; d_z = d_r1 W0 + d_vals w_v + d_fused
+template <class L>
+__device__ __forceinline__ void bwd_b_rnc(const sdumc_chain_args& a, float* sm, int v0, int V, bool wr) {
+  constexpr int R = L::R;
+  float *part = sm + L::part, *s_r1 = sm + L::r1, *s_dz = sm + L::dz;
+  const float *s_g = sm + L::g, *s_dvals = sm + L::dvals;
+  {
+    BwdEpi e{nullptr, 0, s_r1, RD, 1.0f, s_r1, RD, wr ? a.d_r1 + (int64_t)v0 * RD : nullptr, RD};
+    auto epi = [&](int r, int col, f32x4 v) { if (v0 + r < V) e(r, col, v); else st4(s_r1 + r * RD + col, f32x4{0.f, 0.f, 0.f, 0.f}); };
+    rows_x_matrix<R, RD, RD>(s_g, RD, a.rnc2_w, RD, part, epi);
+  }
+  {
+    const float* gf = a.g_fused;
+    const float* wv = a.fcv_w;
+    float* dzg = a.d_z;
+    auto epi = [&](int r, int col, f32x4 v) {
+      v += ld4(wv + col) * s_dvals[r];
+      if (gf && v0 + r < V) v += ld4(gf + (int64_t)(v0 + r) * H + col);
+      if (v0 + r >= V) v = f32x4{0.f, 0.f, 0.f, 0.f};
+      st4(s_dz + r * H + col, v);
+      if (v0 + r < V && wr) st4(dzg + (int64_t)(v0 + r) * H + col, v);
+    };
+    rows_x_matrix<R, RD, H>(s_r1, RD, a.rnc0_w, H, part, epi);
+  }
+}
+
+// stage B backward, zpool: d_h[i] = beta_i d_z ; d_beta_i = <d_z, h_i>; ends with a barrier
+template <class L>
+__device__ __forceinline__ void bwd_b_zpool(const sdumc_chain_args& a, float* sm, int v0, int V, bool wr) {
+  constexpr int R = L::R;
+  const float *s_dz = sm + L::dz, *s_h = sm + L::h, *s_beta = sm + L::beta;
+  float *s_dh = sm + L::dh, *s_dbeta = sm + L::dbeta;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int u = tid; u < R * NQ * (H / 4); u += NTHR) {
+    const int ri = u / (H / 4), c = 4 * (u - ri * (H / 4)), r = ri / NQ, i = ri - r * NQ;
+    st4(s_dh + ri * H + c, ld4(s_dz + r * H + c) * s_beta[r * 8 + i]);
+  }
+  for (int p = wave; p < NQ * R; p += NWV) {
+    const int r = p / NQ, i = p - NQ * r;
+    float s = lane < H / 4 ? dot4(ld4(s_dz + r * H + 4 * lane), ld4(s_h + (r * NQ + i) * H + 4 * lane)) : 0.f;
+    s = wave_sum(s);
+    if (lane == 0) {
+      s_dbeta[r * 8 + i] = s;
+      if (v0 + r < V && wr) a.d_beta[(int64_t)(v0 + r) * NQ + i] = s;
+    }
+  }
+  __syncthreads();
+}
+
+// stage B backward, 11'. cross_fc_att: d_e2 = (d_beta W_cfa) [e2 > 0] s, into the LDS slot of d_z (dead by now); ends with a barrier
+template <class L>
+__device__ __forceinline__ void bwd_b_de2(const sdumc_chain_args& a, float* sm, int v0, int V, float sc, bool wr) {
+  constexpr int R = L::R;
+  const float *s_e2 = sm + L::e2, *s_dbeta = sm + L::dbeta;
+  float* s_dz = sm + L::dz;
+  for (int u = threadIdx.x; u < R * (H / 4); u += NTHR) {
+    const int r = u / (H / 4), c = 4 * (u - r * (H / 4));
+    f32x4 g = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) g += ld4(a.cfa_w + i * H + c) * s_dbeta[r * 8 + i];
+    g = mask_val(g, ld4(s_e2 + r * H + c), sc);
+    if (v0 + r < V && wr) st4(a.d_e2 + (int64_t)(v0 + r) * H + c, g);
+    st4(s_dz + r * H + c, g);
+  }
+  __syncthreads();
+}
+
+// stage B backward, 10'. modality-weighted sum backward of modality m: d_c_m = (alpha_m d_h (+ d_cross_text on m = 1)) [c_m > 0] s
+// -> s_dcm [7R][128]; d_alpha_m = <d_h, c_m> (per-quad partials through `part`, summed per sample in a fixed order).  One barrier
+// inside, none at the end.
+template <class L>
+__device__ __forceinline__ void bwd_b_dc(const sdumc_chain_args& a, float* sm, float* s_dcm, int m, int v0, int V, float sc, bool wr) {
+  constexpr int R = L::R;
+  float* part = sm + L::part;
+  const float *s_dh = sm + L::dh, *s_alpha = sm + L::alpha;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t VQ = (int64_t)V * NQ;
+  for (int u = tid; u < R * NQ * (H / 4); u += NTHR) {
+    const int ri = u / (H / 4), c = 4 * (u - ri * (H / 4)), r = ri / NQ;
+    const bool live = v0 + r < V;
+    f32x4 cm = {0.f, 0.f, 0.f, 0.f}, g = ld4(s_dh + ri * H + c);
+    if (live) cm = ld4(a.c + ((int64_t)m * VQ + (int64_t)v0 * NQ + ri) * H + c);
+    part[u] = dot4(g, cm);
+    g = g * s_alpha[r * 4 + m];
+    if (m == 1 && a.g_cross_text && live) g += ld4(a.g_cross_text + ((int64_t)v0 * NQ + ri) * H + c);
+    g = mask_val(g, cm, sc);
+    st4(s_dcm + ri * H + c, g);
+    if (live && wr) st4(a.d_c + ((int64_t)m * VQ + (int64_t)v0 * NQ + ri) * H + c, g);
+  }
+  __syncthreads();
+  for (int r = wave; r < R; r += NWV) {
+    float s = 0.f;
+    for (int k = lane; k < NQ * (H / 4); k += 64) s += part[r * NQ * (H / 4) + k];
+    s = wave_sum(s);
+    if (lane == 0 && v0 + r < V && wr) a.d_alpha[(int64_t)(v0 + r) * 3 + m] = s;
+  }
+}
+
+// stage A backward: alpha and stage B's d_alpha of rows [v0, v0 + R) -> LDS [R][4] each
+template <class L>
+__device__ __forceinline__ void bwd_a_load_alpha(const sdumc_chain_args& a, float* sm, int v0, int V) {
+  constexpr int R = L::R;
+  float *s_alpha = sm + L::alpha, *s_dalpha = sm + L::dalpha;
+  for (int u = threadIdx.x; u < R * 3; u += NTHR) {
+    const int r = u / 3, j = u - 3 * r;
+    s_alpha[r * 4 + j] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
+    s_dalpha[r * 4 + j] = v0 + r < V ? a.d_alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
+  }
+}
+
+// stage A backward, 6'. + the external gradient of text_hidden (= query 5), ReLU/dropout mask of q -> d_q (pre-activation), for
+// columns [c0, c0 + W) of every (sample, query) row.  out(g, lds, hbm, live): where the value goes -- its slot in s_dq and in d_q.
+template <class L, int W, class Out>
+__device__ __forceinline__ void bwd_a_mask_q(const sdumc_chain_args& a, float* sm, int v0, int V, float sc, int c0, Out out) {
+  constexpr int R = L::R;
+  float* s_dq = sm + L::dq;
+  for (int u = threadIdx.x; u < R * NQ * (W / 4); u += NTHR) {
+    const int ri = u / (W / 4), c = c0 + 4 * (u - ri * (W / 4)), r = ri / NQ, i = ri - r * NQ;
+    f32x4 g = ld4(s_dq + ri * D + c);
+    const bool live = v0 + r < V;
+    if (i == 5 && a.g_text_hidden && live) g += ld4(a.g_text_hidden + (int64_t)(v0 + r) * D + c);
+    f32x4 y = {0.f, 0.f, 0.f, 0.f};
+    if (live) y = ld4(a.q + ((int64_t)(v0 + r) * NQ + i) * D + c);
+    g = mask_val(g, y, sc);
+    out(g, s_dq + ri * D + c, a.d_q + ((int64_t)(v0 + r) * NQ + i) * D + c, live);
+  }
+}
+
+// stage A backward, 5'. fusion algebra backward: d_u (fusion part), d_alpha += <g_m, u_m> (partials through `part`, fixed order);
+// the final d_alpha is what the fc_att dW GEMM reads.  Ends with a barrier.
+template <class L>
+__device__ __forceinline__ void bwd_a_fusion(const sdumc_chain_args& a, float* sm, int v0, int V, bool wr) {
+  constexpr int R = L::R;
+  float *part = sm + L::part, *s_du = sm + L::du, *s_dalpha = sm + L::dalpha;
+  const float *s_dqin = sm + L::dqin, *s_u = sm + L::u, *s_alpha = sm + L::alpha;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int u = tid; u < R * (D / 4); u += NTHR) {
+    const int r = u / (D / 4), c = 4 * (u - r * (D / 4));
+    const f32x4 df = ld4(s_dqin + (0 * R + r) * D + c), dfat = ld4(s_dqin + (1 * R + r) * D + c),
+                dftv = ld4(s_dqin + (2 * R + r) * D + c), dfav = ld4(s_dqin + (3 * R + r) * D + c);
+    const f32x4 ga = df + dfat + dfav, gt = df + dfat + dftv, gv = df + dftv + dfav;
+    const float aa = s_alpha[r * 4], at = s_alpha[r * 4 + 1], av = s_alpha[r * 4 + 2];
+    st4(s_du + r * 3 * D + c, ga * aa + ld4(s_dqin + (4 * R + r) * D + c));
+    st4(s_du + r * 3 * D + D + c, gt * at + ld4(s_dqin + (5 * R + r) * D + c));
+    st4(s_du + r * 3 * D + 2 * D + c, gv * av + ld4(s_dqin + (6 * R + r) * D + c));
+    part[(r * 3 + 0) * (D / 4) + (c >> 2)] = dot4(ga, ld4(s_u + r * 3 * D + c));
+    part[(r * 3 + 1) * (D / 4) + (c >> 2)] = dot4(gt, ld4(s_u + r * 3 * D + D + c));
+    part[(r * 3 + 2) * (D / 4) + (c >> 2)] = dot4(gv, ld4(s_u + r * 3 * D + 2 * D + c));
+  }
+  __syncthreads();
+  for (int p = wave; p < 3 * R; p += NWV) {
+    const float s = wave_sum(part[p * (D / 4) + lane]);
+    if (lane == 0) {
+      const int r = p / 3, j = p - 3 * r;
+      const float da = s_dalpha[r * 4 + j] + s;
+      s_dalpha[r * 4 + j] = da;
+      if (v0 + r < V && wr) a.d_alpha[(int64_t)(v0 + r) * 3 + j] = da;
+    }
+  }
+  __syncthreads();
+}
+
+// stage A backward, 4'. fc_att: d_att2 = (d_alpha W_fc) [att2 > 0] s, over the saved att2 in LDS; ends with a barrier
+template <class L>
+__device__ __forceinline__ void bwd_a_datt2(const sdumc_chain_args& a, float* sm, int v0, int V, float sc, bool wr) {
+  constexpr int R = L::R;
+  float* s_a2 = sm + L::a2;
+  const float* s_dalpha = sm + L::dalpha;
+  for (int u = threadIdx.x; u < R * (D / 4); u += NTHR) {
+    const int r = u / (D / 4), c = 4 * (u - r * (D / 4));
+    f32x4 g = ld4(a.fc_att_w + c) * s_dalpha[r * 4] + ld4(a.fc_att_w + D + c) * s_dalpha[r * 4 + 1] +
+              ld4(a.fc_att_w + 2 * D + c) * s_dalpha[r * 4 + 2];
+    g = mask_val(g, ld4(s_a2 + r * D + c), sc);
+    st4(s_a2 + r * D + c, g);
+    if (v0 + r < V && wr) st4(a.d_att2 + (int64_t)(v0 + r) * D + c, g);
+  }
+  __syncthreads();
 }
 
 }  // namespace
