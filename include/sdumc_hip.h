@@ -283,6 +283,39 @@ int sdumc_p3_split_frag(const float* src, int64_t ld, void* dst, int32_t rows, i
 int sdumc_p3_join(const void* src, int64_t ld_bytes, float* dst, int64_t ld, int64_t rows, int32_t cols, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The input-feature gradient of a frame projection (csrc/frame_dx.hip): the backward of F.linear of frame_dim_reshape_{0,1,2}
+ * (model :193-195, :282-284) with respect to its INPUT,
+ *   C[M, N] = A[M, 256] . W[256, N]     A = dz (gradient w.r.t. the projected frames), W = frame_dim_reshape_m.weight as stored,
+ * fp32 in, fp32 out.  Arithmetic: the wide-tile family's (sdumc_set_split_ bit 1, the frame / key projections -- this is their
+ * backward): six bf16 x bf16 part products per fp32 product on v_mfma_f32_32x32x16_bf16, fp32 accumulation, the edge contract stated
+ * at sdumc_set_split_; with bit 1 off the product takes the fp32-MFMA route (the NN form of the generic GEMM; it reads W, which must
+ * then be given).  A-stationary: a workgroup splits a 64-row tile of dz once, keeps its planes in LDS and walks the columns; the
+ * weight is read k-major per output column, i.e. as the fragment-major P3 layout of W^T [N][256], which sdumc_p3_split_frag_t writes.
+ * C is OVERWRITTEN.  No atomics: a repeated launch gives the same bits.  Nothing is allocated.
+ * Row zeroing (optional): with `lengths` (device int32 [M / T]) rows b T + t with t >= lengths[b] are written as exact +0.0f
+ * whatever A holds there (they are not multiplied).
+ * SDUMC_EINVAL before any launch: null or not 16-byte aligned A / C / W / W_frag / scratch (W and W_frag both NULL), M < 1, N < 256
+ * or N % 256, ldw < N, ldc < N (or not multiples of 4), lengths without T >= 1 and M % T == 0.  SDUMC_ENOMEM: W_frag NULL and scratch
+ * NULL or below the query. */
+typedef struct sdumc_frame_dx {
+  int32_t M, N;             /* rows (any >= 1), output columns (a multiple of 256) */
+  const float* A;           /* [M][256], row stride 256 */
+  const float* W;           /* [256][N], row stride ldw floats; may be NULL when W_frag is given and bit 1 of the split mask is on */
+  const void* W_frag;       /* sdumc_p3_split_frag_t of W, or NULL: the call packs W into `scratch` first */
+  float* C;                 /* [M][N], row stride ldc floats (64-bit row addressing) */
+  int64_t ldw, ldc;
+  const int32_t* lengths;   /* optional, device int32 [M / T] */
+  int32_t T;
+  void* scratch;            /* >= sdumc_frame_dx_scratch_bytes(N), read only when W_frag is NULL */
+  size_t scratch_bytes;
+} sdumc_frame_dx_t;
+size_t sdumc_frame_dx_scratch_bytes(int32_t N);      /* bytes of the packed weight: 6 * 256 * N; 0 for an N the kernel refuses */
+int sdumc_frame_dx(const sdumc_frame_dx_t* p, void* stream);
+/* fp32 src [K][N] (row stride ld floats; K % 16 == 0, N % 32 == 0, 16-byte aligned) -> the fragment-major P3 layout of its TRANSPOSE
+ * [N][K], exactly what sdumc_p3_split_frag would write for src^T: 6 K N bytes into caller-owned memory */
+int sdumc_p3_split_frag_t(const float* src, int64_t ld, void* dst, int32_t K, int32_t N, void* stream);
+
+/* ------------------------------------------------------------------------
  * The same NT product for the bf16-STORAGE step (sdumc_net_dims.bf16 = 2; csrc/gemm_b1.hip): A and the weight are bf16, fp32
  * accumulation, C bf16 or fp32.  The weight is stored fragment-major -- [N / 32][K / 16][64 lanes][16 bytes], lane (li, lh) of block
  * (rb, kt) holds W[32 rb + li][16 kt + 8 lh .. + 7] (sdumc_b1_frag_multi writes it from the fp32 parameters, round to nearest even)
@@ -1185,7 +1218,27 @@ typedef struct sdumc_net_grads {
   const float* d_cross_text;
   float* grads;               /* [live count] flat gradient bucket; every live tensor is OVERWRITTEN
                                  (alignment padding is left untouched: allocate it zeroed) */
+  /* Optional (all NULL / 0 = the call above: same launches, same bits): the gradients with respect to the INPUT FEATURES, i.e. the
+   * backward of frame_dim_reshape_{0,1,2} (model :193-195, :282-284) through its input -- what autograd gives the reference for
+   * model([audio, text, video, flag]) when a feature tensor requires grad: d_feat_m [B T_m, d_m] = dz_m [B T_m, 256] . W_m [256, d_m].
+   * Each pointer independently; fp32, 16-byte aligned, OVERWRITTEN.  streams == 2: d_audio / d_video hold the SUM over both streams
+   * (one tensor feeds both calls).  Without sdumc_net_io.lengths every row is computed (padded frames take part in the reference's
+   * softmax and have a gradient there too); with lengths the rows t >= length are exact zeros (length 0: every row of the sample,
+   * although the poolings treat such a sample as one frame long).  Row-mapped batches: the outputs are
+   * padded [B, T, d] tensors all the same.  Widths that are multiples of 256 take sdumc_frame_dx, other widths the generic NN GEMM.
+   * Written by sdumc_net_backward and by phase 1 of sdumc_net_backward_phase (phase 0 ignores the fields), each product on its
+   * modality's lane once that modality's dz is final; sdumc_train_step and sdumc_loss_backward ignore the fields.
+   * Before anything is enqueued (no fill, no fork; gradient bucket and outputs untouched): SDUMC_EINVAL for bf16 storage
+   * (sdumc_net_dims.bf16 == 2) with any pointer set, for streams == 1 with d_text[1], for a misaligned output; SDUMC_ENOMEM for
+   * feat_scratch NULL or below sdumc_net_feature_grad_scratch_bytes. */
+  float* d_audio;             /* [B, Ta, da] */
+  float* d_video;             /* [B, Tv, dv] */
+  float* d_text[2];           /* [B, Tt[s], dt]: stream 0 = text, stream 1 = feat4 */
+  void* feat_scratch;         /* the packed transposed frame weights (caller-owned: the workspace plan does not change) */
+  size_t feat_scratch_bytes;
 } sdumc_net_grads;
+/* bytes of sdumc_net_grads.feat_scratch for `d` (never 0 for dims the engine takes); 0: dims the engine refuses, or bf16 storage */
+size_t sdumc_net_feature_grad_scratch_bytes(const sdumc_net_dims* d);
 
 /* loss.backward() through the network (main :149).  Needs the workspace of the matching forward. */
 int sdumc_net_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g, void* stream);

@@ -145,7 +145,16 @@ class NetIO(C.Structure):
 class NetGrads(C.Structure):
     _fields_ = [("d_vals", C.c_void_p), ("d_fused", C.c_void_p), ("d_rnc", C.c_void_p),
                 ("d_text_hidden", C.c_void_p), ("d_cross_text", C.c_void_p),
-                ("grads", C.c_void_p)]
+                ("grads", C.c_void_p),
+                # optional input-feature gradients (all None = today's call): [B, T, d] fp32 outputs + the packed frame weights' scratch
+                ("d_audio", C.c_void_p), ("d_video", C.c_void_p), ("d_text", C.c_void_p * 2),
+                ("feat_scratch", C.c_void_p), ("feat_scratch_bytes", C.c_size_t)]
+
+
+class FrameDx(C.Structure):
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("A", C.c_void_p), ("W", C.c_void_p), ("W_frag", C.c_void_p), ("C", C.c_void_p),
+                ("ldw", C.c_int64), ("ldc", C.c_int64), ("lengths", C.c_void_p), ("T", C.c_int32),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
 class StepCfg(C.Structure):
@@ -312,6 +321,9 @@ _SIGS = {
     "sdumc_gemm_p3_nt": (C.c_int, [C.POINTER(GemmP3), C.c_void_p]),
     "sdumc_p3_split": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     "sdumc_p3_split_frag": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sdumc_p3_split_frag_t": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "sdumc_frame_dx_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "sdumc_frame_dx": (C.c_int, [C.POINTER(FrameDx), C.c_void_p]),
     "sdumc_p3_join": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
     "sdumc_gemm_b1_workspace_bytes": (C.c_size_t, [C.POINTER(GemmB1)]),
     "sdumc_gemm_b1_nt": (C.c_int, [C.POINTER(GemmB1), C.c_void_p]),
@@ -423,6 +435,7 @@ _SIGS = {
     "sdumc_net_backward": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(NetGrads), C.c_void_p]),
     "sdumc_net_backward_phase": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(NetGrads), C.c_int32, C.c_void_p]),
     "sdumc_param_early_count": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "sdumc_net_feature_grad_scratch_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_step_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_train_step": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(StepCfg), C.c_void_p]),
     "sdumc_loss_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims), C.c_int32]),

@@ -182,6 +182,9 @@ struct sdumc_attn_layout {
   int64_t total;
 };
 int sdumc_plan_attn_layout_(const sdumc_net_dims* d, struct sdumc_attn_layout* out);
+// frame_dx.hip: rows b T + t with t >= lengths[b] of C [M][N] := +0.0f; the kernel's per-device LDS attribute
+int sdumc_zero_padded_rows_(float* C, int64_t ldc, int32_t M, int32_t N, const int32_t* lengths, int32_t T, void* stream);
+int sdumc_frame_dx_prepare_(void);
 }
 
 // ---------------------------------------------------------------------------

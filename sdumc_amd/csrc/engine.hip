@@ -536,6 +536,7 @@ extern "C" int sdumc_preload_adam_(void);
 extern "C" int sdumc_preload_chain_(void);
 extern "C" int sdumc_preload_chain_cluster_(void);
 extern "C" int sdumc_preload_transformer_(void);
+extern "C" int sdumc_preload_frame_dx_(void);
 namespace {
 __global__ void sdumc_preload_engine_kernel() {}
 // every code object of the library loaded on the current device, once per device (see the note at the end of any kernel source);
@@ -560,6 +561,7 @@ void preload_code_objects() {
     ok = sdumc_preload_chain_() == SDUMC_OK && ok;
     ok = sdumc_preload_chain_cluster_() == SDUMC_OK && ok;
     ok = sdumc_preload_transformer_() == SDUMC_OK && ok;
+    ok = sdumc_preload_frame_dx_() == SDUMC_OK && ok;
     return ok;
   });
 }
@@ -2181,6 +2183,12 @@ struct BwdSchedule {
     bool frame_dw_grouped = false; // frame_dim_reshape dW: a problem of the grouped launch behind the join (else per stream)
     int k1 = 2;                    // the sites [0, k1) are left for the frame-level pass
   } mod[3];
+  // the input-feature gradients (sdumc_net_grads.d_audio / d_text / d_video): set by plan_feature_grads for sdumc_net_backward and
+  // phase 1 only; the fused step's schedule leaves them empty
+  struct Feat {
+    float* out[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};   // [modality][stream]; audio / video: stream 0 = the sum
+    char* wfrag[3] = {nullptr, nullptr, nullptr};      // where modality m's packed transposed weight goes (widths % 256 == 0)
+  } feat;
 };
 const float* feat_in(const Ctx& c, int m, int s) { return m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]); }
 // launches nothing, records no event, touches no stream: a function of dims, io, the context's options, the process-wide switches
@@ -2540,6 +2548,69 @@ int frame_dw_per_layer(const Ctx& c, int m, int s) {
   return run(c, g);
 }
 
+// the caller's scratch for the packed transposed frame weights: byte offset of modality m (3: the total, never 0)
+size_t feat_scratch_off(const sdumc_net_dims& d, int m) {
+  const int din[3] = {d.da, d.dt, d.dv};
+  size_t off = 0;
+  for (int i = 0; i < 3 && i < m; ++i) off += (sdumc_frame_dx_scratch_bytes(din[i]) + 255) & ~(size_t)255;
+  return m < 3 ? off : std::max<size_t>(off, 256);
+}
+// which input-feature gradients the call writes, and whether it can: launches nothing (the refusals of sdumc_net_grads)
+int plan_feature_grads(const sdumc_net_dims& d, const sdumc_net_grads& g, BwdSchedule::Feat& f) {
+  if (!g.d_audio && !g.d_video && !g.d_text[0] && !g.d_text[1]) return SDUMC_OK;
+  if (d.bf16 == 2 || (d.streams == 1 && g.d_text[1])) return SDUMC_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(g.d_audio) | reinterpret_cast<uintptr_t>(g.d_video) | reinterpret_cast<uintptr_t>(g.d_text[0]) |
+       reinterpret_cast<uintptr_t>(g.d_text[1]) | reinterpret_cast<uintptr_t>(g.feat_scratch)) & 15)
+    return SDUMC_EINVAL;
+  if (!g.feat_scratch || g.feat_scratch_bytes < feat_scratch_off(d, 3)) return SDUMC_ENOMEM;
+  f.out[0][0] = g.d_audio;
+  f.out[1][0] = g.d_text[0];
+  f.out[1][1] = g.d_text[1];
+  f.out[2][0] = g.d_video;
+  for (int m = 0; m < 3; ++m) f.wfrag[m] = static_cast<char*>(g.feat_scratch) + feat_scratch_off(d, m);
+  return SDUMC_OK;
+}
+// d_feat_m = dx_m . W_m on the current lane (modality m's, behind whatever made dx final): widths in whole 256-column blocks take
+// the frame_dx kernel on the weight packed once for both text streams, other widths the generic NN product + a zeroing pass
+int feature_grads(const Ctx& c, const BwdSchedule& sch, int m) {
+  const int din = m == 0 ? c.d.da : (m == 1 ? c.d.dt : c.d.dv);
+  const void* wf = nullptr;
+  for (int s = 0; s < (m == 1 ? c.pl.S : 1); ++s) {
+    float* out = sch.feat.out[m][s];
+    if (!out) continue;
+    const int T = c.pl.T[m][s], rows = c.pl.B * T;
+    const int32_t* lengths = c.io.lengths[feat_slot(m, s)];
+    if (din % 256 == 0) {
+      sdumc_frame_dx_t q;
+      memset(&q, 0, sizeof(q));
+      if (!wf && sdumc_split_on_(SDUMC_SPLIT_WIDE)) {
+        RET(sdumc_p3_split_frag_t(c.P + c.pm.frame[m].w, din, sch.feat.wfrag[m], D, din, c.st));
+        wf = sch.feat.wfrag[m];
+      }
+      q.M = rows;
+      q.N = din;
+      q.A = c.p(c.pl.dx[m][s]);
+      q.W = c.P + c.pm.frame[m].w;
+      q.W_frag = wf;
+      q.C = out;
+      q.ldw = q.ldc = din;
+      q.lengths = lengths;
+      q.T = T;
+      RET(sdumc_frame_dx(&q, c.st));
+    } else {
+      sdumc_gemm g = G_(SDUMC_NN, rows, din, D);
+      g.A[0] = c.p(c.pl.dx[m][s]);
+      g.lda = D;
+      g.B[0] = c.P + c.pm.frame[m].w;
+      g.ldb = g.ldc = din;
+      g.C[0] = out;
+      RET(run(c, g));
+      if (lengths) RET(sdumc_zero_padded_rows_(out, din, rows, din, lengths, T, c.st));
+    }
+  }
+  return SDUMC_OK;
+}
+
 // 2'+1'. three independent per-modality chains, one per lane:
 //   fra2utt_m pooling backward (the shared context vector's gradient = sum of the per-sample dq)
 //   -> input_proj backward of both sites (grouped) -> dx = sum of the (up to) four masked paths into the
@@ -2605,6 +2676,7 @@ int bwd_frame(const Ctx& c, const BwdSchedule& sch, const hipEvent_t* early_done
     //  text's lane, beside the other modalities' dX launches: 1.425-1.431 against 1.390-1.395 ms; a persistent launch in the middle
     //  of the backward holds the CUs the dX chain is waiting for)
     if (M.frame_dw_grouped) (c.h() ? c.ggh : c.gg).push_back(frame_dw_problem(c, m));
+    RET(feature_grads(c, sch, m));      // (dx of this modality is final on its lane; beside the grouped dW of lane 3)
   }
   c.use(0);
   for (int m = 0; m < 3; ++m) mark(c.sts[LANE_OF[m]], 16 + 5 * m);
@@ -2796,12 +2868,16 @@ namespace {
 // the schedule is decided -- and a batch it cannot serve rejected -- before anything of the call is enqueued
 int net_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g, int phases, void* stream) {
   RET(check_io(d, io));
-  const SplitScope split_scope(io);
   if (!g || !g->grads || (reinterpret_cast<uintptr_t>(g->grads) & 15) || phases == 0) return SDUMC_EINVAL;      // (0: a phase other than 0 / 1)
+  BwdSchedule::Feat feat;
+  if (phases & 2) RET(plan_feature_grads(*d, *g, feat));      // (host arithmetic only: refused before a lane or a stream is touched)
+  const SplitScope split_scope(io);
   Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
   RET(ctx_init(c));
   c.G = g->grads;
-  return backward(c, *g, plan_backward(c, phases));
+  BwdSchedule sch = plan_backward(c, phases);
+  sch.feat = feat;
+  return backward(c, *g, sch);
 }
 }  // namespace
 extern "C" int sdumc_net_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_net_grads* g, void* stream) {
@@ -2812,6 +2888,12 @@ extern "C" int sdumc_net_backward_phase(const sdumc_net_dims* d, const sdumc_net
   return net_backward_impl(d, io, g, phase < 0 || phase > 1 ? 0 : 1 << phase, stream);
 }
 extern "C" int64_t sdumc_param_early_count(int32_t da, int32_t dt, int32_t dv) { return build_params(da, dt, dv).early; }
+extern "C" size_t sdumc_net_feature_grad_scratch_bytes(const sdumc_net_dims* d) {
+  Plan p;
+  if (!d || d->bf16 == 2 || !make_plan(*d, p)) return 0;
+  (void)sdumc_frame_dx_prepare_();      // the kernel's per-device attribute, set outside any stream capture
+  return feat_scratch_off(*d, 3);
+}
 
 extern "C" size_t sdumc_loss_workspace_bytes(const sdumc_net_dims* d, int32_t B_global) {
   if (!d || d->B <= 0) return 0;
@@ -2967,6 +3049,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   const size_t V = (size_t)d->B * 2;
   float* dout = reinterpret_cast<float*>(base + sl.dout);
   sdumc_net_grads g;
+  memset(&g, 0, sizeof(g));      // (the input-feature gradients are not part of the fused step)
   g.d_vals = dout;
   g.d_fused = dout + 64 * V;
   g.d_rnc = g.d_fused + H * V;

@@ -276,6 +276,8 @@ class NetCall:
                 self._bits_next = torch.zeros(nb, dtype=torch.uint8, device=dev)
                 io.bits_next = ptr(self._bits_next)
         self.io = io
+        self._feat_scratch = None
+        self.d_inputs = (None, [None] * S, None)
         self.refresh_planes()
 
     def refresh_planes(self):
@@ -304,8 +306,11 @@ class NetCall:
         if self._bits_next is not None:
             self.io.bits_phase ^= 1
 
-    def backward(self, d_vals, d_fused, d_rnc, d_text_hidden, d_cross_text, grads=None):
-        """Returns the flat gradient bucket [live] (allocated zeroed when not given)."""
+    def backward(self, d_vals, d_fused, d_rnc, d_text_hidden, d_cross_text, grads=None, feature_grads=None):
+        """Returns the flat gradient bucket [live] (allocated zeroed when not given).
+        feature_grads: None = parameters only.  True, or one boolean per input in the order (audio, *texts, video), also asks for the
+        gradients with respect to those feature tensors: afterwards self.d_inputs == (d_audio, [d_text ...], d_video), fresh fp32
+        tensors shaped like the inputs, None where not asked (with two streams d_audio / d_video are the sum over both)."""
         _require_cuda(d_vals, d_fused, d_rnc, d_text_hidden, d_cross_text)
         if grads is None:
             grads = torch.zeros(self.layout.live, device=self.vals.device)
@@ -313,6 +318,26 @@ class NetCall:
         g.d_vals, g.d_fused, g.d_rnc = ptr(d_vals), ptr(d_fused), ptr(d_rnc)
         g.d_text_hidden, g.d_cross_text = ptr(d_text_hidden), ptr(d_cross_text)
         g.grads = ptr(grads)
+        self.d_inputs = (None, [None] * self.S, None)
+        if feature_grads is not None and feature_grads is not False:
+            want = (True,) * (2 + self.S) if feature_grads is True else tuple(bool(w) for w in feature_grads)
+            if len(want) != 2 + self.S:
+                raise _lib.SdumcError("feature_grads: True, or one boolean per input (audio, *texts, video)")
+            if any(want):
+                if self.dims.bf16 == 2:
+                    raise _lib.SdumcError("feature gradients are not available in bf16 storage")
+                _, audio, texts, video, _ = self._keep
+                if self._feat_scratch is None:      # the packed transposed frame weights: once per call object
+                    nb = lib.sdumc_net_feature_grad_scratch_bytes(C.byref(self.dims))
+                    self._feat_scratch = torch.empty(nb, dtype=torch.uint8, device=self.vals.device)
+                g.feat_scratch, g.feat_scratch_bytes = ptr(self._feat_scratch), self._feat_scratch.numel()
+                mk = lambda t, w: torch.empty(t.shape, dtype=torch.float32, device=t.device) if w else None
+                d_audio, d_video = mk(audio, want[0]), mk(video, want[-1])
+                d_texts = [mk(t, w) for t, w in zip(texts, want[1:-1])]
+                g.d_audio, g.d_video = ptr(d_audio), ptr(d_video)
+                for i, t in enumerate(d_texts):
+                    g.d_text[i] = ptr(t)
+                self.d_inputs = (d_audio, d_texts, d_video)
         check(lib.sdumc_net_backward(C.byref(self.dims), C.byref(self.io), C.byref(g), _lib.current_stream()),
               "sdumc_net_backward")
         return grads

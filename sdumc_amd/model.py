@@ -21,12 +21,14 @@ GENERAL_DIM = 256
 
 
 class _NetFn(torch.autograd.Function):
-    """One reference forward call (one stream) = sdumc_net_forward; backward = sdumc_net_backward."""
+    """One reference forward call (one stream) = sdumc_net_forward; backward = sdumc_net_backward.  Differentiable in the live
+    parameters and in the three feature tensors (the ones that require grad; model :193-195 through the input); no double backward.
+    train=False: the eval-mode network (no dropout, no Philox state), for input gradients asked of model.eval()."""
 
     @staticmethod
-    def forward(ctx, module, audio, text, video, call_index, lengths, *live_params):
-        rng = engine.RngState(module.seed, audio.device, call=call_index)
-        call = engine.NetCall(module._flat, audio, [text], video, True, rng, sample0=module.sample0,
+    def forward(ctx, module, audio, text, video, call_index, lengths, train, *live_params):
+        rng = engine.RngState(module.seed, audio.device, call=call_index) if train else None
+        call = engine.NetCall(module._flat, audio, [text], video, bool(train), rng, sample0=module.sample0 if train else 0,
                               p_mlp=module.dropout_p, lengths=lengths, planes=False)     # (fresh features every call: a plane copy would be split for one use)
         outs = call.forward()
         ctx.call, ctx.module = call, module
@@ -37,7 +39,10 @@ class _NetFn(torch.autograd.Function):
         def c(t):
             return None if t is None else t.contiguous()
         lay = ctx.module._layout
-        grads = ctx.call.backward(c(d_vals), c(d_fused), c(d_rnc), c(d_text_hidden), c(d_cross_text))
+        want = tuple(ctx.needs_input_grad[1:4])      # (audio, text, video): exactly what autograd asks for
+        grads = ctx.call.backward(c(d_vals), c(d_fused), c(d_rnc), c(d_text_hidden), c(d_cross_text),
+                                  feature_grads=want if any(want) else None)
+        d_audio, d_texts, d_video = ctx.call.d_inputs
         out = []
         for name in ctx.module._live_names:
             off, shape, _ = lay.entries[name]
@@ -46,7 +51,7 @@ class _NetFn(torch.autograd.Function):
                 n *= s
             out.append(grads[off:off + n].view(shape))
         ctx.call = None
-        return (None, None, None, None, None, None) + tuple(out)
+        return (None, d_audio, d_texts[0], d_video, None, None, None) + tuple(out)
 
 
 class WengnetMOSEIMultViewsTextMissing(nn.Module):
@@ -128,12 +133,17 @@ class WengnetMOSEIMultViewsTextMissing(nn.Module):
             self._calls += 1
             if torch.is_grad_enabled():
                 live = [self._get(n) for n in self._live_names]
-                vals, fused, rnc, th, ct = _NetFn.apply(self, audio, text, video, call_index, lengths, *live)
+                vals, fused, rnc, th, ct = _NetFn.apply(self, audio, text, video, call_index, lengths, True, *live)
             else:
                 rng = engine.RngState(self.seed, audio.device, call=call_index)
                 vals, fused, rnc, th, ct = engine.NetCall(self._flat, audio, [text], video, True, rng,
                                                           sample0=self.sample0, p_mlp=self.dropout_p,
                                                           lengths=lengths, planes=False).forward()
+        elif torch.is_grad_enabled() and (audio.requires_grad or text.requires_grad or video.requires_grad):
+            # eval mode with an input that requires grad (saliency, adversarial directions): the reference's eval-mode outputs are
+            # autograd-connected, so are these; every other eval call takes the plain path below
+            live = [self._get(n) for n in self._live_names]
+            vals, fused, rnc, th, ct = _NetFn.apply(self, audio, text, video, 0, lengths, False, *live)
         else:
             vals, fused, rnc, th, ct = engine.NetCall(self._flat, audio, [text], video, False, None,
                                                       p_mlp=self.dropout_p, lengths=lengths, planes=False).forward()

@@ -134,6 +134,38 @@ def p3_split_frag(w, out=None):
     return out
 
 
+def p3_split_frag_t(w, out=None):
+    """fp32 [K, N] (K % 16 == 0, N % 32 == 0) -> the fragment-major P3 tensor of its TRANSPOSE [N, K] (= p3_split_frag(w.t())):
+    uint8 [N / 32, K / 16 * 3072]."""
+    K, N = w.shape
+    if out is None:
+        out = torch.empty(N // 32, K // 16 * 3072, dtype=torch.uint8, device=w.device)
+    check(lib.sdumc_p3_split_frag_t(ptr(w), w.stride(0), ptr(out), K, N, _st()), "sdumc_p3_split_frag_t")
+    return out
+
+
+def frame_dx(dz, W, C_out=None, W_frag=None, lengths=None, T=0, scratch=None):
+    """C [M, N] = dz [M, 256] . W [256, N] (sdumc_frame_dx: the input-feature gradient of a frame projection).  W_frag: the weight
+    already packed by p3_split_frag_t; else the call packs it into `scratch` (allocated here when not given).  lengths (int32
+    [M / T]) + T: rows b * T + t with t >= lengths[b] come back as +0.0.  C_out may be a view with a row stride above N."""
+    M, N = dz.shape[0], W.shape[1]
+    if C_out is None:
+        C_out = torch.empty(M, N, device=dz.device)
+    q = _lib.FrameDx()
+    q.M, q.N, q.A, q.W, q.C = M, N, ptr(dz), ptr(W), ptr(C_out)
+    q.ldw, q.ldc = W.stride(0), C_out.stride(0)
+    if W_frag is not None:
+        q.W_frag = ptr(W_frag)
+    else:
+        if scratch is None:
+            scratch = torch.empty(max(16, lib.sdumc_frame_dx_scratch_bytes(N)), dtype=torch.uint8, device=dz.device)
+        q.scratch, q.scratch_bytes = ptr(scratch), scratch.numel()
+    if lengths is not None:
+        q.lengths, q.T = ptr(lengths), T
+    check(lib.sdumc_frame_dx(C.byref(q), _st()), "sdumc_frame_dx")
+    return C_out
+
+
 def p3_join(p3, cols):
     """P3 tensor -> fp32 [rows, cols], bit-exact inverse of p3_split"""
     rows = p3.shape[0]
