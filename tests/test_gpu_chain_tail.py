@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import grad_parity as GP
 from tests.test_gpu_net import NAMES, _oracle_grads, close, flat_from
 
 pytestmark = pytest.mark.gpu
@@ -79,7 +80,7 @@ _oracle_cache = {}
 
 
 def oracle(B, mode, backward=True):
-    """fp64 oracle of run_net's call, computed once per (B, mode)"""
+    """fp64 oracle of run_net's call (outputs, gradients) and the fp32 oracle's gradients, computed once per (B, mode)"""
     key = (B, mode)
     if key not in _oracle_cache:
         from oracle import sdumc_oracle as O
@@ -87,14 +88,15 @@ def oracle(B, mode, backward=True):
         d = O.DropCtx("eval" if mode == "eval" else "philox", SEED, CALL0)
         y, (z, r, th, ct) = O.forward({k: v.double() for k, v in P.items()}, audio.double(), text.double(), video.double(), d)
         grads = _oracle_grads(P, audio, [text], video, mode, SEED, CALL0, douts) if backward else None
-        _oracle_cache[key] = ((y, z, r, th, ct), grads)
+        grads32 = _oracle_grads(P, audio, [text], video, mode, SEED, CALL0, douts, dtype=torch.float32) if backward else None
+        _oracle_cache[key] = ((y, z, r, th, ct), grads, grads32)
     return _oracle_cache[key]
 
 
 @pytest.mark.parametrize("B", [3, 1])
 def test_odd_sample_count_forward_backward_both_families_vs_oracle(E, B):
     """Cases a (V = 3) and b (V = 1): train-mode forward, backward with all five external gradients, plain and clustered."""
-    want_outs, want_grads = oracle(B, "train")
+    want_outs, want_grads, grads32 = oracle(B, "train")
     lay = E.ParamLayout.get(*DIMS[:3])
     res = [run_net(E, B, True, cluster) for cluster in (0, 1)]
     for cluster, (outs, grads) in enumerate(res):
@@ -104,6 +106,9 @@ def test_odd_sample_count_forward_backward_both_families_vs_oracle(E, B):
         assert set(want_grads) == set(lay.live_names())
         for k in lay.live_names():
             close(gv[k], want_grads[k], 2e-4, f"{k} cluster={cluster}")
+        # (that bar is tied to max(1, |g|)) every tensor against its own norm: external gradients of O(1), every tensor carries signal
+        own = GP.tensor_errors(lay, gv, want_grads, grads32, 2e-4, what=f"fp32 NetCall train, V = {B}, cluster={cluster}")
+        assert len(own) == len(lay.live_names())
     for name, a, b in zip(NAMES, res[0][0], res[1][0]):
         assert float((a - b).abs().max()) < 2e-5 * float(a.abs().max()), name
     gscale = float(res[0][1].abs().max())
@@ -114,7 +119,7 @@ def test_odd_sample_count_forward_backward_both_families_vs_oracle(E, B):
 
 def test_odd_sample_count_eval_forward_vs_oracle(E):
     """Case c: eval mode (no dropout, relu_scale = 1), V = 3, both families."""
-    want_outs, _ = oracle(3, "eval", backward=False)
+    want_outs = oracle(3, "eval", backward=False)[0]
     for cluster in (0, 1):
         outs, _ = run_net(E, 3, False, cluster, backward=False)
         for name, got, want in zip(NAMES, outs, want_outs):

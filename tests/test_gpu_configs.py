@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import grad_parity as GP
+
 pytestmark = pytest.mark.gpu
 
 NAMES = ("vals", "fused", "rnc", "text_hidden", "cross_text")
@@ -37,15 +39,10 @@ def flat_from(E, P, dims):
     return flat.cuda(), lay
 
 
-def close_norm(got, want, tol, msg):
-    """Tensor-wise relative error: gradients of this path are 1e-5 and smaller, an absolute tolerance tied to 1.0 says nothing about them."""
-    got, want = got.detach().cpu().double(), want.detach().cpu().double().reshape(got.shape)
-    ref = float(want.norm())
-    if ref < 1e-7:       # (analytically zero up to rounding: the RnC head's biases -- the loss is translation invariant)
-        assert float(got.norm()) < 1e-6, msg
-        return
-    err = float((got - want).norm()) / ref
-    assert err < tol, f"{msg}: relative error {err:.3e} (norms {float(got.norm()):.3e} vs {ref:.3e})"
+# Tensor-wise relative error: gradients of this path are 1e-5 and smaller, an absolute tolerance tied to 1.0 says nothing about them.
+# The absolute bar below a reference norm of 1e-7 holds for the RnC head's biases alone (analytically zero: the loss is translation
+# invariant) -- by name: C2's frame biases have norms of 1.4e-7 and belong with the compared tensors whatever the batch makes of them.
+close_norm = GP.close_norm
 
 
 def test_c1_mosi_shapes_full_step_vs_oracle(E):
@@ -147,7 +144,7 @@ def test_c4_global_batch_512_on_one_gpu_and_two_simulated_ranks(E):
     for l in ls:
         np.testing.assert_allclose(l[3:7].numpy(), ref_losses[3:7].numpy(), rtol=1e-4)
     gv, rv = gsum.cpu(), ref_grads.cpu()
-    worst = (0.0, "")
+    worst, skipped = (0.0, ""), []
     span = {k: (lay.entries[k][0], int(np.prod(lay.entries[k][1]))) for k in lay.live_names()}
     G = max(float(rv[o:o + n].double().norm()) / np.sqrt(n) for o, n in span.values())      # the largest per-element rms of a tensor
     for k, (off, n) in span.items():
@@ -156,12 +153,16 @@ def test_c4_global_batch_512_on_one_gpu_and_two_simulated_ranks(E):
         # sides differ by summation order only (two K ranges of 256 rows against one of 512): measured <= 1e-5
         ref = float(rv[off:off + n].double().norm())
         err = float((gv[off:off + n].double() - rv[off:off + n].double()).norm())
-        if ref / np.sqrt(n) >= 1e-6 * G:
+        if k in GP.NO_SIGNAL and ref / np.sqrt(n) < 1e-6 * G:
+            # the RnC head's biases, and no other tensor: zero by translation invariance -- rounding noise on both sides.  (There is
+            # no oracle at this size; until the rule went by name, every tensor under 1e-6 G was let through here.)
+            assert err / np.sqrt(n) < 1e-5 * G, (k, err, G)
+            skipped.append(k)
+        else:
             assert err / ref < 2e-4, f"{k}: DP(2 x 256) vs single(512) relative gradient error {err / ref:.3e} (|g| = {ref:.3e})"
             worst = max(worst, (err / ref, k))
-        else:      # (the RnC head's biases: zero by translation invariance -- rounding noise on both sides)
-            assert err / np.sqrt(n) < 1e-5 * G, (k, err, G)
-    print("C4: DP(2 x 256) vs single process, worst relative gradient error %.3g (%s)" % worst)
+    print("grad parity C4 DP(2 x 256) vs single process: %d of %d tensors compared, %d no-signal; worst %s = %.3g" %
+          (len(span) - len(skipped), len(span), len(skipped), worst[1], worst[0]))
     for be in bes:
         be.grads.copy_(gsum)
         be.adam(1.0)
@@ -181,15 +182,15 @@ C5_BF16_GRAD_MAX = 0.2
 
 
 def grad_errors(lay, got, ref):
-    """norm-wise relative error of every live gradient tensor; tensors whose reference gradient is numerically zero -- per-element
-    rms below 1e-6 of the largest tensor's: orgin_linear_change.{0,2}.bias, zero by the translation invariance of RnC -- carry
-    no signal for a relative error and must be just as small on the device"""
+    """norm-wise relative error of every live gradient tensor but orgin_linear_change.{0,2}.bias -- BY NAME (tests/grad_parity.py):
+    zero by the translation invariance of RnC, where their per-element rms is below 1e-6 of the largest tensor's they carry no
+    signal for a relative error and must be just as small on the device.  (By size alone that rule skipped a third of the tensors.)"""
     rms = {k: float(ref[k].double().norm() / np.sqrt(ref[k].numel())) for k in lay.live_names()}
     G = max(rms.values())
     errs = {}
     for k in lay.live_names():
         d = float((got[k].double() - ref[k].double()).norm())
-        if rms[k] < 1e-6 * G:
+        if k in GP.NO_SIGNAL and rms[k] < 1e-6 * G:
             assert d / np.sqrt(ref[k].numel()) < 1e-5 * G, (k, d, G)
             continue
         errs[k] = d / float(ref[k].double().norm())
@@ -234,6 +235,9 @@ def _bf16_full_batch_properties(E, dims, B, Tn, seed):
     assert not torch.equal(runs[0][1], runs[2][1]), "bf16 mode is not active"
     gb, gf = lay.views(torch.cat([runs[0][1], torch.zeros(lay.total - lay.live)])), lay.views(torch.cat([runs[2][1], torch.zeros(lay.total - lay.live)]))
     errs = grad_errors(lay, gb, gf)
+    worst = max(errs, key=errs.get)
+    print("grad parity bf16 storage vs fp32 storage, B = %d, T = %s: %d of %d tensors compared; worst %s = %.3g" %
+          (B, Tn, len(errs), len(lay.live_names()), worst, errs[worst]))
     for k, err in errs.items():
         assert float(gb[k].abs().max()) > 0.0, k
         assert err < C5_BF16_GRAD_MAX, (k, err)
@@ -274,10 +278,10 @@ def test_c5_long_sequence_shapes_in_bf16_vs_fp32_oracle(E):
     # norm-wise per tensor; tensors whose gradient is (analytically or numerically) negligible next to the largest one --
     # orgin_linear_change.2.bias is exactly zero by the translation invariance of RnC -- carry no signal to compare
     errs = grad_errors(lay, gv, grads)
-    vals = sorted(errs.values())
+    vals = sorted(errs[k] for k in GP.old_rule_compared(list(lay.live_names()), grads))      # (median, p90: over the set they were set for)
     worst = max(errs, key=errs.get)
-    print("C5 bf16 gradient errors: median %.3g, 90th percentile %.3g, worst %s = %.3g" %
-          (float(np.median(vals)), vals[int(0.9 * len(vals))], worst, errs[worst]))
+    print("grad parity C5 B = 4 bf16 storage vs fp32 oracle: %d of %d tensors compared; median %.3g, p90 %.3g (both over the %d of the former "
+          "rule), worst %s = %.3g" % (len(errs), len(lay.live_names()), float(np.median(vals)), vals[int(0.9 * len(vals))], len(vals), worst, errs[worst]))
     # median 2 %; a few small tensors (a handful of biases whose gradient is a difference of large terms) sit higher; EVERY
     # tensor is bounded (C5_BF16_GRAD_MAX): a tensor of garbage would read >= 1
     assert float(np.median(vals)) < 4e-2 and vals[int(0.9 * len(vals))] < 0.2, (float(np.median(vals)), worst, errs[worst])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from . import grad_parity as GP
 from .test_gpu_configs import NAMES, close, flat_from, grad_errors
 
 pytestmark = pytest.mark.gpu
@@ -26,6 +27,13 @@ BF16_EMU_GRAD_TOL = 1e-2          # every tensor
 BF16_EMU_GRAD_P90 = 2e-3          # 90th percentile over the tensors
 BF16_EMU_GRAD_MEDIAN = 5e-4
 BF16_EMU_OUT_TOL = 2e-3
+# C2 in bf16 storage: the formerly skipped tensors that the emulation's fp32-parameter evaluation moves by more than
+# BF16_EMU_GRAD_TOL / 4 (profiles/grad_parity_by_tensor.txt: e_ref 0.004 for fra2utt_1.input_proj.bias, 0.015 .. 0.035 for the
+# others; the next formerly skipped tensor, cross_att_fra2utt_0.input_proj.bias, has 1.8e-3 and is held to the flat bar)
+C2_BF16_BETWEEN = ("audio_mlp.0.weight", "audio_mlp.3.weight", "video_mlp.0.weight", "video_mlp.3.weight",
+                   "fra2utt_0.attention_context_vector", "fra2utt_0.input_proj.weight", "fra2utt_0.input_proj.bias",
+                   "fra2utt_1.input_proj.bias",
+                   "fra2utt_2.attention_context_vector", "fra2utt_2.input_proj.weight", "fra2utt_2.input_proj.bias")
 
 
 @pytest.fixture(scope="module")
@@ -40,8 +48,13 @@ def E():
 # ~1e-5, the smallest 3.5e-10 -- so an absolute tolerance tied to max(1, |g|) passes an all-zero gradient; that was this test until
 # round 6).  Measured on MI355X (profiles/r6_fullsize_grad_errors.txt): C2 median 1.0e-6, 90th percentile 1.3e-6, worst 2.5e-5
 # (planes) / 5.7e-5 (in-kernel split), both on the RnC head (orgin_linear_change.0: small gradients with heavy cancellation); C5
-# median 1.2e-6, worst 4e-6.  (The RnC head's analytically zero biases are handled by grad_errors: they must be as small on the
-# device.)  A kernel that drops a term moves its tensors to >= 1e-2.
+# median 1.2e-6, worst 4e-6.  A kernel that drops a term moves its tensors to >= 1e-2.
+# WHICH tensors are compared is decided on the reference side alone (tests/grad_parity.py): the reference is the fp64 oracle, and a
+# tensor is set aside only where the fp32 oracle disagrees with it by more than 10 % of the tensor's norm -- the RnC head's biases,
+# zero by translation invariance -- 82 of 83 at C2, 81 of 83 at C5.  (Until this rule, every tensor whose per-element rms was below
+# 1e-6 of the largest tensor's was set aside: 26 of C2's 83 and 30 of C5's, the whole backward of the audio and video attention
+# sites among them.)  Measured over all of them (profiles/grad_parity_by_tensor.txt): median 1.0e-6, p90 1.4e-6, worst 6.0e-5, still on
+# the RnC head; orgin_linear_change.2.weight is the one tensor the two oracles know no better than 5e-5 .. 6e-5 (in between).
 FP32_GRAD_TOL = 2e-4
 
 
@@ -49,7 +62,8 @@ _ORACLE_CACHE = {}
 
 
 def _oracle_step(cfg, pseed, bseed, seed):
-    """(P, batch, Pd after Adam, loss, terms, grads, outs): 5-10 s of CPU per call at these sizes, shared by the two product paths"""
+    """(P, batch, Pd after Adam, loss, terms, grads, outs, grads of the fp64 evaluation): 5-10 s of CPU for the fp32 step and about as
+    much for the fp64 one at these sizes, shared by the two product paths"""
     from oracle import sdumc_oracle as O
     key = (cfg, pseed, bseed, seed)
     if key not in _ORACLE_CACHE:
@@ -57,7 +71,8 @@ def _oracle_step(cfg, pseed, bseed, seed):
         P = O.init_params(dims, seed=pseed)
         batch = O.synthetic_batch(B, Tn, dims, seed=bseed)
         Pd = {k: v.clone() for k, v in P.items()}
-        _ORACLE_CACHE[key] = (P, batch, Pd) + tuple(O.train_step(Pd, {}, *batch, mode="philox", seed=seed, step=0))
+        _ORACLE_CACHE[key] = (P, batch, Pd) + tuple(O.train_step(Pd, {}, *batch, mode="philox", seed=seed, step=0)) + \
+            (GP.oracle_step_grads(P, batch, seed),)
     return _ORACLE_CACHE[key]
 
 
@@ -65,7 +80,7 @@ def _step_fp32_vs_oracle(E, cfg, pseed, bseed, seed, delta_names, planes):
     """planes=False: the step a set_batch-per-step loop runs (in-kernel operand split, csrc/gemm_wide.hip); planes=True: the step over
     RESIDENT batches -- bench.py's headline and FusedTrainer.run_epoch -- whose frame / key projections read bf16 planes (csrc/gemm_p3.hip)."""
     dims, B, Tn = cfg
-    P, batch, Pd, loss, terms, grads, outs = _oracle_step(cfg, pseed, bseed, seed)
+    P, batch, Pd, loss, terms, grads, outs, grads64 = _oracle_step(cfg, pseed, bseed, seed)
     flat, lay = flat_from(E, P, dims)
     ts = E.TrainStep(flat, B, Tn, dims, seed=seed, planes=planes)
     assert (ts._planes is not None) == planes
@@ -80,12 +95,13 @@ def _step_fp32_vs_oracle(E, cfg, pseed, bseed, seed, delta_names, planes):
     assert set(grads) == set(lay.live_names())
     for k in lay.live_names():
         close(gv[k], grads[k], 1e-3, k)           # (the north-star's absolute bar; says little about tensors far below 1e-3 ...)
-    errs = grad_errors(lay, gv, grads)            # (... so: every tensor relative to its own norm)
-    worst = max(errs, key=errs.get)
-    vals = sorted(errs.values())
-    print("fp32 %s, planes=%s: gradient errors relative to each tensor's norm: median %.3g, p90 %.3g, worst %s = %.3g" %
-          ("C2" if cfg is C2 else "C5", planes, float(np.median(vals)), vals[int(0.9 * len(vals))], worst, errs[worst]))
-    for k, e in errs.items():
+    # (... so: every tensor relative to its own norm, against the fp64 oracle; the fp32 oracle says how well each can be known)
+    errs = GP.tensor_errors(lay, gv, grads64, grads, FP32_GRAD_TOL, what="fp32 %s B = %d, planes=%s" % ("C2" if cfg is C2 else "C5", B, planes))
+    assert len(errs) == (82 if cfg is C2 else 81), errs.line
+    # (what this test held until now, against the fp32 oracle; the set is now taken from the fp64 gradients' rms where it was taken
+    # from the fp32 oracle's: the same tensors unless one sits exactly on 1e-6 G)
+    for k in errs.old_compared:
+        e = float((gv[k].double() - grads[k].double()).norm()) / float(grads[k].double().norm())
         assert e < FP32_GRAD_TOL, f"{k}: relative gradient error {e:.3e} (|g| = {float(grads[k].norm()):.3e})"
     pv = lay.views(flat.cpu())
     for k in delta_names:          # post-Adam deltas (first step: lr * g / (|g| + eps))
@@ -135,13 +151,17 @@ def _step_bf16_vs_oracles(E, cfg, pseed, bseed, seed):
     for s in range(2):
         for n, got, want in zip(NAMES, got_outs, outs64[s]):
             close(got[s * B:(s + 1) * B], want, BF16_EMU_OUT_TOL, f"bf16 vs rounding emulation: {n} stream {s}")
-    errs = grad_errors(lay, gv, grads64)
-    worst = max(errs, key=errs.get)
-    vals = sorted(errs.values())
-    print("bf16 storage vs fp64 rounding emulation, gradient errors: median %.3g, worst %s = %.3g; vs fp32 oracle: worst %.3g" %
-          (float(np.median(vals)), worst, errs[worst], max(grad_errors(lay, gv, grads32).values())))
-    for k, e in errs.items():
-        assert e < BF16_EMU_GRAD_TOL, (k, e)
+    # every tensor at BF16_EMU_GRAD_TOL; where the emulation's OWN fp32-parameter evaluation moves a tensor by more than a quarter of
+    # that the bar follows it (grad_parity's in-between rule), for the tensors this test did not compare before.  At C5 there is
+    # none and the helper's cap of 2 holds.  At C2 the cap cannot hold: bf16 roundings that flip between the emulation's fp64 and
+    # fp32 evaluation move the audio and video branch up to the pooling by e_ref 4e-3 .. 3.5e-2, so the class is pinned to
+    # C2_BF16_BETWEEN by name instead; a twelfth tensor in it fails the test.  The device does not need the raise: measured, all 82
+    # tensors of C2 within 3.3e-3 (worst frame_dim_reshape_2.weight), all 81 of C5 within 5.9e-3 (fra2utt_2.input_proj.bias).
+    lo = GP.oracle_step_grads(P, batch, seed, dtype=torch.float32, st=Bf16Storage())
+    errs = GP.tensor_errors(lay, gv, grads64, lo, BF16_EMU_GRAD_TOL, between=C2_BF16_BETWEEN if cfg is C2 else (),
+                            what="bf16 storage %s B = %d vs fp64 rounding emulation" % ("C2" if cfg is C2 else "C5", B))
+    vals = sorted(errs[k] for k in errs.old_compared)      # (median and p90 over the tensors this test has always compared)
+    print("bf16 storage vs fp32 oracle: worst %.3g" % max(grad_errors(lay, gv, grads32).values()))
     assert vals[int(0.9 * len(vals))] < BF16_EMU_GRAD_P90 and float(np.median(vals)) < BF16_EMU_GRAD_MEDIAN, \
         (float(np.median(vals)), vals[int(0.9 * len(vals))])
 

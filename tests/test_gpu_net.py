@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import grad_parity as GP
+
 pytestmark = pytest.mark.gpu
 
 NAMES = ("vals", "fused", "rnc", "text_hidden", "cross_text")
@@ -77,16 +79,16 @@ def test_forward_vs_reference_golden(E, golden, mode, streams):
                 close(t, g[f"{mode}{s}_{n}"], 2e-5, f"{n} stream {s}")
 
 
-def _oracle_grads(P, audio, texts, video, mode, seed, call0, douts):
+def _oracle_grads(P, audio, texts, video, mode, seed, call0, douts, dtype=torch.float64):
     from oracle import sdumc_oracle as O
-    leaves = {k: v.double().requires_grad_(not O.is_dead(k)) for k, v in P.items()}
+    leaves = {k: v.to(dtype).requires_grad_(not O.is_dead(k)) for k, v in P.items()}
     total = 0
     for s, tx in enumerate(texts):
         d = O.DropCtx("eval" if mode == "eval" else "philox", seed, call0 + s)
-        y, (z, r, th, ct) = O.forward(leaves, audio.double(), tx.double(), video.double(), d)
+        y, (z, r, th, ct) = O.forward(leaves, audio.to(dtype), tx.to(dtype), video.to(dtype), d)
         for o, do in zip((y, z, r, th, ct), douts):
             B = y.shape[0]
-            total = total + (o * do[s * B:(s + 1) * B].double().reshape(o.shape)).sum()
+            total = total + (o * do[s * B:(s + 1) * B].to(dtype).reshape(o.shape)).sum()
     total.backward()
     return {k: v.grad for k, v in leaves.items() if v.grad is not None}
 
@@ -255,6 +257,8 @@ def test_mosei_shape_forward_and_step_vs_oracle(E):
     gv = lay.views(torch.cat([ts.grads.cpu(), torch.zeros(lay.total - lay.live)]))
     for k in lay.live_names():
         close(gv[k], grads[k], 1e-3, k)
+    # (75 of the 83 tensors are so far below that bar that a zero gradient would pass it) every tensor against its own norm
+    GP.tensor_errors(lay, gv, GP.oracle_step_grads(P, (audio, text, video, feat4, vals), 777), grads, 2e-4, what="fp32 C2 shapes B = 8 (plain schedule)")
     pv = lay.views(flat.cpu())
     for k in ("frame_dim_reshape_1.weight", "cross_att_fra2utt_0.input_proj.weight", "fc_out_v.weight"):
         close((pv[k] - P[k]) * 1e4, (Pd[k] - P[k]) * 1e4, 2e-2, k)
@@ -285,6 +289,12 @@ def test_train_step_smallest_batches_vs_oracle(E, B):
         gv = lay.views(torch.cat([ts.grads.cpu(), torch.zeros(lay.total - lay.live)]))
         for k in lay.live_names():
             close(gv[k], grads[k], 5e-4, k)
+        # ... and against its own norm (the absolute bar cannot see 32 / 45 / 54 of the 83 tensors at B = 1 / 2 / 3).  B = 1: the RnC
+        # loss of the two rows of one sample has no negative, its gradient is exactly zero -- the head's four tensors
+        zeros = [f"orgin_linear_change.{i}.{w}" for i in (0, 2) for w in ("weight", "bias")] if B == 1 else ()
+        res = GP.tensor_errors(lay, gv, GP.oracle_step_grads(P, (audio, text, video, feat4, vals), 5), grads, 2e-4, zeros=zeros,
+                               what=f"fp32 toy shapes B = {B}")
+        assert len(res.zero) == len(zeros)
 
 
 def test_full_c2_batch_properties(E):
@@ -388,6 +398,7 @@ def test_long_sequence_c5_shapes_vs_oracle(E):
     gv = lay.views(torch.cat([ts.grads.cpu(), torch.zeros(lay.total - lay.live)]))
     for k in lay.live_names():
         close(gv[k], grads[k], 1e-3, k)
+    GP.tensor_errors(lay, gv, GP.oracle_step_grads(P, batch, 11), grads, 2e-4, what="fp32 C5 shapes B = 4")      # 72 of 83 are below the bar above
 
 
 def test_large_batch_rnc_1024_rows(E):
@@ -403,10 +414,14 @@ def test_large_batch_rnc_1024_rows(E):
     ts = E.TrainStep(flat, B, Tn, dims, seed=12)
     ts.set_batch(*[t.cuda() for t in batch])
     losses = ts.run().cpu().numpy()
-    loss, terms, _ = O.step_loss(P, *batch, mode="philox", seed=12, step=0)
+    loss, terms, grads, _ = O.train_step({k: v.clone() for k, v in P.items()}, {}, *batch, mode="philox", seed=12, step=0)
     np.testing.assert_allclose(losses[1:7], [float(t) for t in terms], rtol=2e-4, atol=1e-6)
     np.testing.assert_allclose(losses[0], float(loss), rtol=2e-4)
     assert torch.isfinite(ts.grads).all()
+    # every gradient tensor against its own norm (the sorted RnC formulation's backward at n = 1024 with ties; about 10 s of CPU for
+    # the oracle's two backward passes through the literal RnC loop)
+    gv = lay.views(torch.cat([ts.grads.cpu(), torch.zeros(lay.total - lay.live)]))
+    GP.tensor_errors(lay, gv, GP.oracle_step_grads(P, batch, 12), grads, 2e-4, what="fp32 B = 512, RnC over 1024 rows")
 
 
 def test_bf16_operand_mode_c3(E):
