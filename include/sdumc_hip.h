@@ -1250,6 +1250,44 @@ int sdumc_net_backward_phase(const sdumc_net_dims* d, const sdumc_net_io* io, co
                              void* stream);
 int64_t sdumc_param_early_count(int32_t da, int32_t dt, int32_t dv);
 
+/* Per-frame saliency of a completed feature-gradient backward, in STORE order (csrc/frame_saliency.hip): what a gradient-based
+ * attribution of model.eval() (model :282-284 through :364) reduces sdumc_net_grads.d_audio / d_text / d_video to.  For a
+ * descriptor's sample b < B and frame t < length[idx[b]] (and t < T), with g = grad[b, t, :] and x = that frame's feature row, row
+ * start[idx[b]] + t of dst receives
+ *   column 0   sum_c g[c] x[c]        (gradient x input, signed)
+ *   column 1   sqrt(sum_c g[c]^2)     (gradient norm)
+ * x is feat[b, t, :] of a padded [B, T, d] tensor, or -- with row_map, the int32 [B T] map the forward read the batch through
+ * (sdumc_net_io.row_map) -- row row_map[b T + t] of the store's packed [store_rows, d] tensor; a map entry outside [0, store_rows)
+ * is a zero row and is never read.  Frames t >= length are not written; rows of utterances not in the batch are not touched; an idx
+ * outside [0, n_utt) or a destination row outside [0, dst_rows) is skipped, never written.
+ * ONE launch for up to SDUMC_SALIENCY_MAX_DESCS descriptors (normally the three modalities of one stream) that share the batch's
+ * index vector idx (device int64 [B]; every descriptor has the same B).
+ * Arithmetic: the products of the fp32 values are formed in fp64 (exact there); every lane of the row's wave adds its strided
+ * chunks (16 bytes when d % 4 == 0, one float otherwise) in index order into two fp64 accumulators; the 64 lanes combine in a fixed
+ * butterfly; one fp64 square root for column 1; one rounding to fp32 per column; one 8-byte store per row.  No atomics, no state
+ * between launches: a repeated launch gives the same bits, and the order of a row's sum depends on d alone -- the same grad and feat
+ * rows give the same bits whatever batch, B, T or batch position they came in.  NaN / Inf in a row propagate to that row's two
+ * values, and only to those.  One 64-lane wave per padded frame row on a capped grid, 64-bit element offsets, plain vector loads
+ * and stores, no LDS.  Stream-ordered behind the backward that wrote grad; no host synchronisation.
+ * SDUMC_EINVAL, before anything is launched: descs or idx NULL; n outside 1 .. SDUMC_SALIENCY_MAX_DESCS; a descriptor with grad,
+ * feat, start, length or dst NULL, with B, T, d, n_utt or dst_rows < 1, with a B other than the first descriptor's, with a row_map
+ * and store_rows < 1, with grad or dst not 16-byte aligned, or with feat not 16-byte aligned while d % 4 == 0; more than 2^31 - 1
+ * padded rows in all. */
+#define SDUMC_SALIENCY_MAX_DESCS 4
+typedef struct sdumc_saliency_desc {
+  const float* grad;         /* [B, T, d] fp32: the d_feat tensor the backward wrote; 16-byte aligned */
+  const float* feat;         /* the features the forward read: padded [B, T, d], or with row_map the packed [store_rows, d] rows */
+  const int32_t* row_map;    /* device int32 [B T], or NULL */
+  int64_t store_rows;        /* rows of the packed tensor (read with row_map only) */
+  const int64_t* start;      /* store-wide table, device [n_utt]: first packed row of every utterance of this modality */
+  const int32_t* length;     /* store-wide table, device [n_utt]: frames of every utterance */
+  int64_t n_utt;
+  float* dst;                /* [dst_rows, 2] fp32, 16-byte aligned */
+  int64_t dst_rows;          /* packed rows of that modality in the store (without the trailing zero row) */
+  int32_t B, T, d;
+} sdumc_saliency_desc;
+int sdumc_frame_saliency(const sdumc_saliency_desc* descs, int32_t n, const int64_t* idx, void* stream);
+
 /* Two-stream self-distillation step (main :119-150). */
 typedef struct sdumc_step_cfg {
   float weights[6];      /* full_mse, missing_mse, text_feat, text_query_feat, features, rnc (main :234-239) */

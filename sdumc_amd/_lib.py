@@ -290,6 +290,16 @@ class AttnExport(C.Structure):      # sdumc_attn_export: a completed eval-mode f
                 ("dst", (C.c_void_p * 3) * 2), ("dst_rows", (C.c_int64 * 3) * 2)]
 
 
+SALIENCY_MAX_DESCS = 4
+SALIENCY_COLS = 2
+
+
+class SaliencyDesc(C.Structure):    # sdumc_saliency_desc: one modality's feature gradient x features -> a store-ordered [rows, 2] tensor
+    _fields_ = [("grad", C.c_void_p), ("feat", C.c_void_p), ("row_map", C.c_void_p), ("store_rows", C.c_int64),
+                ("start", C.c_void_p), ("length", C.c_void_p), ("n_utt", C.c_int64), ("dst", C.c_void_p), ("dst_rows", C.c_int64),
+                ("B", C.c_int32), ("T", C.c_int32), ("d", C.c_int32)]
+
+
 ADAM_MAX_SEGS = 96
 
 
@@ -435,6 +445,7 @@ _SIGS = {
     "sdumc_net_backward": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(NetGrads), C.c_void_p]),
     "sdumc_net_backward_phase": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(NetGrads), C.c_int32, C.c_void_p]),
     "sdumc_param_early_count": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "sdumc_frame_saliency": (C.c_int, [C.POINTER(SaliencyDesc), C.c_int32, C.c_void_p, C.c_void_p]),
     "sdumc_net_feature_grad_scratch_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_step_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_train_step": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(StepCfg), C.c_void_p]),

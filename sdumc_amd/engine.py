@@ -981,6 +981,18 @@ class FusedTrainer:
                                         prefetch_workgroups=kw["prefetch_workgroups"])
         return self._evaluator.eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out, attention=attention)
 
+    def saliency_epoch(self, store, batches, key_padding=False, streams=("full", "missing"), out=None):
+        """One saliency pass (saliency.saliency_epoch has the semantics) over `batches` of `store` with the trainer's parameters and its
+        inplace / planes choices -> saliency.SaliencyResult in store order: per stream and modality the gradient x input and the gradient
+        norm of the eval-mode prediction per frame.  Like eval_epoch it owns its memory (saliency.Saliency, made on first use and
+        kept) and only reads the parameters.  fp32 storage only: a bf16-storage trainer raises."""
+        if getattr(self, "_saliency", None) is None:
+            from .saliency import Saliency
+            kw = self._arena_kw
+            self._saliency = Saliency(self.params, self.dims, bf16=kw["bf16"], inplace=self.inplace, planes=kw["planes"],
+                                      prefetch_workgroups=kw["prefetch_workgroups"])
+        return self._saliency.saliency_epoch(store, batches, key_padding=key_padding, streams=streams, out=out)
+
     def step(self, audio, text, video, feat4, labels, lengths=None):
         """One optimisation step on one batch of any shape; returns the device loss vector
         [total, mse_full, mse_missing, rmse_text, rmse_query, rmse_fused, rnc, 0]."""
