@@ -959,6 +959,38 @@ typedef struct sdumc_epoch_rec {
 } sdumc_epoch_rec;
 size_t sdumc_epoch_record_scratch_bytes(int64_t n_grads);
 int sdumc_epoch_record(const sdumc_epoch_rec* r, void* stream);
+/* The same reduce BY TENSOR: the L2 norm and the non-finite count of each of n (1 .. SDUMC_TENSOR_NORMS_MAX_SEGS) segments of fp32
+ * device memory in two launches, stream-ordered, no host synchronisation.  What a training epoch keeps per step beside the one norm
+ * of the whole bucket -- the gradient bucket cut at the parameter table's offsets, and the flat parameters against a snapshot of
+ * their values before the step -- and what a loop over per-parameter .grad tensors asks for.  segs is a HOST table, read by the call.
+ * Per segment t:
+ *   norm[t]       fp32 of sqrt(sum_i x[i]^2)
+ *   nonfinite[t]  the number of x[i] that are NaN or +-Inf (saturating at 2^31 - 1)
+ *   y != NULL:    diff_norm[t] = fp32 of sqrt(sum_i (x[i] - y[i])^2), and then y[i] = x[i], in the same pass over the data: the
+ *                 rolling snapshot (after the call y equals x bit for bit, so a second call gives 0).  x and y must not overlap.
+ *   y == NULL (or count == 0): diff_norm[t] is left as it is; diff_norm may be NULL when no segment has a y.
+ * count == 0 gives norm 0, nonfinite 0.  Differences, squares and sums are fp64 (a sum of fp32 squares cannot overflow there), rounded
+ * ONCE to fp32 -- a norm beyond the fp32 range comes out as +Inf; NaN and +-Inf elements propagate as in torch.linalg.vector_norm.
+ * Fixed order: the call cuts every segment into chunks by its count alone (8192 floats, at most 1024 chunks per segment, longer
+ * chunks beyond that; a chunk never spans two segments), one workgroup folds a chunk in a fixed lane order into fp64 partials in
+ * scratch, and the second launch adds each segment's partials in index order: the same input gives the same bits on every call,
+ * wherever the segments lie.  No atomics.  Nothing but 4-byte alignment is assumed of x and y: 16-byte loads from a chunk's first
+ * aligned element on (with a y, where x and y sit alike within 16 bytes; else that segment goes one float per lane), single
+ * elements in front and behind.  norm / nonfinite / diff_norm name n consecutive elements, e.g. one row of a [steps, n] tensor.
+ * scratch: caller-owned device memory of at least the scratch query's bytes for the same table (it depends on n and the counts
+ * only; 0 = a table the entry refuses), 16-byte aligned; every call writes what it reads of it; one call at a time per scratch.
+ * SDUMC_EINVAL, before anything is launched: segs NULL or not 8-byte aligned, n < 1 or > SDUMC_TENSOR_NORMS_MAX_SEGS, a negative
+ * count, x NULL with count > 0, x or y not 4-byte aligned, norm / nonfinite NULL, diff_norm NULL while a segment has a y, an output
+ * not 4-byte aligned, scratch NULL or not 16-byte aligned, scratch_bytes short. */
+#define SDUMC_TENSOR_NORMS_MAX_SEGS 96
+typedef struct sdumc_norm_seg {
+  const float* x;
+  float* y;              /* optional: the snapshot */
+  int64_t count;         /* floats */
+} sdumc_norm_seg;
+size_t sdumc_tensor_norms_scratch_bytes(const sdumc_norm_seg* segs, int32_t n);
+int sdumc_tensor_norms(const sdumc_norm_seg* segs, int32_t n, float* norm, int32_t* nonfinite, float* diff_norm, void* scratch,
+                       size_t scratch_bytes, void* stream);
 /* dst[r, 0:cols] = src[r, 0:cols] for r < rows, with leading dimensions */
 /* dst[r, 0:cols] += src[r, 0:cols] */
 int sdumc_axpy2d(const float* src, int32_t ld_src, float* dst, int32_t ld_dst, int32_t rows, int32_t cols, void* stream);

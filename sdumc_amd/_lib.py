@@ -285,6 +285,13 @@ class EpochRec(C.Structure):        # sdumc_epoch_rec: a completed train step's 
                 ("grads", C.c_void_p), ("n_grads", C.c_int64), ("scratch", C.c_void_p)]
 
 
+TENSOR_NORMS_MAX_SEGS = 96
+
+
+class NormSeg(C.Structure):         # sdumc_norm_seg: one tensor of sdumc_tensor_norms (y: the optional rolling snapshot)
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("count", C.c_int64)]
+
+
 class AttnExport(C.Structure):      # sdumc_attn_export: a completed eval-mode forward's attention weights -> store-ordered [rows, 8] tensors
     _fields_ = [("idx", C.c_void_p), ("start", C.c_void_p * 4), ("length", C.c_void_p * 4), ("n_utt", C.c_int64),
                 ("dst", (C.c_void_p * 3) * 2), ("dst_rows", (C.c_int64 * 3) * 2)]
@@ -317,6 +324,9 @@ _SIGS = {
     "sdumc_scatter_rows_multi": (C.c_int, [C.POINTER(ScatterSeg), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sdumc_epoch_record_scratch_bytes": (C.c_size_t, [C.c_int64]),
     "sdumc_epoch_record": (C.c_int, [C.POINTER(EpochRec), C.c_void_p]),
+    "sdumc_tensor_norms_scratch_bytes": (C.c_size_t, [C.POINTER(NormSeg), C.c_int32]),
+    "sdumc_tensor_norms": (C.c_int, [C.POINTER(NormSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     "sdumc_profile_enable": (C.c_int, [C.c_int]),
     "sdumc_profile_report": (C.c_int, [C.POINTER(ProfEntry), C.c_int]),
     "sdumc_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(Gemm)]),

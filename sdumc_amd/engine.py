@@ -916,27 +916,53 @@ class FusedTrainer:
         self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers)
         return n
 
-    def train_epoch(self, store, batches, key_padding=False, on_step=None, embeddings=False, grad_norm=False, out=None):
+    def train_epoch(self, store, batches, key_padding=False, on_step=None, embeddings=False, grad_norm=False, out=None, by_tensor=False):
         """run_epoch with the epoch's record kept -> record.TrainRecord: what the reference's training pass returns (main :156-178: the
         train-mode predictions of both streams in store order and their MSE; embeddings=True: the four embeddings too) and a log row
         per step (the loss vector, B, the learning rate; grad_norm=True: the L2 norm of the step's raw gradient bucket -- without
         Adam's coupled L2 term -- and its number of non-finite elements).  The same launches as run_epoch plus one per step, two with
         grad_norm (sdumc_epoch_record), which only read what the step left: parameters, moments and dropout counter are those of run_epoch.
         The epoch must not visit an utterance twice (checked on the host before anything is enqueued; `out` is untouched if it
-        does).  out= reuses a record (TrainRecord.fits: this store, at least this many steps, the same options)."""
+        does).  out= reuses a record (TrainRecord.fits: this store, at least this many steps, the same options).
+        by_tensor=True: one more call per step (sdumc_tensor_norms, two launches) cuts the same raw bucket at ParamLayout's offsets ->
+        rec.by_tensor (record.TensorNorms): every live tensor's gradient norm and non-finite count per step.  by_tensor='updates': a
+        second such call over the flat parameters against a snapshot the record owns (one device copy in front of the first step) adds
+        each tensor's weight norm after the step and the norm of the step's actual update.  Both only read what the step left."""
         self._need_sets("train_epoch")
         from .evaluate import checked_plan
-        from .record import TrainRecord
+        from .record import NormTable, TrainRecord, by_tensor_mode
+        by_tensor = by_tensor_mode(by_tensor)
         dev, n_store = self.params.device, len(store)
         plan, batches = checked_plan(batches, n_store)
         n = len(plan if plan is not None else batches)
-        n_grads = ParamLayout.get(*self.dims[:3]).live if grad_norm else 0
-        if out is not None and not (isinstance(out, TrainRecord) and out.fits(n_store, n, dev, embeddings, n_grads)):
+        lay = ParamLayout.get(*self.dims[:3])
+        n_grads = lay.live if grad_norm else 0
+        if out is not None and not (isinstance(out, TrainRecord) and out.fits(n_store, n, dev, embeddings, n_grads, by_tensor, lay)):
             raise _lib.SdumcError("train_epoch: out= is not a record of this store's size and device, these many steps and these options")
         if plan is None:
             plan = store.plan_epoch(batches)
-        rec = (out if out is not None else TrainRecord.empty(n_store, n, dev, embeddings, n_grads)).reset()
+        rec = (out if out is not None else TrainRecord.empty(n_store, n, dev, embeddings, n_grads, by_tensor, lay)).reset()
         descs, st = {}, _lib.current_stream()
+        bt, tables = rec.by_tensor, {}
+        if by_tensor == "updates":
+            # the snapshot: the view of the record's buffer that sits like the parameters within 16 bytes (16-byte loads of both),
+            # filled once here; every step's call then rolls it forward itself
+            k = ((self.params.data_ptr() - bt.snapshot.data_ptr()) >> 2) & 3
+            snap = bt.snapshot[k:k + lay.live]
+            snap.copy_(self.params[:lay.live])
+            base = self.params.data_ptr()
+            tables["params"] = NormTable((base + 4 * o, snap.data_ptr() + 4 * o, c) for o, c in zip(bt.offsets, bt.counts))
+
+        def record_by_tensor(i, ts):
+            g = ts.grads.data_ptr()
+            tb = tables.get(g)      # (one bucket per arena: a table per address it has had)
+            if tb is None:
+                tb = tables[g] = NormTable((g + 4 * o, None, c) for o, c in zip(bt.offsets, bt.counts))
+            row = 4 * len(bt.names) * i
+            tb.launch(bt.grad_norm.data_ptr() + row, bt.grad_nonfinite.data_ptr() + row, 0, bt.scratch, st)
+            if by_tensor == "updates":
+                tables["params"].launch(bt.param_norm.data_ptr() + row, bt.param_nonfinite.data_ptr() + row,
+                                        bt.update_norm.data_ptr() + row, bt.scratch, st)
 
         def record(i, ts):
             d = descs.get(ts.B)
@@ -945,6 +971,8 @@ class FusedTrainer:
             r = d[0]
             r.idx, r.log_row = plan.idx_ptr(i), rec.log.data_ptr() + 4 * _lib.LOG_COLS * i
             check(lib.sdumc_epoch_record(C.byref(r), st), "sdumc_epoch_record")
+            if by_tensor:
+                record_by_tensor(i, ts)
 
         rec.steps = self._epoch(store, plan, key_padding, on_step, record)
         return rec
