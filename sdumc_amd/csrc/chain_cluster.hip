@@ -220,22 +220,130 @@ constexpr int FOLD_MAXCHUNK = 32;
 //  slowest member at the first exchange, 29 of stage B forward's 60, 57 of stage A backward's 120 (profiles/r4z_step_marks_fp32.txt);
 //  the in-place normalisation of the stored weights is dealt to the members by ELEMENT range, not by (modality, sample) pair: the
 //  member that drew audio's 375 frames kept the other three waiting at the first exchange)
+// (the fold is cut into a REQUEST half and two later halves, so that a stage head asks for everything whose address it knows at
+//  its first instruction -- chunk statistics, the first batch of partial rows, the stored weights, biases, alpha, the first
+//  layer's weights -- before it waits for any of it; profiles/README.md, "Stage heads".  Three rules keep the requests in flight
+//  together:
+//   * a request is branch-free where something older is still awaited behind it: a thread without a live item re-reads a live
+//     address and drops the value.  Behind a branch around a load the compiler can no longer count the loads in front of a use
+//     and waits for all of them (vmcnt(0));
+//   * modality tables (part, stats, nchunk, T) are read through sel3, a pair of selects: indexed by a per-thread m they are vector
+//     loads from the kernel's argument block, one more dependent round trip in front of every address;
+//   * each arithmetic statement exists once, as in the loops this replaces: the sums run as a two-deep pipeline over (unit, batch of 8 chunks)
+//     items whose first item is requested early, not as a peeled first pass.)
+template <class T>
+__device__ __forceinline__ T sel3v(T t0, T t1, T t2, int m) { return m == 0 ? t0 : (m == 1 ? t1 : t2); }
+// (the three VALUES are passed, not a reference to the table: a select between addresses inside the argument block made the compiler
+//  keep a copy of the whole block in scratch memory -- 1336 bytes per thread, every pointer then a flat one)
+#define sel3(t, m) sel3v((t)[0], (t)[1], (t)[2], m)
+
+// A thread's share of a sum over chunks: output units u = tid, tid + NTHR, .. < NU (four columns of one row), per unit the rows of
+// its nc chunks, STRIDE floats apart, in batches of 8.  desc(u, src, nc): chunk 0's address of a unit < NU (a live address also for
+// a row beyond V) and its chunk count (0: row beyond V).
+struct ChunkItem {
+  const float* src;
+  int u, c0, nc;      // unit, first chunk of the batch, chunks of the unit; nc < 0: the thread has no such item
+};
+template <int NU, class Desc>
+__device__ __forceinline__ ChunkItem chunk_item(int u, int c0, Desc& desc) {
+  ChunkItem it;
+  it.u = u;
+  it.c0 = c0;
+  desc(min(u, NU - 1), it.src, it.nc);
+  if (u >= NU) it.nc = -1;
+  return it;
+}
+// (only the chunks that exist are requested: a 16-byte load per lane that is dropped afterwards still takes its turn in the
+//  texture path, and at C2 the text and video rows have one or two chunks of the eight.  These loads ARE behind branches: what is
+//  waited for with them in flight has to be complete before -- chunk_drain's rows are, its copy at the end of a round waits)
+template <int STRIDE>
+__device__ __forceinline__ void chunk_request(const ChunkItem& it, f32x4 (&pv)[8]) {
+  static_for<8>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    if (it.c0 + j < it.nc) pv[j] = ld4(it.src + (size_t)(it.c0 + j) * STRIDE);
+  });
+}
+// cur's rows have been requested into pa.  acc(sum, row, u, c) adds chunk c (ascending); fin(u, sum) takes a unit's finished sum.
+template <int NU, int STRIDE, class Desc, class Acc, class Fin>
+__device__ __forceinline__ void chunk_drain(ChunkItem cur, f32x4 (&pa)[8], Desc& desc, Acc&& acc, Fin&& fin) {
+  f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+  while (cur.nc >= 0) {
+    const bool more = cur.c0 + 8 < cur.nc;
+    const ChunkItem nx = chunk_item<NU>(more ? cur.u : cur.u + NTHR, more ? cur.c0 + 8 : 0, desc);
+    f32x4 pb[8];
+    chunk_request<STRIDE>(nx, pb);      // the next item's rows travel under this item's arithmetic
+    if (cur.c0 == 0) sum = f32x4{0.f, 0.f, 0.f, 0.f};
+    static_for<8>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      if (cur.c0 + j < cur.nc) acc(sum, pa[j], cur.u, cur.c0 + j);
+    });
+    if (!more) fin(cur.u, sum);
+    cur = nx;
+    static_for<8>([&](auto jc) { pa[decltype(jc)::value] = pb[decltype(jc)::value]; });
+  }
+}
+
 template <int R, int NQT>
-__device__ __forceinline__ void fold_combine(const sdumc_chain_fold& f, float* out, float* s_rows, float* s_fac, const int v0, const int V,
-                                             const int member, const DropRT& dbase) {
+struct FoldHead {
+  static constexpr int NS = 3 * R * NQT;            // (modality, sample, query) rows: one thread each for the statistics
+  static constexpr int NU = NS * (D / 4);           // units of the pooled rows
+  static_assert(NS <= NTHR, "one statistics row per thread");
+  float cm[8], cs[8];     // chunk maxima and sums of this thread's row (nc <= 8)
+  ChunkItem it;           // the first item of the partial rows ...
+  f32x4 pa[8];            // ... and its rows
+};
+template <int R, int NQT>
+struct FoldDesc {
+  const sdumc_chain_fold& f;
+  int v0, V;
+  __device__ __forceinline__ void operator()(int u, const float*& src, int& nc) const {
+    const int row = u / (D / 4), cq = u - row * (D / 4);         // row = (m R + r) NQT + i
+    const int mr = row / NQT, i = row - mr * NQT;
+    const int m = mr / R, v = v0 + (mr - m * R);
+    const int ncm = sel3(f.nchunk, m);
+    src = sel3(f.part, m) + ((size_t)min(v, V - 1) * ncm * NQT + i) * D + 4 * cq;
+    nc = v < V ? ncm : 0;
+  }
+};
+
+// the request half: chunk statistics (nc <= 8) and the first batch of partial rows
+template <int R, int NQT>
+__device__ __forceinline__ void fold_request(FoldHead<R, NQT>& h, const sdumc_chain_fold& f, const int v0, const int V) {
+  using FH = FoldHead<R, NQT>;
+  const int u = min((int)threadIdx.x, FH::NS - 1);
+  const int mr = u / NQT, i = u - mr * NQT;
+  const int m = mr / R, v = min(v0 + (mr - m * R), V - 1);
+  const int nc = sel3(f.nchunk, m);
+  const float* st = sel3(f.stats, m) + (size_t)v * nc * 16 + i;
+  static_for<8>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    const int k = min(c, nc - 1);
+    h.cm[c] = st[k * 16];
+    h.cs[c] = st[k * 16 + 8];
+  });
+  FoldDesc<R, NQT> desc{f, v0, V};
+  h.it = chunk_item<FH::NU>(threadIdx.x, 0, desc);
+  chunk_request<NQT * D>(h.it, h.pa);
+}
+
+// the second half: s_fac, the barrier that publishes it, the pooled rows
+template <int R, int NQT>
+__device__ __forceinline__ void fold_combine(FoldHead<R, NQT>& h, const sdumc_chain_fold& f, float* out, float* s_rows, float* s_fac, const int v0,
+                                             const int V, const int member, const DropRT& dbase) {
+  using FH = FoldHead<R, NQT>;
   const int tid = threadIdx.x;
-  for (int u = tid; u < 3 * R * NQT; u += NTHR) {
+  if (tid < FH::NS) {
+    const int u = tid;
     const int mr = u / NQT, i = u - mr * NQT;
     const int m = mr / R, v = v0 + (mr - m * R);
     if (v < V) {
-      const int nc = f.nchunk[m];
-      const float* st = f.stats[m] + (size_t)v * nc * 16 + i;
-      if (nc <= 8) {      // the chunk statistics of a row in registers: 16 independent loads
+      const int nc = sel3(f.nchunk, m);
+      if (nc <= 8) {      // the chunk statistics of a row in registers: 16 independent loads, requested by fold_request
         float cm[8], cs[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          cm[c] = c < nc ? st[c * 16] : -INFINITY;
-          cs[c] = c < nc ? st[c * 16 + 8] : 0.f;
+          cm[c] = c < nc ? h.cm[c] : -INFINITY;
+          cs[c] = c < nc ? h.cs[c] : 0.f;
         }
         float mx = -INFINITY;
 #pragma unroll
@@ -249,6 +357,7 @@ __device__ __forceinline__ void fold_combine(const sdumc_chain_fold& f, float* o
         for (int c = 0; c < 8; ++c)
           if (c < nc) s_fac[(mr * FOLD_MAXCHUNK + c) * 8 + i] = expf(cm[c] - mx) * inv;
       } else {
+        const float* st = sel3(f.stats, m) + (size_t)v * nc * 16 + i;
         float mx = -INFINITY;
         for (int c = 0; c < nc; ++c) mx = fmaxf(mx, st[c * 16]);
         float l = 0.f;
@@ -258,66 +367,94 @@ __device__ __forceinline__ void fold_combine(const sdumc_chain_fold& f, float* o
       }
     }
   }
-  __syncthreads();
-  for (int u = tid; u < 3 * R * NQT * (D / 4); u += NTHR) {
-    const int row = u / (D / 4), cq = u - row * (D / 4);         // row = (m R + r) NQT + i
-    const int mr = row / NQT, i = row - mr * NQT;
-    const int m = mr / R, v = v0 + (mr - m * R);
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-    if (v < V) {
-      const int nc = f.nchunk[m];
-      const float* src = f.part[m] + ((size_t)v * nc * NQT + i) * D + 4 * cq;
-      const float* fac = s_fac + (mr * FOLD_MAXCHUNK) * 8 + i;
-      f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-      for (int c0 = 0; c0 < nc; c0 += 8) {      // eight chunks' rows in flight, summed in ascending c
-        f32x4 pv[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (c0 + j < nc) pv[j] = ld4(src + (size_t)(c0 + j) * NQT * D);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (c0 + j < nc) sum += pv[j] * fac[(c0 + j) * 8];
-      }
-      o = sum;
-      if (dbase.enabled) {
-        DropRT od = mkdrop_rt(dbase, (uint32_t)f.site[m], NQT, D);
-        od.threshold = f.threshold;
-        od.scale = f.scale;
-        o *= drop_mask4(od, (uint32_t)(v * NQT + i), (uint32_t)cq);
-      }
-      if ((mr & (CL - 1)) == member) {
-        st4(f.pooled[m] + ((size_t)v * NQT + i) * D + 4 * cq, sum);
-        st4(out + (((size_t)m * V + v) * NQT + i) * D + 4 * cq, o);
-      }
-    }
-    st4(s_rows + (size_t)row * D + 4 * cq, o);
-  }
-  // stored weights *= fac: every (modality, sample) row range is cut into CL equal parts, one per member; four elements per thread in flight
+  __syncthreads();      // (the partial rows requested by fold_request stay in flight across it)
+  FoldDesc<R, NQT> desc{f, v0, V};
+  chunk_drain<FH::NU, NQT * D>(
+      h.it, h.pa, desc,
+      [&](f32x4& sum, const f32x4 pv, int u, int c) {
+        const int row = u / (D / 4), mr = row / NQT, i = row - mr * NQT;
+        sum += pv * s_fac[(mr * FOLD_MAXCHUNK + c) * 8 + i];
+      },
+      [&](int u, const f32x4 sum) {
+        const int row = u / (D / 4), cq = u - row * (D / 4);
+        const int mr = row / NQT, i = row - mr * NQT;
+        const int m = mr / R, v = v0 + (mr - m * R);
+        f32x4 o = sum;      // (zero for a row beyond V)
+        if (v < V) {
+          if (dbase.enabled) {
+            DropRT od = mkdrop_rt(dbase, (uint32_t)sel3(f.site, m), NQT, D);
+            od.threshold = f.threshold;
+            od.scale = f.scale;
+            o *= drop_mask4(od, (uint32_t)(v * NQT + i), (uint32_t)cq);
+          }
+          if ((mr & (CL - 1)) == member) {
+            st4(sel3(f.pooled, m) + ((size_t)v * NQT + i) * D + 4 * cq, sum);
+            st4(out + (((size_t)m * V + v) * NQT + i) * D + 4 * cq, o);
+          }
+        }
+        st4(s_rows + (size_t)row * D + 4 * cq, o);
+      });
+}
+
+// stored weights *= fac, in place: every (modality, sample) row range is cut into CL equal parts, one per member, and a member walks
+// its part in rounds of NTHR elements.  Nothing in the launch reads the weights (the pooling backward and the exports do), so the
+// first KR rounds of every pair -- all of them up to T = 2048 at the FRA2UTT sites and T = 585 at the Cross_Attention sites -- are
+// requested with the head's other loads (fold_norm_request), wait in registers, and are scaled and stored behind the first layer
+// group (fold_norm_finish), off the path to the first layer; later rounds are loaded there.  Pair and round of a register are
+// compile-time constants: the element's address and factor cost a handful of instructions.
+// (The request is not issued behind the input rows, under the layers: the layer loop's waits for its weights are counted for the
+//  loop's later rounds, where the weights are the youngest loads, and in its first round they would wait for anything younger too.)
+// fold_norm_finish reads s_fac: before its host buffer is reused.
+template <int R, int NQT>
+struct FoldNorm {
+  static constexpr int KR = NQT == 1 ? 1 : 2;
+  float wv[3 * R * KR];      // [round][pair]
+};
+struct NormSlot {
+  float* p;       // the element (a live one also for a dead slot)
+  int fac;        // its factor's index in s_fac
+  bool live;
+};
+template <int R, int NQT>
+__device__ __forceinline__ NormSlot fold_norm_slot(const sdumc_chain_fold& f, int mr, int k, int v0, int V, int member) {
+  const int m = mr / R, v = v0 + (mr - m * R);
+  const int n = sel3(f.T, m) * NQT, per = (n + CL - 1) / CL;
+  const int e0 = member * per, e1 = min(n, e0 + per);
+  const int e = e0 + (int)threadIdx.x + k * NTHR, ec = min(e, n - 1);
+  const int t = ec / NQT, i = ec - t * NQT;
+  NormSlot o;
+  o.p = sel3(f.attn, m) + (size_t)min(v, V - 1) * n + ec;
+  o.fac = (mr * FOLD_MAXCHUNK + (t >> 6)) * 8 + i;
+  o.live = v < V && e < e1;
+  return o;
+}
+template <int R, int NQT>
+__device__ __forceinline__ void fold_norm_request(FoldNorm<R, NQT>& g, const sdumc_chain_fold& f, int v0, int V, int member) {
+  static_for<3 * R * FoldNorm<R, NQT>::KR>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    g.wv[s] = *fold_norm_slot<R, NQT>(f, s % (3 * R), s / (3 * R), v0, V, member).p;
+  });
+}
+template <int R, int NQT>
+__device__ __forceinline__ void fold_norm_finish(const FoldNorm<R, NQT>& g, const sdumc_chain_fold& f, const float* s_fac, int v0, int V, int member) {
 #if defined(SDUMC_FOLD_DBG)
   if (SDUMC_FOLD_DBG & 1) return;
 #endif
-  for (int mr = 0; mr < 3 * R; ++mr) {
-    const int m = mr / R, v = v0 + (mr - m * R);
-    if (v >= V) continue;
-    const int n = f.T[m] * NQT, per = (n + CL - 1) / CL;
-    const int e0 = member * per, e1 = min(n, e0 + per);
-    float* w = f.attn[m] + (size_t)v * n;
-    const float* fac = s_fac + (mr * FOLD_MAXCHUNK) * 8;
-    for (int e = e0 + tid; e < e1; e += 4 * NTHR) {
-      float wv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (e + j * NTHR < e1) wv[j] = w[e + j * NTHR];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int ee = e + j * NTHR;
-        if (ee < e1) {
-          const int t = ee / NQT, i = ee - t * NQT;
-          w[ee] = wv[j] * fac[(t >> 6) * 8 + i];
-        }
-      }
+  constexpr int KR = FoldNorm<R, NQT>::KR;
+  static_for<3 * R * KR>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    const NormSlot sl = fold_norm_slot<R, NQT>(f, s % (3 * R), s / (3 * R), v0, V, member);
+    if (sl.live) *sl.p = g.wv[s] * s_fac[sl.fac];
+  });
+  const int tmax = max(f.T[0], max(f.T[1], f.T[2]));
+  const int kp = ((tmax * NQT + CL - 1) / CL + NTHR - 1) / NTHR;
+#pragma unroll 1
+  for (int k = KR; k < kp; ++k)
+#pragma unroll 1
+    for (int mr = 0; mr < 3 * R; ++mr) {
+      const NormSlot sl = fold_norm_slot<R, NQT>(f, mr, k, v0, V, member);
+      if (sl.live) *sl.p = *sl.p * s_fac[sl.fac];
     }
-  }
 }
 
 // diagnosis (cl_mode bit 6): the LDS copy of the stage's input rows against global memory (the inputs are final before the launch)
@@ -432,7 +569,18 @@ __device__ __forceinline__ void chain_fwd_a_cl_body(const sdumc_chain_args a, co
   CL_PROLOGUE();
   TR(0);
   const int64_t VD = (int64_t)V * D;
-  fwd_a_stage_bias(a, s_bias);
+  const bool fold = a.fra.part[0] != nullptr;
+  // the head: every request whose address is known here goes out before the first wait -- the fold's statistics and first partial
+  // rows, the biases, the first layer's weights -- and is consumed in that order
+  FoldHead<R, 1> fh;
+  FoldNorm<R, 1> fn;
+  if (fold) {
+    fold_request<R, 1>(fh, a.fra, v0, V);
+    fold_norm_request<R, 1>(fn, a.fra, v0, V, member);
+  }
+  constexpr int NBIAS = (FWD_A_BIAS_UNITS + NTHR - 1) / NTHR;
+  f32x4 bias[NBIAS];
+  static_for<NBIAS>([&](auto kc) { bias[decltype(kc)::value] = ld4(fwd_a_bias_src(a, min(tid + decltype(kc)::value * NTHR, FWD_A_BIAS_UNITS - 1))); });
   const DropRT dbase = drop_resolve(a.drop);
   CRing ring;
   if (a.cl_mode & 2) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -441,8 +589,12 @@ __device__ __forceinline__ void chain_fwd_a_cl_body(const sdumc_chain_args a, co
   PF(D, OC, a.umlp0_w[0] + coff, D);
   if (a.cl_mode & 16) cxm_selfcheck<D, OC, 1>(ring, a.umlp0_w[0] + coff, D, a.cl_dbg);
   // the FRA2UTT sites' combine (three launches, 31-39 us each inside the step, on every modality lane's way to this stage) rides here
-  if (a.fra.part[0]) fold_combine<R, 1>(a.fra, a.hpre, s_hpre, s_qin, v0, V, member, dbase);      // (s_qin: free until the fusion algebra)
+  if (fold) fold_combine<R, 1>(fh, a.fra, a.hpre, s_hpre, s_qin, v0, V, member, dbase);      // (s_qin: free until the fusion algebra)
   else for (int m = 0; m < 3; ++m) load_rows<R>(s_hpre + m * R * D, a.hpre + m * VD, D, D, v0, V);
+  static_for<NBIAS>([&](auto kc) {
+    const int u = tid + decltype(kc)::value * NTHR;
+    if (u < FWD_A_BIAS_UNITS) st4(s_bias + 4 * u, bias[decltype(kc)::value]);
+  });
   __syncthreads();
   TR(11);
   if ((a.cl_mode & 64) && !a.fra.part[0])
@@ -459,6 +611,7 @@ __device__ __forceinline__ void chain_fwd_a_cl_body(const sdumc_chain_args a, co
     cxm_run<R, D, OC>(ring, s_hpre + m * R * D, D, a.umlp0_w[m] + coff, D, part, epi,
                                 [&] { PF(D, OC, (m < 2 ? a.umlp0_w[m + 1] : a.umlp3_w[0]) + coff, D); });
   }
+  if (fold) fold_norm_finish<R, 1>(fn, a.fra, s_qin, v0, V, member);      // the stored weights' normalisation, requested in the head
   TR(1);
   if ((a.cl_mode & 64) && !a.fra.part[0])       // ... and again after the three layers that read it
     for (int m = 0; m < 3; ++m) lds_selfcheck<R>(s_hpre + m * R * D, a.hpre + m * VD, D, v0, V, a.cl_dbg, 20 + m);
@@ -567,14 +720,25 @@ __device__ __forceinline__ void chain_fwd_b_cl_body(const sdumc_chain_args a, co
   TR(0);
   const int64_t VQ = (int64_t)V * NQ;
   const int hoff = member * HC;
-  fwd_b_stage_bias(a, s_bias);
+  const bool fold = a.ca.part[0] != nullptr;
+  // the head, as stage A forward's: one batch of requests, consumed in the order they went out
+  FoldHead<R, NQ> fh;
+  FoldNorm<R, NQ> fn;
+  if (fold) {
+    fold_request<R, NQ>(fh, a.ca, v0, V);
+    fold_norm_request<R, NQ>(fn, a.ca, v0, V, member);
+  }
+  static_assert(FWD_B_BIAS_UNITS <= NTHR, "one bias unit per thread");
+  const f32x4 bias = ld4(fwd_b_bias_src(a, min(tid, FWD_B_BIAS_UNITS - 1)));
+  const float al = alpha_request<R>(a.alpha, v0, V);
   const DropRT dbase = drop_resolve(a.drop);
   CRing ring;
   PF14(D, OC, a.cmlp0_w[0] + coff, D);
-  fwd_b_load_alpha<L>(a, sm, v0, V);
   // the Cross_Attention sites' combine (one grouped launch between the pooling and this stage) rides here
-  if (a.ca.part[0]) fold_combine<R, NQ>(a.ca, a.ca_out, s_x, s_c, v0, V, member, dbase);      // (s_c: first written by cross_*_mlp.3)
+  if (fold) fold_combine<R, NQ>(fh, a.ca, a.ca_out, s_x, s_c, v0, V, member, dbase);      // (s_c: first written by cross_*_mlp.3)
   else for (int m = 0; m < 3; ++m) load_rows<NQ * R>(s_x + m * NQ * R * D, a.ca_out + (int64_t)m * VQ * D, D, D, v0 * NQ, V * NQ);
+  if (tid < FWD_B_BIAS_UNITS) st4(s_bias + 4 * tid, bias);
+  alpha_store<R>(al, sm + L::alpha, v0, V);
   __syncthreads();
   TR(11);
   // cross_{audio,text,video}_mlp (model :338-340), rows = (sample, query)
@@ -591,6 +755,7 @@ __device__ __forceinline__ void chain_fwd_b_cl_body(const sdumc_chain_args a, co
       else PF14(D, HC, a.cmlp3_w[0] + hoff, H);
     });
   }
+  if (fold) fold_norm_finish<R, NQ>(fn, a.ca, s_c, v0, V, member);      // the stored weights' normalisation, requested in the head
   TR(1);
   cl_sync(cl, &s_bail);
   TR(2);
@@ -673,10 +838,15 @@ __device__ __forceinline__ void chain_bwd_b_cl_body(const sdumc_chain_args a, co
   const float sc = a.relu_scale;
   const bool wr = member == 0;
 
+  // the head: the saved activations of the whole stage as one batch of requests, one wait
+  BwdBHead<R> hd;
+  RowsReg<NQ * R, D> c1[3];
+  bwd_b_head_request<L>(hd, a, v0, V);
+  static_for<3>([&](auto mc) { rows_request(c1[decltype(mc)::value], a.c1 + (int64_t)decltype(mc)::value * VQ * D, D, v0 * NQ, V * NQ); });
   CRing ring;
   PF(H, OC, a.catt3_w + coff, D);
-  bwd_b_load_head<L>(a, sm, v0, V);
-  for (int m = 0; m < 3; ++m) load_rows<NQ * R>(s_c1 + m * NQ * R * D, a.c1 + (int64_t)m * VQ * D, D, D, v0 * NQ, V * NQ);
+  bwd_b_head_store<L>(hd, a, sm, v0, V);
+  static_for<3>([&](auto mc) { rows_store(c1[decltype(mc)::value], s_c1 + decltype(mc)::value * NQ * R * D, v0 * NQ, V * NQ); });
   __syncthreads();
   bwd_b_rnc<L>(a, sm, v0, V, wr);
   bwd_b_zpool<L>(a, sm, v0, V, wr);
@@ -771,38 +941,52 @@ __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, co
   const float sc = a.relu_scale;
   const bool wr = member == 0;
 
+  // the head: the dq slabs' first batch, alpha / d_alpha and the first layer's weights first -- the query_proj products wait for
+  // them -- and with them the saved activations, which nothing reads before the second exchange: they stay in registers until the
+  // three products are done and go to LDS in front of the first exchange
+  const bool slabs = a.dq_part[0] != nullptr;
+  auto dq_desc = [&](int u, const float*& src, int& nc) {
+    const int row = u / (D / 4), cq = u - row * (D / 4);           // row = (m R + r) NQ + i
+    const int mr = row / NQ, i = row - mr * NQ;
+    const int m = mr / R, v = v0 + (mr - m * R);
+    const int ncm = sel3(a.dq_nchunk, m);
+    src = sel3(a.dq_part, m) + ((size_t)min(v, V - 1) * ncm * NQ + i) * D + 4 * cq;
+    nc = v < V ? ncm : 0;
+  };
+  constexpr int NUX = 3 * R * NQ * (D / 4);
+  ChunkItem it;
+  f32x4 pa[8];
+  RowsReg<NQ * R, D> x[3];
+  if (slabs) {      // the pooling backward's dq reduce (a launch between it and this stage) rides here
+    it = chunk_item<NUX>(tid, 0, dq_desc);
+    chunk_request<NQ * D>(it, pa);
+  } else {
+    static_for<3>([&](auto mc) { rows_request(x[decltype(mc)::value], a.d_qp + (int64_t)decltype(mc)::value * VQ * D, D, v0 * NQ, V * NQ); });
+  }
+  const float al = alpha_request<R>(a.alpha, v0, V), dal = alpha_request<R>(a.d_alpha, v0, V);
   CRing ring;
   PF14(D, OC, a.caq_w[0] + coff, D);
-  load_rows<R>(s_u, a.u, 3 * D, 3 * D, v0, V);
-  load_rows<R>(s_a2, a.att2, D, D, v0, V);
-  load_rows<R>(s_a1, a.att1, D, D, v0, V);
-  for (int m = 0; m < 3; ++m) load_rows<R>(s_u1 + m * R * D, a.u1 + m * VD, D, D, v0, V);
-  if (a.dq_part[0]) {      // the pooling backward's dq reduce (a launch between it and this stage) rides here
-    for (int u = tid; u < 3 * R * NQ * (D / 4); u += NTHR) {
-      const int row = u / (D / 4), cq = u - row * (D / 4);           // row = (m R + r) NQ + i
-      const int mr = row / NQ, i = row - mr * NQ;
-      const int m = mr / R, v = v0 + (mr - m * R);
-      f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-      if (v < V) {
-        const int nc = a.dq_nchunk[m];
-        const float* src = a.dq_part[m] + ((size_t)v * nc * NQ + i) * D + 4 * cq;
-        for (int c0 = 0; c0 < nc; c0 += 8) {      // eight chunks' slabs in flight (one dependent round trip per chunk made this loop 57 us of the stage)
-          f32x4 pv[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (c0 + j < nc) pv[j] = ld4(src + (size_t)(c0 + j) * NQ * D);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (c0 + j < nc) sum += pv[j];      // ascending c, as dq_reduce_multi
-        }
-        if ((mr & (CL - 1)) == member) st4(a.d_qp + (((size_t)m * V + v) * NQ + i) * D + 4 * cq, sum);
-      }
-      st4(s_x + (size_t)row * D + 4 * cq, sum);
-    }
+  RowsReg<R, 3 * D> g_u;
+  RowsReg<R, D> g_a2, g_a1, g_u1[3];
+  rows_request(g_u, a.u, 3 * D, v0, V);
+  rows_request(g_a2, a.att2, D, v0, V);
+  rows_request(g_a1, a.att1, D, v0, V);
+  static_for<3>([&](auto mc) { rows_request(g_u1[decltype(mc)::value], a.u1 + decltype(mc)::value * VD, D, v0, V); });
+  if (slabs) {
+    chunk_drain<NUX, NQ * D>(
+        it, pa, dq_desc, [](f32x4& sum, const f32x4 pv, int, int) { sum += pv; },      // ascending c, as dq_reduce_multi
+        [&](int u, const f32x4 sum) {
+          const int row = u / (D / 4), cq = u - row * (D / 4);
+          const int mr = row / NQ, i = row - mr * NQ;
+          const int m = mr / R, v = v0 + (mr - m * R);
+          if (v < V && (mr & (CL - 1)) == member) st4(a.d_qp + (((size_t)m * V + v) * NQ + i) * D + 4 * cq, sum);
+          st4(s_x + (size_t)row * D + 4 * cq, sum);
+        });
   } else {
-    for (int m = 0; m < 3; ++m) load_rows<NQ * R>(s_x + m * NQ * R * D, a.d_qp + (int64_t)m * VQ * D, D, D, v0 * NQ, V * NQ);
+    static_for<3>([&](auto mc) { rows_store(x[decltype(mc)::value], s_x + decltype(mc)::value * NQ * R * D, v0 * NQ, V * NQ); });
   }
-  bwd_a_load_alpha<L>(a, sm, v0, V);
+  alpha_store<R>(al, sm + L::alpha, v0, V);
+  alpha_store<R>(dal, sm + L::dalpha, v0, V);
   __syncthreads();
   // 7'. query_proj: d_q = sum_m d_qp_m W_q[m]  (this member's columns, accumulated in LDS over the three modalities)
 #pragma unroll 1
@@ -819,6 +1003,10 @@ __device__ __forceinline__ void chain_bwd_a_cl_body(const sdumc_chain_args a, co
   bwd_a_mask_q<L, OC>(a, sm, v0, V, sc, coff, [](f32x4 g, float*, float* hbm, bool live) {
     if (live) st4_dev(hbm, g);
   });
+  rows_store(g_u, s_u, v0, V);
+  rows_store(g_a2, s_a2, v0, V);
+  rows_store(g_a1, s_a1, v0, V);
+  static_for<3>([&](auto mc) { rows_store(g_u1[decltype(mc)::value], s_u1 + decltype(mc)::value * R * D, v0, V); });
   TR(1);
   cl_sync(cl, &s_bail);
   TR(2);

@@ -278,6 +278,34 @@ __device__ __forceinline__ void load_rows(float* dst_lds, const float* src, int6
   }
 }
 
+// load_rows in two halves, for a stage head that wants every request in flight before its first wait: rows_request asks for the
+// rows into registers, rows_store puts them into LDS [ROWS][WIDTH] (rows beyond V zero-filled).  The request is branch-free -- a unit
+// without a live row re-reads the last live one and is zeroed at the store: behind a branch around a load the compiler has to wait
+// for every older load as well, which is the serial chain of round trips the split is there to remove.  v0 < V.
+template <int ROWS, int WIDTH>
+struct RowsReg {
+  static constexpr int Q = WIDTH / 4, N = (ROWS * Q + NTHR - 1) / NTHR;
+  f32x4 v[N];
+};
+template <int ROWS, int WIDTH>
+__device__ __forceinline__ void rows_request(RowsReg<ROWS, WIDTH>& g, const float* src, int64_t ld, int v0, int V) {
+  constexpr int Q = WIDTH / 4;
+#pragma unroll
+  for (int k = 0; k < RowsReg<ROWS, WIDTH>::N; ++k) {
+    const int u = min((int)threadIdx.x + k * NTHR, ROWS * Q - 1), r = u / Q, c = u - r * Q;
+    g.v[k] = ld4(src + (int64_t)min(v0 + r, V - 1) * ld + 4 * c);
+  }
+}
+template <int ROWS, int WIDTH>
+__device__ __forceinline__ void rows_store(const RowsReg<ROWS, WIDTH>& g, float* dst_lds, int v0, int V, bool zero = false) {
+  constexpr int Q = WIDTH / 4;
+#pragma unroll
+  for (int k = 0; k < RowsReg<ROWS, WIDTH>::N; ++k) {
+    const int u = threadIdx.x + k * NTHR;
+    if (u < ROWS * Q) st4(dst_lds + 4 * u, (v0 + u / Q < V && !zero) ? g.v[k] : f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // LDS layouts: float offsets into a stage's dynamic LDS.  One definition per stage: the kernel takes its pointers from it and the
 // host takes the launch's dynamic-LDS bytes from `bytes`.  PART = the partial-sum area (PART_FLOATS here, PARTC in
@@ -366,12 +394,32 @@ struct BwdALds {
 // The summation orders are fixed (bitwise reproducible steps): do not reorder a sum here.
 // ------------------------------------------------------------------------------------------------------------------
 
-// stage A forward: the 18 bias rows of the stage -> LDS
+// A pointer of the kernel's argument block as an opaque scalar value.  A select between two pointers that were both loaded from the
+// argument block the compiler turns into ONE load through a selected address: with a per-thread condition that is a vector load,
+// a dependent round trip in front of the load the pointer is for.  Through arg_value the select stays a select of values.
+template <class T>
+__device__ __forceinline__ const T* arg_value(const T* p) {
+  asm("" : "+s"(p));
+  return p;
+}
+// stage A forward: the 18 bias rows of the stage -> LDS.  Unit u (< FWD_A_BIAS_UNITS) is four floats: fwd_a_bias_src(a, u) -> s_bias + 4 u.
+// (a chain of selects, not a table of pointers indexed by u: the table lived in scratch memory -- the 160 bytes of
+//  chain_fwd_a_cl_kernel's frame -- and every bias load waited for a scratch load first)
+constexpr int FWD_A_BIAS_UNITS = 18 * (D / 4);
+__device__ __forceinline__ const float* fwd_a_bias_src(const sdumc_chain_args& a, int u) {
+  const float* t[18] = {arg_value(a.umlp0_b[0]), arg_value(a.umlp0_b[1]), arg_value(a.umlp0_b[2]), arg_value(a.umlp3_b[0]),
+                        arg_value(a.umlp3_b[1]), arg_value(a.umlp3_b[2]), arg_value(a.att0_b), arg_value(a.att3_b),
+                        arg_value(a.query_b[0]), arg_value(a.query_b[1]), arg_value(a.query_b[2]), arg_value(a.query_b[3]),
+                        arg_value(a.query_b[4]), arg_value(a.query_b[5]), arg_value(a.query_b[6]), arg_value(a.caq_b[0]),
+                        arg_value(a.caq_b[1]), arg_value(a.caq_b[2])};
+  const int row = u / (D / 4);
+  const float* p = t[0];
+#pragma unroll
+  for (int k = 1; k < 18; ++k) p = row == k ? t[k] : p;
+  return p + 4 * (u % (D / 4));
+}
 __device__ __forceinline__ void fwd_a_stage_bias(const sdumc_chain_args& a, float* s_bias) {
-  const float* bsrc[18] = {a.umlp0_b[0], a.umlp0_b[1], a.umlp0_b[2], a.umlp3_b[0], a.umlp3_b[1], a.umlp3_b[2], a.att0_b, a.att3_b,
-                           a.query_b[0], a.query_b[1], a.query_b[2], a.query_b[3], a.query_b[4], a.query_b[5], a.query_b[6],
-                           a.caq_b[0], a.caq_b[1], a.caq_b[2]};
-  for (int u = threadIdx.x; u < 18 * (D / 4); u += NTHR) st4(s_bias + 4 * u, ld4(bsrc[u / (D / 4)] + 4 * (u % (D / 4))));
+  for (int u = threadIdx.x; u < FWD_A_BIAS_UNITS; u += NTHR) st4(s_bias + 4 * u, ld4(fwd_a_bias_src(a, u)));
 }
 
 // stage A forward, fc_att (model :303): alpha[r][j] = att2[r] . W[j] + b[j]; ends with a barrier
@@ -417,28 +465,48 @@ __device__ __forceinline__ void fwd_a_fusion(const sdumc_chain_args& a, float* s
   __syncthreads();
 }
 
-// stage B forward: the bias rows of the stage -> LDS
+// stage B forward: the bias rows of the stage -> LDS, back to back in the order of FwdBLds::bias.  Unit u (< FWD_B_BIAS_UNITS) is
+// four floats: fwd_b_bias_src(a, u) -> s_bias + 4 u.
+constexpr int FWD_B_BIAS_UNITS = (4 * D + 4 * H + 2 * RD) / 4;
+__device__ __forceinline__ const float* fwd_b_bias_src(const sdumc_chain_args& a, int u) {
+  constexpr int U0 = 3 * (D / 4), U1 = U0 + 3 * (H / 4), U2 = U1 + D / 4, U3 = U2 + H / 4, U4 = U3 + RD / 4;
+  const int m0 = u / (D / 4), m1 = (u - U0) / (H / 4);
+  const float *c0 = arg_value(a.cmlp0_b[0]), *c1 = arg_value(a.cmlp0_b[1]), *c2 = arg_value(a.cmlp0_b[2]), *d0 = arg_value(a.cmlp3_b[0]),
+              *d1 = arg_value(a.cmlp3_b[1]), *d2 = arg_value(a.cmlp3_b[2]), *e0 = arg_value(a.catt0_b), *e3 = arg_value(a.catt3_b),
+              *r0 = arg_value(a.rnc0_b), *r2 = arg_value(a.rnc2_b);
+  const float* p = c0 + 4 * u;
+  p = m0 == 1 ? c1 + 4 * (u - D / 4) : p;
+  p = m0 == 2 ? c2 + 4 * (u - 2 * (D / 4)) : p;
+  p = u >= U0 ? d0 + 4 * (u - U0) : p;
+  p = (u >= U0 && m1 == 1) ? d1 + 4 * (u - U0 - H / 4) : p;
+  p = (u >= U0 && m1 == 2) ? d2 + 4 * (u - U0 - 2 * (H / 4)) : p;
+  p = u >= U1 ? e0 + 4 * (u - U1) : p;
+  p = u >= U2 ? e3 + 4 * (u - U2) : p;
+  p = u >= U3 ? r0 + 4 * (u - U3) : p;
+  p = u >= U4 ? r2 + 4 * (u - U4) : p;
+  return p;
+}
 __device__ __forceinline__ void fwd_b_stage_bias(const sdumc_chain_args& a, float* s_bias) {
-  const int tid = threadIdx.x;
-  for (int u = tid; u < 3 * (D / 4); u += NTHR) st4(s_bias + 4 * u, ld4(a.cmlp0_b[u / (D / 4)] + 4 * (u % (D / 4))));
-  for (int u = tid; u < 3 * (H / 4); u += NTHR) st4(s_bias + 3 * D + 4 * u, ld4(a.cmlp3_b[u / (H / 4)] + 4 * (u % (H / 4))));
-  for (int u = tid; u < D / 4; u += NTHR) st4(s_bias + 3 * D + 3 * H + 4 * u, ld4(a.catt0_b + 4 * u));
-  for (int u = tid; u < H / 4; u += NTHR) st4(s_bias + 4 * D + 3 * H + 4 * u, ld4(a.catt3_b + 4 * u));
-  for (int u = tid; u < RD / 4; u += NTHR) {
-    st4(s_bias + 4 * D + 4 * H + 4 * u, ld4(a.rnc0_b + 4 * u));
-    st4(s_bias + 4 * D + 4 * H + RD + 4 * u, ld4(a.rnc2_b + 4 * u));
-  }
+  for (int u = threadIdx.x; u < FWD_B_BIAS_UNITS; u += NTHR) st4(s_bias + 4 * u, ld4(fwd_b_bias_src(a, u)));
 }
 
+// alpha (or d_alpha) of rows [v0, v0 + R) -> LDS [R][4], in request / store halves as rows_request / rows_store: thread u < 3 R
+// holds alpha[r][j], u = 3 r + j
+template <int R>
+__device__ __forceinline__ float alpha_request(const float* alpha, int v0, int V) {
+  static_assert(R * 3 <= NTHR, "one element per thread");
+  const int u = min((int)threadIdx.x, R * 3 - 1), r = u / 3, j = u - 3 * r;
+  return alpha[(int64_t)min(v0 + r, V - 1) * 3 + j];
+}
+template <int R>
+__device__ __forceinline__ void alpha_store(float al, float* s_alpha, int v0, int V) {
+  const int u = threadIdx.x, r = u / 3, j = u - 3 * r;
+  if (u < R * 3) s_alpha[r * 4 + j] = v0 + r < V ? al : 0.f;
+}
 // stage B forward: alpha of rows [v0, v0 + R) -> LDS [R][4]
 template <class L>
 __device__ __forceinline__ void fwd_b_load_alpha(const sdumc_chain_args& a, float* sm, int v0, int V) {
-  constexpr int R = L::R;
-  float* s_alpha = sm + L::alpha;
-  for (int u = threadIdx.x; u < R * 3; u += NTHR) {
-    const int r = u / 3, j = u - 3 * r;
-    s_alpha[r * 4 + j] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
-  }
+  alpha_store<L::R>(alpha_request<L::R>(a.alpha, v0, V), sm + L::alpha, v0, V);
 }
 
 // stage B forward, modality-weighted sum (model :346-349): h[r][i][:] = sum_m alpha[r][m] c_m[r][i][:]; ends with a barrier
@@ -520,22 +588,51 @@ __device__ __forceinline__ void fwd_b_tail(const sdumc_chain_args& a, float* sm,
 }
 
 // stage B backward, head loads: d_rnc, saved r1 / h / e2 / e1, beta, alpha, d_vals (rows beyond V zero).  No barrier.
+// In two halves (rows_request / rows_store): all of it is requested before any of it is waited for.
+template <int R>
+struct BwdBHead {
+  RowsReg<R, RD> g, r1;
+  RowsReg<R, NQ * H> h;
+  RowsReg<R, H> e2;
+  RowsReg<R, D> e1;
+  float beta, alpha, dval;      // thread u < 8 R: u = 8 r + i
+};
+template <class L>
+__device__ __forceinline__ void bwd_b_head_request(BwdBHead<L::R>& hd, const sdumc_chain_args& a, int v0, int V) {
+  constexpr int R = L::R;
+  static_assert(R * 8 <= NTHR, "one element per thread");
+  rows_request(hd.g, a.g_rnc ? a.g_rnc : a.r1, RD, v0, V);      // (no d_rnc: any live rows, zeroed at the store)
+  rows_request(hd.r1, a.r1, RD, v0, V);
+  rows_request(hd.h, a.h, NQ * H, v0, V);
+  rows_request(hd.e2, a.e2, H, v0, V);
+  rows_request(hd.e1, a.e1, D, v0, V);
+  const int u = min((int)threadIdx.x, R * 8 - 1), i = u & 7;
+  const int64_t v = min(v0 + (u >> 3), V - 1);
+  hd.beta = a.beta[v * NQ + min(i, NQ - 1)];
+  hd.alpha = a.alpha[v * 3 + min(i, 2)];
+  hd.dval = (a.g_vals ? a.g_vals : a.beta)[v];
+}
+template <class L>
+__device__ __forceinline__ void bwd_b_head_store(const BwdBHead<L::R>& hd, const sdumc_chain_args& a, float* sm, int v0, int V) {
+  constexpr int R = L::R;
+  float *s_beta = sm + L::beta, *s_alpha = sm + L::alpha, *s_dvals = sm + L::dvals;
+  rows_store(hd.g, sm + L::g, v0, V, a.g_rnc == nullptr);
+  rows_store(hd.r1, sm + L::r1, v0, V);
+  rows_store(hd.h, sm + L::h, v0, V);
+  rows_store(hd.e2, sm + L::e2, v0, V);
+  rows_store(hd.e1, sm + L::e1, v0, V);
+  const int u = threadIdx.x, r = u >> 3, i = u & 7;
+  if (u < R * 8) {
+    s_beta[u] = (i < NQ && v0 + r < V) ? hd.beta : 0.f;
+    if (i < 3) s_alpha[r * 4 + i] = v0 + r < V ? hd.alpha : 0.f;
+    if (i == 0) s_dvals[r] = (a.g_vals && v0 + r < V) ? hd.dval : 0.f;
+  }
+}
 template <class L>
 __device__ __forceinline__ void bwd_b_load_head(const sdumc_chain_args& a, float* sm, int v0, int V) {
-  constexpr int R = L::R;
-  float *s_g = sm + L::g, *s_beta = sm + L::beta, *s_alpha = sm + L::alpha, *s_dvals = sm + L::dvals;
-  if (a.g_rnc) load_rows<R>(s_g, a.g_rnc, RD, RD, v0, V);
-  else for (int u = threadIdx.x; u < R * RD; u += NTHR) s_g[u] = 0.f;
-  load_rows<R>(sm + L::r1, a.r1, RD, RD, v0, V);
-  load_rows<R>(sm + L::h, a.h, NQ * H, NQ * H, v0, V);
-  load_rows<R>(sm + L::e2, a.e2, H, H, v0, V);
-  load_rows<R>(sm + L::e1, a.e1, D, D, v0, V);
-  for (int u = threadIdx.x; u < R * 8; u += NTHR) {
-    const int r = u >> 3, i = u & 7;
-    s_beta[u] = (i < NQ && v0 + r < V) ? a.beta[(int64_t)(v0 + r) * NQ + i] : 0.f;
-    if (i < 3) s_alpha[r * 4 + i] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + i] : 0.f;
-    if (i == 0) s_dvals[r] = (a.g_vals && v0 + r < V) ? a.g_vals[v0 + r] : 0.f;
-  }
+  BwdBHead<L::R> hd;
+  bwd_b_head_request<L>(hd, a, v0, V);
+  bwd_b_head_store<L>(hd, a, sm, v0, V);
 }
 
 // stage B backward, 12'. orgin_linear_change: d_r1 = (d_rnc W2) [r1 > 0] ; d_z = d_r1 W0 + d_vals w_v + d_fused
@@ -639,13 +736,9 @@ __device__ __forceinline__ void bwd_b_dc(const sdumc_chain_args& a, float* sm, f
 // stage A backward: alpha and stage B's d_alpha of rows [v0, v0 + R) -> LDS [R][4] each
 template <class L>
 __device__ __forceinline__ void bwd_a_load_alpha(const sdumc_chain_args& a, float* sm, int v0, int V) {
-  constexpr int R = L::R;
-  float *s_alpha = sm + L::alpha, *s_dalpha = sm + L::dalpha;
-  for (int u = threadIdx.x; u < R * 3; u += NTHR) {
-    const int r = u / 3, j = u - 3 * r;
-    s_alpha[r * 4 + j] = v0 + r < V ? a.alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
-    s_dalpha[r * 4 + j] = v0 + r < V ? a.d_alpha[(int64_t)(v0 + r) * 3 + j] : 0.f;
-  }
+  const float al = alpha_request<L::R>(a.alpha, v0, V), dal = alpha_request<L::R>(a.d_alpha, v0, V);
+  alpha_store<L::R>(al, sm + L::alpha, v0, V);
+  alpha_store<L::R>(dal, sm + L::dalpha, v0, V);
 }
 
 // stage A backward, 6'. + the external gradient of text_hidden (= query 5), ReLU/dropout mask of q -> d_q (pre-activation), for
