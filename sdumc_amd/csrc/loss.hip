@@ -94,6 +94,47 @@ __device__ __forceinline__ void rnc_loss_body(int n, RncWs w, float* loss_out) {
 }
 __global__ __launch_bounds__(256) void rnc_loss_kernel(int n, RncWs w, float* loss_out) { rnc_loss_body(n, w, loss_out); }
 
+// Measurement builds only (-DSDUMC_LOSS_DBG=1, off in the shipped library): thread 0 of workgroup 0 stamps the phases of rnc_row_body
+// (slots 0-5: entry | anchor row in LDS | distances | exp | row loss | G) and of rnc_dfeat_body (8-11: entry | coef in LDS | sums |
+// df written) with the 100 MHz wall clock; sdumc_loss_stamps_ copies the sixteen slots out (tools/loss_stamps.py).
+#ifndef SDUMC_LOSS_DBG
+#define SDUMC_LOSS_DBG 0
+#endif
+#if SDUMC_LOSS_DBG
+__device__ unsigned long long g_loss_stamps[16];
+#define LTR_INIT(wg) const bool ltr_on = (wg) == 0 && threadIdx.x == 0
+#define LTR(k) do { if (ltr_on) g_loss_stamps[k] = wall_clock64(); } while (0)
+#else
+#define LTR_INIT(wg)
+#define LTR(k)
+#endif
+
+constexpr int RNC_HEADQ = 16;   // row quads requested in rnc_row_body's head: 64 channels, the model's RnC width
+
+// sum over q = 0 .. n-1, ascending, of (q != i && pred) ? b[q] : 0 with pred = a[q] >= x (A_GE) or x >= a[q]; a and b in LDS, every
+// lane reading the same address.  Both arrays are read unconditionally, sixteen bytes at a time where they are aligned, and the term is
+// a select: with b[q] inside the condition each step was two dependent LDS round trips (a[q], the compare, then b[q] under its mask)
+// and the two loops of rnc_row_body were 16 of loss_stage1_kernel's 20 us at n = 128.  An excluded term adds 0.f, as it always did.
+template <bool A_GE>
+__device__ __forceinline__ float rnc_masked_sum(const float* a, const float* b, const float x, const int n, const int i, const bool al4) {
+  float sum = 0.f;
+  int q = 0;
+  if (al4) {
+#pragma unroll 4
+    for (; q + 4 <= n; q += 4) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(a + q), bv = *reinterpret_cast<const f32x4*>(b + q);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) sum += (q + c != i && (A_GE ? av[c] >= x : x >= av[c])) ? bv[c] : 0.f;
+    }
+  }
+#pragma unroll 8
+  for (; q < n; ++q) {
+    const float av = a[q], bv = b[q];
+    sum += (q != i && (A_GE ? av >= x : x >= av)) ? bv : 0.f;
+  }
+  return sum;
+}
+
 // One workgroup per anchor i, everything that depends on row i only: distances, label differences, exp,
 // the masked denominators D_ik, the row's loss and G_i* = dLoss/dlogit_i*.  labels: y[j] = labels[j % label_mod]
 // when label_mod > 0 (the reference's labels.repeat(2, 1), loss.py:283, without materialising it).
@@ -106,51 +147,113 @@ __device__ __forceinline__ void rnc_row_body(const float* f, const float* labels
   float* dd = ee + n;
   float* thr = dd + n;
   float* iD = thr + n;
-  for (int c = threadIdx.x; c < dim; c += 256) fi[c] = f[(size_t)i * dim + c];
-  __syncthreads();
-  const float yi = labels[label_mod > 0 ? i % label_mod : i];
-  float mx = -INFINITY;
+  const int tid = threadIdx.x;
   const bool vec = (dim & 3) == 0 && (reinterpret_cast<uintptr_t>(f) & 15) == 0;
-  for (int j = threadIdx.x; j < n; j += 256) {
-    float s = 0.f;
-    if (vec) {
-      // 16-byte loads, 8 in flight: the scalar loop below is one dependent L2 round trip per channel (64 of them at the
-      // model's width: ~20 of this kernel's 26 us).  Same summation order as the scalar loop.
-      const f32x4* fj = reinterpret_cast<const f32x4*>(f + (size_t)j * dim);
-      for (int c0 = 0; c0 < dim / 4; c0 += 8) {
-        f32x4 r[8];
+  const int nq = dim >> 2;   // 16-byte quads of a row (vector form only)
+  const bool hfull = vec && nq >= RNC_HEADQ;
+  // Head: every load whose address is known at the first instruction goes out before the first wait -- the anchor's channel, both
+  // labels and the first RNC_HEADQ quads of this thread's first row (the whole row at the model's width) -- and is consumed below in
+  // the order it went out.  One cold round trip instead of five (fi | labels[i] | quads 0-7 | quads 8-15 | labels[j]).
+  LTR_INIT(i);
+  LTR(0);
+  float fi0 = 0.f, yj0 = 0.f;
+  f32x4 q[RNC_HEADQ];
+  if (tid < dim) fi0 = f[(size_t)i * dim + tid];
+  const float yi = labels[label_mod > 0 ? i % label_mod : i];
+  if (tid < n) {
+    yj0 = labels[label_mod > 0 ? tid % label_mod : tid];
+    const f32x4* fj = reinterpret_cast<const f32x4*>(f + (size_t)tid * dim);
+    if (hfull) {          // no branch between the requests
 #pragma unroll
-        for (int u = 0; u < 8; ++u) r[u] = c0 + u < dim / 4 ? fj[c0 + u] : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int u = 0; u < RNC_HEADQ; ++u) q[u] = fj[u];
+    } else if (vec) {     // only the quads that exist (a slot without one is never read)
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (c0 + u < dim / 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float d = fi[4 * (c0 + u) + e] - r[u][e];
-              s += d * d;
-            }
-          }
-      }
-    } else {
-      for (int c = 0; c < dim; ++c) {
-        const float d = fi[c] - f[(size_t)j * dim + c];
-        s += d * d;
-      }
+      for (int u = 0; u < RNC_HEADQ; ++u)
+        if (u < nq) q[u] = fj[u];
     }
+  }
+  if (tid < dim) fi[tid] = fi0;
+  for (int c = tid + 256; c < dim; c += 256) fi[c] = f[(size_t)i * dim + c];
+  __syncthreads();
+  LTR(1);
+  float mx = -INFINITY;
+  // quads [c0, nq) of row j, 16-byte loads, 8 in flight (a scalar loop is one dependent L2 round trip per channel).  Same summation
+  // order as the scalar loop: s over the channels ascending.  The fused multiply-add is written out: left to contraction, a chain that
+  // starts from a literal 0 may become fma(d0, d0, d1 * d1) -- the other order, other bits.
+  auto quads_from = [&](const int j, int c0, float s) -> float {
+    const f32x4* fj = reinterpret_cast<const f32x4*>(f + (size_t)j * dim);
+    for (; c0 < nq; c0 += 8) {
+      f32x4 r[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) r[u] = c0 + u < nq ? fj[c0 + u] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (c0 + u < nq) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float d = fi[4 * (c0 + u) + e] - r[u][e];
+            s = __fmaf_rn(d, d, s);
+          }
+        }
+    }
+    return s;
+  };
+  auto scalar_row = [&](const int j) -> float {
+    float s = 0.f;
+    for (int c = 0; c < dim; ++c) {
+      const float d = fi[c] - f[(size_t)j * dim + c];
+      s = __fmaf_rn(d, d, s);
+    }
+    return s;
+  };
+  auto put = [&](const int j, const float s, const float yj) {
     const float dist = sqrtf(s);
     dd[j] = dist;
     w.dist[(size_t)i * n + j] = dist;
-    const float l = fabsf(yi - labels[label_mod > 0 ? j % label_mod : j]);
+    const float l = fabsf(yi - yj);
     ld[j] = l;
     thr[j] = __fsub_rn(l, 0.0001f);
     mx = fmaxf(mx, -dist * inv_t);
+  };
+  if (tid < n) {   // the row whose loads are already on their way
+    float s = 0.f;
+    if (hfull) {
+#pragma unroll
+      for (int u = 0; u < RNC_HEADQ; ++u) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = fi[4 * u + e] - q[u][e];
+          s = __fmaf_rn(d, d, s);
+        }
+      }
+      s = quads_from(tid, RNC_HEADQ, s);
+    } else if (vec) {
+#pragma unroll
+      for (int u = 0; u < RNC_HEADQ; ++u)
+        if (u < nq) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float d = fi[4 * u + e] - q[u][e];
+            s = __fmaf_rn(d, d, s);
+          }
+        }
+      s = quads_from(tid, RNC_HEADQ, s);
+    } else {
+      s = scalar_row(tid);
+    }
+    put(tid, s, yj0);
   }
+  for (int j = tid + 256; j < n; j += 256)
+    put(j, vec ? quads_from(j, 0, 0.f) : scalar_row(j), labels[label_mod > 0 ? j % label_mod : j]);
+  LTR(2);
   mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   for (int j = threadIdx.x; j < n; j += 256) ee[j] = expf(-dd[j] * inv_t - mx);
   __syncthreads();
+  LTR(3);
+  const bool al4 = (n & 3) == 0 && (reinterpret_cast<uintptr_t>(ld) & 15) == 0;   // ld, ee, thr, iD: all on 16-byte boundaries then
   float acc = 0.f;
   for (int k = threadIdx.x; k < n; k += 256) {
     if (k == i) {
@@ -158,15 +261,13 @@ __device__ __forceinline__ void rnc_row_body(const float* f, const float* labels
       continue;
     }
     const float t = thr[k];
-    float dsum = 0.f;
-#pragma unroll 8
-    for (int j = 0; j < n; ++j)      // unrolled: the LDS reads of 8 iterations are in flight together (same summation order)
-      dsum += (j != i && ld[j] >= t) ? ee[j] : 0.f;
+    const float dsum = rnc_masked_sum<true>(ld, ee, t, n, i, al4);    // j ascending: (j != i && ld[j] >= t) ? ee[j] : 0
     iD[k] = 1.f / dsum;
     acc += (-dd[k] * inv_t - mx) - logf(dsum);
   }
   const float s = block_sum_256(acc, red);
   if (threadIdx.x == 0) w.rowloss[i] = s;
+  LTR(4);
   if (!want_grad) return;
   __syncthreads();
   const float c = 1.f / ((float)n * (float)(n - 1));
@@ -174,14 +275,12 @@ __device__ __forceinline__ void rnc_row_body(const float* f, const float* labels
     float g = 0.f;
     if (j != i) {
       const float lj = ld[j];
-      float sum = 0.f;
-#pragma unroll 8
-      for (int k = 0; k < n; ++k)
-        sum += (k != i && lj >= thr[k]) ? iD[k] : 0.f;
+      const float sum = rnc_masked_sum<false>(thr, iD, lj, n, i, al4);   // k ascending: (k != i && lj >= thr[k]) ? iD[k] : 0
       g = -c * (1.f - ee[j] * sum);
     }
     w.G[(size_t)i * n + j] = g;
   }
+  LTR(5);
 }
 __global__ __launch_bounds__(256) void rnc_row_kernel(const float* f, const float* labels, int label_mod, int n,
                                                       int dim, float inv_t, RncWs w, int want_grad) {
@@ -386,11 +485,14 @@ __device__ __forceinline__ void rnc_dfeat_body(const float* f, int n, int dim, f
   float* coef = sm;
   float* red = sm + n;
   const int i = row0 + bx;
+  LTR_INIT(bx);
+  LTR(8);
   for (int j = threadIdx.x; j < n; j += 256) {
     const float d = w.dist[(size_t)i * n + j];
     coef[j] = (j != i && d > 0.f) ? (w.G[(size_t)i * n + j] + w.G[(size_t)j * n + i]) / d : 0.f;
   }
   __syncthreads();
+  LTR(9);
   const int part = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int c0 = 0; c0 < dim; c0 += 64) {
     const int c = c0 + lane;
@@ -407,12 +509,14 @@ __device__ __forceinline__ void rnc_dfeat_body(const float* f, int n, int dim, f
       }
       for (; j < n; j += 4) acc += coef[j] * (fic - f[(size_t)j * dim + c]);
     }
+    LTR(10);
     red[part * 64 + lane] = acc;
     __syncthreads();
     if (part == 0 && c < dim)
       df[(size_t)bx * dim + c] = -weight * inv_t * (red[lane] + red[64 + lane] + red[128 + lane] + red[192 + lane]);
     __syncthreads();
   }
+  LTR(11);
 }
 __global__ __launch_bounds__(256) void rnc_dfeat_kernel(const float* f, int n, int dim, float inv_t, float weight,
                                                         int row0, RncWs w, float* df) {
@@ -1065,6 +1169,14 @@ extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* la
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
 }
+
+#if SDUMC_LOSS_DBG
+// measurement builds only: the sixteen stamp slots of the last launches (call after synchronising the stream)
+extern "C" int sdumc_loss_stamps_(unsigned long long* out16) {
+  if (!out16) return SDUMC_EINVAL;
+  return hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_loss_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
+}
+#endif
 
 extern "C" int sdumc_rnc_dfeat_rows(const float* feats, int32_t n, int32_t dim, float temperature, float weight,
                                     int32_t row0, int32_t rows, float* dfeats, float* workspace, void* stream) {
