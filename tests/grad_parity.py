@@ -49,11 +49,12 @@ def old_rule_compared(names, ref):
     return [k for k in names if rms[k] >= OLD_SKIP * G]
 
 
-def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=()):
+def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=(), nosignal=NO_SIGNAL, max_between=MAX_BETWEEN):
     """Own-norm error of every live tensor of `got` against `ref_hi`, each held to its class's bar (module docstring); prints one
     summary line and returns a TensorErrors.  lay: a ParamLayout, or the list of tensor names.  zeros: the tensors the caller
     expects to be exactly zero in the reference.  between: where a case has more than MAX_BETWEEN tensors in between, the caller
-    names them all, as it names its zeros, and says why; the class may then hold those and no other."""
+    names them all, as it names its zeros, and says why; the class may then hold those and no other.  nosignal / max_between: the two
+    caps, for a caller whose graph is not the step's (default: the module's NO_SIGNAL and MAX_BETWEEN)."""
     names = list(lay.live_names()) if hasattr(lay, "live_names") else list(lay)
     assert set(names) <= set(ref_hi) and set(names) <= set(ref_lo) and set(names) <= set(got)
     hi = {k: ref_hi[k].detach().cpu().double() for k in names}
@@ -100,8 +101,8 @@ def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=()):
         if not e < SMALL * G:
             fails.append(f"{k}: the reference carries no signal here; device error rms {e:.3e} is not below {SMALL * G:.3e}")
     assert not fails, f"{what}: " + "; ".join(fails)
-    assert set(res.nosignal) <= NO_SIGNAL, f"{what}: no-signal tensors beyond the RnC head's biases: {sorted(set(res.nosignal) - NO_SIGNAL)}"
-    assert len(res.between) <= MAX_BETWEEN or set(res.between) <= set(between), \
+    assert set(res.nosignal) <= set(nosignal), f"{what}: no-signal tensors beyond the named ones: {sorted(set(res.nosignal) - set(nosignal))}"
+    assert len(res.between) <= max_between or set(res.between) <= set(between), \
         f"{what}: {len(res.between)} tensors in between, not named: {[(k, res.e_ref[k]) for k in res.between if k not in set(between)]}"
     assert set(res.zero) <= set(zeros), f"{what}: exactly zero in the reference but not named: {sorted(set(res.zero) - set(zeros))}"
     return res
