@@ -725,8 +725,22 @@ int sdumc_gather_pad_idx(const float* packed, const int64_t* start_all, const in
  * units wide (fp32 rows: d / 4; bf16 rows: d / 8; P3 rows: 3 d / 8), whatever they hold.  A segment with map_out writes the batch's
  * ROW MAP instead of (or beside) the padded copy: 4 bytes per frame instead of its 10 d.  max_workgroups > 0 caps the grid (the
  * kernel strides): a capped launch on a side stream fills the NEXT step's buffers beside the running step without queueing in
- * front of its kernels (sdumc_amd/engine.py, FusedTrainer); 0 = one pass.  seg.unit0 and total are filled by the call. */
+ * front of its kernels (sdumc_amd/engine.py, FusedTrainer); 0 = one pass.  seg.unit0 and total are filled by the call.
+ *
+ * THE RANDOM-MISSING PROTOCOL (miss_enable != 0; all-zero miss_* fields = none of it: a memset descriptor is unchanged).  Frame t
+ * of a segment whose miss_mod is m (0..3 = audio, text, video, feat4), of utterance e = idx[b] (its index IN THE STORE), is ABSENT
+ *   iff  word(t) < miss_frame_thr  or  (miss_all & 1)  or  word(0xFFFFFFFF) < miss_utt_thr  or  (miss_all & 2),   where
+ *   word(c0) = philox4x32_10(counter = (c0, (uint32) e, 0x4D530000 + m, miss_draw), key = (miss_seed_lo, miss_seed_hi))[0]
+ * (thresholds = floor(rate * 2^32), the dropout sites' "dropped when word < threshold"; a rate of 1 does not fit 32 bits and is the
+ * miss_all flag; counter word 2 is disjoint from every dropout site under the same seed).  An absent frame is assembled exactly as
+ * a padded one -- map_out entry = zero_row, row of the padded copy = zero bytes -- but STAYS A FRAME: len_out is unchanged, the
+ * row takes part in the softmaxes like any zero feature row (the reference's audio_feat * mask, main_frame_val_text_missing.py:123-129,
+ * without a rescale).  The decision depends on (seed, draw, m, e, t) alone: not on the batch, the position in it, B, Tmax, map or
+ * copy, nor on the segment -- a modality's rows segment and its planes segment carry the same miss_mod and so lose the same frames.
+ * miss_enable with a miss_mod outside 0..3 (or unknown miss_all bits) in any segment: SDUMC_EINVAL, nothing is launched. */
 #define SDUMC_GATHER_MAX_SEGS 8
+#define SDUMC_MISSING_SITE 0x4D530000u      /* + miss_mod: Philox counter word 2 of the protocol */
+#define SDUMC_MISSING_UTT 0xFFFFFFFFu       /* counter word 0 of the utterance-level (whole modality) draw */
 typedef struct sdumc_gather_seg {
   const void* packed;        /* [sum T, 16 d4 bytes] */
   const int64_t* start_all;  /* [N] first row of utterance e */
@@ -737,6 +751,10 @@ typedef struct sdumc_gather_seg {
                                 (sdumc_net_io.row_map: the step then reads the batch in place) */
   int32_t zero_row;          /* index of an all-zero row of the packed tensor (the store appends one) */
   int32_t Tmax, d4;
+  int32_t miss_mod;          /* the random-missing protocol (above): the segment's modality index 0..3 */
+  uint32_t miss_frame_thr;   /* floor(frame rate * 2^32), clamped to 2^32 - 1 */
+  uint32_t miss_utt_thr;     /* floor(modality rate * 2^32), likewise: the whole utterance loses this modality */
+  uint32_t miss_all;         /* bit 0: frame rate >= 1, bit 1: modality rate >= 1 (every frame absent, exactly) */
   int64_t unit0;            /* (filled by the call: first output row of the segment in the launch's row space) */
 } sdumc_gather_seg;
 typedef struct sdumc_gather_desc {
@@ -746,6 +764,9 @@ typedef struct sdumc_gather_desc {
   const float* labels_all;   /* [N] or NULL */
   float* labels_out;         /* [B] or NULL */
   int64_t total;             /* (filled by the call: output rows of all segments) */
+  uint32_t miss_seed_lo, miss_seed_hi;   /* the protocol's Philox key: seed & 0xffffffff, seed >> 32 */
+  uint32_t miss_draw;        /* counter word 3: the epoch number in training, a fixed number in evaluation */
+  uint32_t miss_enable;      /* 0: no frame is absent, whatever the other miss_* fields hold */
 } sdumc_gather_desc;
 int sdumc_gather_batch(const sdumc_gather_desc* g, int32_t max_workgroups, void* stream);
 

@@ -214,12 +214,15 @@ GATHER_MAX_SEGS = 8
 class GatherSeg(C.Structure):
     _fields_ = [("packed", C.c_void_p), ("start_all", C.c_void_p), ("len_all", C.c_void_p), ("out", C.c_void_p),
                 ("len_out", C.c_void_p), ("map_out", C.c_void_p), ("zero_row", C.c_int32), ("Tmax", C.c_int32), ("d4", C.c_int32),
+                # the random-missing protocol (data.MissingSpec.thresholds; all zero = none of it)
+                ("miss_mod", C.c_int32), ("miss_frame_thr", C.c_uint32), ("miss_utt_thr", C.c_uint32), ("miss_all", C.c_uint32),
                 ("unit0", C.c_int64)]
 
 
 class GatherBatch(C.Structure):
     _fields_ = [("seg", GatherSeg * GATHER_MAX_SEGS), ("nseg", C.c_int32), ("B", C.c_int32), ("idx", C.c_void_p),
-                ("labels_all", C.c_void_p), ("labels_out", C.c_void_p), ("total", C.c_int64)]
+                ("labels_all", C.c_void_p), ("labels_out", C.c_void_p), ("total", C.c_int64),
+                ("miss_seed_lo", C.c_uint32), ("miss_seed_hi", C.c_uint32), ("miss_draw", C.c_uint32), ("miss_enable", C.c_uint32)]
 
 
 class PoolFrames(C.Structure):

@@ -138,6 +138,8 @@ __global__ void gather_pad_idx_kernel(const float* packed, const int64_t* start_
 // 32-bit arithmetic; the lanes then stream its 16-byte units, four loads in flight each), waves striding over the rows of all
 // segments, and a CAPPED number of workgroups: the launch is meant to run on a side stream BESIDE a step (engine.FusedTrainer
 // prefetches the next batch), where an uncapped grid would queue tens of thousands of workgroups in front of the step's own kernels.
+// MISS: the random-missing protocol is enabled (g.miss_enable); a descriptor without it launches the instantiation that has no trace of it.
+template <bool MISS>
 __global__ __launch_bounds__(256) void gather_batch_kernel(const sdumc_gather_desc g) {
   const int i0 = blockIdx.x * 256 + threadIdx.x;
   if (i0 < g.B) {
@@ -158,7 +160,18 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const sdumc_gather_de
     const uint32_t r = row - (uint32_t)sg.unit0;
     const uint32_t b = r / (uint32_t)sg.Tmax, t = r - b * (uint32_t)sg.Tmax;
     const int64_t e = g.idx[b];
-    const bool valid = (int)t < sg.len_all[e];
+    bool valid = (int)t < sg.len_all[e];
+    // the random-missing protocol (include/sdumc_hip.h): an absent frame is assembled as a padded one.  Decided once per row from
+    // (seed, draw, modality, utterance, frame) alone -- wave-uniform, at most two Philox calls, none for a level whose rate is 0
+    if (MISS && valid) {
+      bool absent = sg.miss_all != 0u;
+      const uint32_t c2 = SDUMC_MISSING_SITE + (uint32_t)sg.miss_mod;
+      if (!absent && sg.miss_frame_thr)
+        absent = philox4x32_10(t, (uint32_t)e, c2, g.miss_draw, g.miss_seed_lo, g.miss_seed_hi).w[0] < sg.miss_frame_thr;
+      if (!absent && sg.miss_utt_thr)
+        absent = philox4x32_10(SDUMC_MISSING_UTT, (uint32_t)e, c2, g.miss_draw, g.miss_seed_lo, g.miss_seed_hi).w[0] < sg.miss_utt_thr;
+      valid = !absent;
+    }
     const int d4 = sg.d4;
     if (sg.map_out && lane == 0) sg.map_out[r] = valid ? (int32_t)(sg.start_all[e] + t) : sg.zero_row;
     if (!sg.out) continue;      // (the map only: the step reads the batch in place)
@@ -610,6 +623,7 @@ extern "C" int sdumc_gather_batch(const sdumc_gather_desc* gp, int32_t max_workg
     if (sg.out && (!sg.packed || sg.d4 <= 0)) return SDUMC_EINVAL;
     if (sg.map_out && ((reinterpret_cast<uintptr_t>(sg.map_out) & 3) || sg.zero_row < 0)) return SDUMC_EINVAL;
     if ((reinterpret_cast<uintptr_t>(sg.packed) | reinterpret_cast<uintptr_t>(sg.out)) & 15) return SDUMC_EINVAL;
+    if (g.miss_enable && ((uint32_t)sg.miss_mod > 3u || (sg.miss_all & ~3u))) return SDUMC_EINVAL;      // (the random-missing protocol)
     sg.unit0 = total;
     total += (int64_t)g.B * sg.Tmax;
   }
@@ -618,7 +632,8 @@ extern "C" int sdumc_gather_batch(const sdumc_gather_desc* gp, int32_t max_workg
   int64_t blocks = (total + 3) / 4;      // one wave per row
   if (max_workgroups > 0 && blocks > max_workgroups) blocks = max_workgroups;
   if (blocks < (g.B + 255) / 256) blocks = (g.B + 255) / 256;
-  hipLaunchKernelGGL(gather_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
+  if (g.miss_enable) hipLaunchKernelGGL(gather_batch_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
+  else hipLaunchKernelGGL(gather_batch_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
 }

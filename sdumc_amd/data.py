@@ -149,6 +149,146 @@ def resample_instances(instances, feat_scale=1, feat_type='frm_unalign'):
     return out
 
 
+# ---- the random-missing protocol: frame and modality drops, decided per (seed, draw, modality, utterance, frame) ----------------------
+# The rule (include/sdumc_hip.h states it beside sdumc_gather_batch, whose kernel evaluates it while it writes a batch's row maps):
+#   word(c0) = philox4x32_10(ctr = (c0, e, MISSING_SITE + m, draw), key = (seed & 0xffffffff, seed >> 32))[0]
+#   frame t of modality m (index in MODS) of utterance e (index in the store) is ABSENT
+#       iff word(t) < floor(frame[m] * 2^32)  or  word(MISSING_UTT) < floor(modality[m] * 2^32)
+# -- the dropout sites' "dropped when word < threshold" convention; a rate >= 1 makes every frame absent (its threshold does not fit
+# 32 bits: a flag), a rate of 0 none.  An absent frame is a ZERO FEATURE ROW THAT STILL COUNTS AS A FRAME (the reference's
+# audio_feat * mask, main_frame_val_text_missing.py:123-129, no rescale): lengths are unchanged, the row takes part in the softmaxes.
+MISSING_SITE = 0x4D530000      # + m: counter word 2, disjoint from every dropout site (small integers) under the same seed
+MISSING_UTT = 0xFFFFFFFF       # counter word 0 of the utterance-level draw (a frame index never reaches it)
+_SPEC_MODS = ('audio', 'text', 'video', 'feat4')
+
+
+def _philox_word0(c0, c1, c2, c3, k0, k1):
+    """word 0 of Philox4x32-10 (Salmon et al., SC'11) for broadcastable uint32 counters: csrc/common.h's philox4x32_10 on the host"""
+    c0, c1, c2, c3 = np.broadcast_arrays(*[np.asarray(c, dtype=np.uint64) for c in (c0, c1, c2, c3)])
+    k0, k1, mask = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF, np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = c0 * np.uint64(0xD2511F53), c2 * np.uint64(0xCD9E8D57)      # (32 x 32 bits: exact in 64)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & mask
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0.astype(np.uint32)
+
+
+class MissingSpec:
+    """A validated missing spec: frame / modality = four rates in MODS order ('audio', 'text', 'video', 'feat4'), seed < 2^64,
+    draw < 2^32 (the epoch number in training, a fixed number in evaluation).  Bad values raise SdumcError, on the host."""
+    __slots__ = ('frame', 'modality', 'seed', 'draw')
+
+    def __init__(self, frame=None, modality=None, seed=0, draw=0):
+        from ._lib import SdumcError
+
+        def rates(arg, what):
+            arg = {} if arg is None else arg
+            if not hasattr(arg, 'items'):
+                raise SdumcError(f"missing spec: {what} is a mapping from modality name to rate, not {arg!r}")
+            out = [0.0] * 4
+            for name, r in arg.items():
+                if name not in _SPEC_MODS:
+                    raise SdumcError(f"missing spec: unknown modality {name!r} in {what} (one of {_SPEC_MODS})")
+                if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not 0.0 <= float(r) <= 1.0:
+                    raise SdumcError(f"missing spec: {what}[{name!r}] must be a rate in [0, 1], not {r!r}")
+                out[_SPEC_MODS.index(name)] = float(r)
+            return tuple(out)
+
+        def integer(v, bits, what):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** bits:
+                raise SdumcError(f"missing spec: {what} must be an integer in [0, 2^{bits}), not {v!r}")
+            return int(v)
+
+        object.__setattr__(self, 'frame', rates(frame, 'frame'))
+        object.__setattr__(self, 'modality', rates(modality, 'modality'))
+        object.__setattr__(self, 'seed', integer(seed, 64, 'seed'))
+        object.__setattr__(self, 'draw', integer(draw, 32, 'draw'))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("a MissingSpec does not change: with_missing(...) / redrawn(draw) make a new one")
+
+    def __repr__(self):
+        f = {m: r for m, r in zip(_SPEC_MODS, self.frame) if r}
+        u = {m: r for m, r in zip(_SPEC_MODS, self.modality) if r}
+        return f"MissingSpec(frame={f}, modality={u}, seed={self.seed}, draw={self.draw})"
+
+    def __eq__(self, other):
+        return isinstance(other, MissingSpec) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self):
+        return hash((self.frame, self.modality, self.seed, self.draw))
+
+    @property
+    def enabled(self):
+        """False: no rate above 0 -- nothing is ever absent, and a view's descriptors are the plain store's"""
+        return any(r > 0.0 for r in self.frame + self.modality)
+
+    def with_draw(self, draw):
+        return MissingSpec(dict(zip(_SPEC_MODS, self.frame)), dict(zip(_SPEC_MODS, self.modality)), self.seed, draw)
+
+    def thresholds(self, k):
+        """modality index k -> (frame threshold, modality threshold, flags): the sdumc_gather_seg fields.  threshold =
+        floor(rate * 2^32) where that fits 32 bits; a rate of 1 sets the flag instead (bit 0: frame level, bit 1: modality level)."""
+        out, flags = [], 0
+        for bit, rate in enumerate((self.frame[k], self.modality[k])):
+            thr = int(rate * 4294967296.0)
+            if thr > 0xFFFFFFFF:
+                thr, flags = 0xFFFFFFFF, flags | (1 << bit)
+            out.append(thr)
+        return out[0], out[1], flags
+
+
+def _as_spec(spec):
+    if isinstance(spec, MissingSpec):
+        return spec
+    if hasattr(spec, 'keys'):
+        from ._lib import SdumcError
+        if set(spec.keys()) - set(MissingSpec.__slots__):
+            raise SdumcError(f"missing spec: unknown fields {sorted(set(spec.keys()) - set(MissingSpec.__slots__))}")
+        return MissingSpec(**dict(spec))
+    from ._lib import SdumcError
+    raise SdumcError(f"a missing spec is a MissingSpec or a mapping with frame / modality / seed / draw, not {spec!r}")
+
+
+def _modality_index(modality):
+    if isinstance(modality, str) and modality in _SPEC_MODS:
+        return _SPEC_MODS.index(modality)
+    if not isinstance(modality, (bool, str)) and isinstance(modality, (int, np.integer)) and 0 <= int(modality) < 4:
+        return int(modality)
+    from ._lib import SdumcError
+    raise SdumcError(f"unknown modality {modality!r}: one of {_SPEC_MODS}, or its index 0..3")
+
+
+def _missing_absent(spec, k, utt, t):
+    """the rule for modality index k at broadcastable utterance indices `utt` and frame indices `t` -> bool array, True = absent"""
+    ft, ut, flags = spec.thresholds(k)
+    utt, t = np.asarray(utt, dtype=np.uint64) & np.uint64(0xFFFFFFFF), np.asarray(t, dtype=np.uint64)
+    k0, k1 = spec.seed & 0xFFFFFFFF, spec.seed >> 32
+    absent = np.zeros(np.broadcast(utt, t).shape, dtype=bool)
+    if flags:
+        absent[...] = True
+        return absent
+    if ft:
+        absent |= _philox_word0(t, utt, MISSING_SITE + k, spec.draw, k0, k1) < np.uint32(ft)
+    if ut:
+        absent |= np.broadcast_to(_philox_word0(MISSING_UTT, utt, MISSING_SITE + k, spec.draw, k0, k1) < np.uint32(ut), absent.shape)
+    return absent
+
+
+def missing_keep(spec, modality, utt, length):
+    """bool [length]: which of the `length` frames of modality `modality` (a name of ('audio', 'text', 'video', 'feat4') or its index)
+    of utterance `utt` (its index in the store / dataset) are PRESENT under `spec` (a MissingSpec, or a mapping with its fields) --
+    the rule above on the host, for a loader loop that masks its own batches: feat[~missing_keep(...)] = 0.  The same bits
+    store.with_missing(...) applies on the device, whatever the batch."""
+    from ._lib import SdumcError
+    spec, k = _as_spec(spec), _modality_index(modality)
+    if isinstance(utt, bool) or not isinstance(utt, (int, np.integer)) or not 0 <= int(utt) < 2 ** 32:
+        raise SdumcError(f"missing_keep: utt is the utterance's index in the store, 0 <= utt < 2^32, not {utt!r}")
+    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or not 0 <= int(length) < 0xFFFFFFFF:
+        raise SdumcError(f"missing_keep: length must be a frame count, not {length!r}")
+    return ~_missing_absent(spec, k, int(utt), np.arange(int(length), dtype=np.uint64))
+
+
 class EpochPlan:
     """The batches of one epoch as the device sees them: ONE index tensor uploaded once (no per-batch host -> device copy inside the
     loop -- a pageable upload per step costs the host a synchronisation with the previous step), the host-side offsets into it and the
@@ -290,6 +430,19 @@ class DeviceFeatureStore:
             new.packed[m] = dst
         return new
 
+    def with_missing(self, frame=None, modality=None, seed=0, draw=0):
+        """The random-missing protocol on this store: a VIEW (MissingView) that shares every tensor and table and whose batches lose
+        frames -- frame = {modality name: rate} drops single frames, modality = {name: rate} drops the modality of a whole utterance;
+        the rule is stated above missing_keep and in include/sdumc_hip.h.  An absent frame is a zero feature row that still counts as
+        a frame: the reference's audio_feat * mask (main_frame_val_text_missing.py:123-129), no rescale, lengths unchanged.  Which
+        frames go depends on (seed, draw, modality, utterance's index in the store, frame) alone: pass draw=epoch for a fresh draw per
+        training epoch (view.redrawn(epoch)), a fixed draw for a reproducible corrupted test set.  No device work, no allocation:
+        the gather launch that writes a batch's row maps (or padded copies) redirects the absent frames to the store's zero row, so
+        the view goes wherever a store goes -- run_epoch, train_epoch, step_from_store, eval_epoch, saliency_epoch, batch_into, batch.
+        'text' and 'feat4' are separate modalities (the two streams degrade independently); 'audio' and 'video' are shared by both
+        streams.  Bad rates, names, seed or draw raise SdumcError here, on the host."""
+        return MissingView(self, MissingSpec(frame, modality, seed, draw))
+
     @property
     def nbytes(self):
         n = sum(t.numel() * t.element_size() for t in self.packed.values())
@@ -364,7 +517,7 @@ class DeviceFeatureStore:
         if (outs is None) == (maps_out is None):
             raise _lib.SdumcError("gather_desc: padded copies (outs) or row maps (maps_out), one of the two")
         g = _lib.GatherBatch()
-        n = 0
+        n = 0      # (the miss_* fields stay zero: no frame is absent; MissingView.gather_desc fills them)
         for k, m in enumerate(self.MODS):
             if maps_out is not None:
                 sg = g.seg[n]
@@ -433,3 +586,94 @@ class DeviceFeatureStore:
             pads.append((tmax - lens).tolist())
         idx_d = idx.to(self.device)
         return out, pads, self.emos[idx_d], self.vals[idx_d], [self.names[i] for i in idx.tolist()]
+
+
+class MissingView(DeviceFeatureStore):
+    """store.with_missing(...): the store under a missing spec.  Holds nothing of its own but `base`, `spec` and the spec's descriptor
+    fields: every tensor and table is the base store's (attribute reads fall through to it, so planes made later on the base are seen
+    here too), and making a view does no device work -- one per epoch (view.redrawn(epoch)) rebuilds no arena, no cached step and no planes.  The one thing that
+    differs is gather_desc, which fills the descriptor's miss_* fields: every consumer assembles its batches through it."""
+
+    def __init__(self, base, spec):
+        if isinstance(base, MissingView):      # a spec REPLACES the view's, it does not compose
+            base = base.base
+        self.base, self.spec = base, spec
+        # the descriptor's fields, worked out once: (seed lo, seed hi, draw), per modality (frame threshold, modality threshold, flags);
+        # None when every rate is 0 -- the view's descriptors are then the plain store's, bit for bit
+        self._miss = ((spec.seed & 0xFFFFFFFF, spec.seed >> 32, spec.draw), tuple(spec.thresholds(k) for k in range(4))) if spec.enabled else None
+
+    def __getattr__(self, name):      # (only reached for what the view does not hold itself)
+        if name in ('base', 'spec', '_miss'):
+            raise AttributeError(name)
+        return getattr(self.base, name)
+
+    def gather_desc(self, idx_ptr, B, T, outs, labels_out, lengths_out=None, planes_out=None, maps_out=None):
+        """the store's descriptor with the protocol's fields filled in: every segment of a modality -- its rows and, in a padded copy with
+        planes, its planes -- carries that modality's index and thresholds, so both lose the same frames"""
+        g = DeviceFeatureStore.gather_desc(self, idx_ptr, B, T, outs, labels_out, lengths_out, planes_out, maps_out)
+        if self._miss is not None:
+            (g.miss_seed_lo, g.miss_seed_hi, g.miss_draw), per = self._miss[0], g.nseg // 4      # (segments are laid out modality by modality)
+            g.miss_enable = 1
+            for j in range(g.nseg):
+                sg, k = g.seg[j], j // per
+                sg.miss_mod = k
+                sg.miss_frame_thr, sg.miss_utt_thr, sg.miss_all = self._miss[1][k]
+        return g
+
+    def with_missing(self, frame=None, modality=None, seed=0, draw=0):
+        return self.base.with_missing(frame, modality, seed, draw)
+
+    def redrawn(self, draw):
+        """the same spec at another draw (the epoch number: a fresh mask per epoch, the same one whenever that epoch is replayed)"""
+        return MissingView(self.base, self.spec.with_draw(draw))
+
+    def make_planes(self):
+        self.base.make_planes()
+        return self
+
+    def resampled(self, feat_scale=1, feat_type='frm_unalign', planes=None):
+        from ._lib import SdumcError
+        raise SdumcError("resampled: not on a with_missing view (the mask is defined on the frames of the store it was made on) -- "
+                         "pool first, then view: store.resampled(...).with_missing(...)")
+
+    def batch(self, indices):
+        """as DeviceFeatureStore.batch, through batch_into (the one launch that knows the protocol): absent frames are zero rows"""
+        idx = self._checked(indices)
+        B, T = self.batch_shape(idx)
+        outs = [torch.empty(B, T[k], self.dim[m], dtype=self.packed[m].dtype, device=self.device) for k, m in enumerate(self.MODS)]
+        labels = torch.empty(B, dtype=torch.float32, device=self.device)
+        self.batch_into(idx, outs, labels)
+        pads = [(T[k] - self.length[m][idx]).tolist() for k, m in enumerate(self.MODS)]
+        idx_d = idx.to(self.device)
+        return dict(zip(KEYS, outs)), pads, self.emos[idx_d], self.vals[idx_d], [self.names[i] for i in idx.tolist()]
+
+    def absent_rows(self, modality):
+        """bool numpy [frames of the store]: True where the packed row (start[e] + t, store order, without the trailing zero row) of
+        `modality` is absent under the spec -- the rule on the host, for every frame at once"""
+        k = _modality_index(modality)
+        lens = self._len_np[self.MODS[k]].astype(np.int64)
+        utt = np.repeat(np.arange(lens.size, dtype=np.int64), lens)
+        t = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(self.start[self.MODS[k]].numpy(), lens)
+        return _missing_absent(self.spec, k, utt, t)
+
+    def materialized(self, planes=None):
+        """A NEW ordinary store with the spec burnt in: the packed tensors cloned, the absent rows zeroed (torch indexing on the device),
+        the planes split again -- a fixed corrupted test set to share or checkpoint.  Shares the base's labels, names and tables.
+        planes: None = as the base, True / False overrides.  Its batches hold the bits this view's batches hold."""
+        base, _lib = self.base, self._lib
+        want_planes = (base.packed_p3 is not None) if planes is None else bool(planes)
+        new = DeviceFeatureStore.__new__(DeviceFeatureStore)
+        new._C, new._lib, new.device = base._C, _lib, base.device
+        new.names, new.vals, new.emos = list(base.names), base.vals, base.emos
+        new.start, new.length, new.dim = dict(base.start), dict(base.length), dict(base.dim)
+        new.start_d, new.length_d, new._len_np = dict(base.start_d), dict(base.length_d), dict(base._len_np)
+        new.packed, new.packed_p3 = {}, None
+        for m in self.MODS:
+            t = base.packed[m].clone()
+            rows = np.flatnonzero(self.absent_rows(m))
+            if rows.size:
+                t[torch.from_numpy(rows).to(base.device)] = 0
+            new.packed[m] = t
+        if want_planes:
+            new.make_planes()
+        return new

@@ -385,3 +385,25 @@ def eval_epoch(flat_params, dims, store, batches, *, bf16=False, key_padding=Fal
     if _evaluator is None or _evaluator[0] != key:
         _evaluator = (key, Evaluator(flat_params, dims, bf16=bf16, inplace=inplace, prefetch_workgroups=prefetch_workgroups))
     return _evaluator[1].eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out, attention=attention)
+
+
+def missing_curve(runner, store, batches, rates, modalities=('audio', 'video'), kind='frame', seed=0, draw=0, key_padding=False):
+    """The random-missing evaluation protocol: the metrics of both streams at every rate of `rates`, with the frames (kind='frame') or
+    the whole utterances (kind='modality') of `modalities` absent at that rate -- one eval_epoch per rate over store.with_missing views
+    of the SAME store (no second copy of it, no feature byte rewritten; data.DeviceFeatureStore.with_missing has the rule).
+    runner: a FusedTrainer or an Evaluator (anything with their eval_epoch).  -> [{'rate', 'full': metrics, 'missing': metrics}, ...]
+    in the order of `rates` (EvalResult.metrics); the entry of rate 0 is eval_epoch on the plain store.  The same (seed, draw) at every
+    rate: a frame absent at one rate is absent at every higher one."""
+    if kind not in ('frame', 'modality'):
+        raise _lib.SdumcError(f"missing_curve: kind must be 'frame' or 'modality', not {kind!r}")
+    if isinstance(modalities, str):
+        modalities = (modalities,)
+    base = getattr(store, 'base', store)
+    views = [base.with_missing(**{kind: {m: r for m in modalities}}, seed=seed, draw=draw) for r in rates]      # (validated up front)
+    from .data import EpochPlan
+    plan = batches if isinstance(batches, EpochPlan) else base.plan_epoch(batches)      # (one upload for all the rates)
+    curve, res = [], None
+    for rate, view in zip(rates, views):
+        res = runner.eval_epoch(view, plan, key_padding=key_padding, out=res)
+        curve.append({'rate': float(rate), **res.metrics(base)})
+    return curve
