@@ -435,7 +435,8 @@ typedef struct sdumc_attnpool {
   const int32_t* lengths; /* EXTENSION (default NULL = the reference's behaviour, where zero-padded frames take
                           part in the softmax, read_data.py:139-151 / model :63,:90): device int32 [V], valid frames per
                           virtual sample; frames t >= max(1, lengths[v]) get weight exactly 0 (key-padding mask) and
-                          therefore zero gradient in sdumc_attnpool_bwd, which needs no mask of its own */
+                          therefore zero gradient in sdumc_attnpool_bwd, which needs no mask of its own; a sample with ONE valid
+                          frame gets exactly zero dz and dq there, as a sample run on its own with T = 1 does */
   int32_t bf16;        /* 1: x and keys (and, in sdumc_attnpool_bwd, dz and dxd) are bf16 tensors of the same shapes (the engine's
                           bf16-storage mode, BASELINE configs[2] / [4]); scores, softmax, pooling, attn, pooled, out, dq stay
                           fp32.  dim must be 256; a fused x_drop needs precomputed keep-bits.  0 (default): fp32 */

@@ -457,6 +457,8 @@ __device__ __forceinline__ void attnpool_bwd_body(const sdumc_attnpool_bwd_t b, 
   const int t0 = chunk * CH;
   const bool fuse = p.tickets != nullptr;
   const DropRT od = drop_resolve(p.out_drop);
+  // one valid frame (key-padding length <= 1): the softmax is the constant 1 and dS EXACTLY 0, as for T == 1 in the launcher
+  const float scale = (p.lengths && p.lengths[v] <= 1) ? 0.f : p.scale;
   // this wave's first four key rows are requested before anything else: the round trip runs under the dO staging, the
   // delta dot products and the dA MFMAs
   constexpr int RB = 4;
@@ -507,7 +509,7 @@ __device__ __forceinline__ void attnpool_bwd_body(const sdumc_attnpool_bwd_t b, 
         float a = 0.f, dS = 0.f;
         if (r16 < nq && t < T) {
           a = p.attn[((size_t)v * T + t) * nq + r16];
-          dS = p.scale * a * (dA[e] - delta_s[r16]);
+          dS = scale * a * (dA[e] - delta_s[r16]);
         }
         A_s[rl * MAXQ + r16] = a;
         dS_s[rl * MAXQ + r16] = dS;
@@ -773,8 +775,10 @@ __device__ __forceinline__ void attnpool_bwd_v2(const sdumc_attnpool_bwd_t b, fl
   float dSv[4];
   {
     const float dl = r16 < NQT ? delta_s[r16] : 0.f;
+    // one valid frame (key-padding length <= 1): dS EXACTLY 0, see attnpool_bwd_body
+    const float scale = (p.lengths && p.lengths[v] <= 1) ? 0.f : p.scale;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) dSv[e] = p.scale * av[e] * (acc[e] * xscale - dl);      // rows beyond T, columns beyond nq: av = 0
+    for (int e = 0; e < 4; ++e) dSv[e] = scale * av[e] * (acc[e] * xscale - dl);      // rows beyond T, columns beyond nq: av = 0
   }
   // ---- 4. the row x channel parts: lane = 4 channels, the row's factors by v_readlane ----------------------------------
   f32x4 g[NQT], dqa[NQT];
@@ -1132,6 +1136,8 @@ extern "C" int sdumc_attnpool_bwd(const sdumc_attnpool_bwd_t* bp, void* stream) 
   // T == 1: the softmax of one frame is constant, its score gradient EXACTLY 0.  The kernels form dS = scale * A * (dA - delta)
   // from the same dot product summed in two orders; the rounding difference would leak into dz, dq and everything behind them,
   // so the backward of a single frame runs with scale = 0 (the kernels read the scale for dS only).
+  // (A sample with ONE VALID frame inside a longer padded batch, lengths[v] <= 1, is the same case per sample: the kernels zero
+  // the scale themselves, from the length they read.)
   if (b.f.T == 1) b.f.scale = 0.f;
   const sdumc_attnpool& p = b.f;
   if ((!b.dxd || b.dout_masked) && !v2_takes(p)) return SDUMC_EINVAL;      // (dxd left to the consumer: the wavefront-tiled kernels only)

@@ -344,39 +344,54 @@ def attnpool_desc(x, keys, q, V, T, nq, x_samples, q_stride, x_drop, out_drop, a
     return a
 
 
-def attnpool_fwd(x, keys, q, nq, x_samples=None, q_shared=False, x_drop=None, out_drop=None, lengths=None, tickets=True):
+def _out(*shape, **kw):
+    """every output tensor and workspace of the pooling wrappers below (a test may put a NaN-filling allocator in its place, so that
+    an element no kernel wrote cannot pass)"""
+    return torch.empty(*shape, **kw)
+
+
+def attnpool_fwd(x, keys, q, nq, x_samples=None, q_shared=False, x_drop=None, out_drop=None, lengths=None, tickets=True, dim=0,
+                 bf16=False, partial_only=False):
+    """dim: channels per row for the descriptor (0 = 256; 512 / 768 / 1024 size the workspace by the _dim query); bf16: x and keys are
+    torch.bfloat16; partial_only: stop after the per-chunk pass -- the flash-style partials stay in the workspace, returned as
+    desc._keep_ws (a float32 view: sdumc_attnpool.partial_only has the layout), out / pooled are not written."""
     V, T, Dm = keys.shape
     dev = keys.device
-    attn = torch.empty(V, T, nq, device=dev)
-    pooled = torch.empty(V, nq, Dm, device=dev)
-    out = torch.empty(V, nq, Dm, device=dev)
+    attn = _out(V, T, nq, device=dev)
+    pooled = _out(V, nq, Dm, device=dev)
+    out = _out(V, nq, Dm, device=dev)
     if lengths is not None and (lengths.dtype != torch.int32 or not lengths.is_cuda or lengths.numel() != V):
         raise _lib.SdumcError("lengths must be a cuda int32 tensor with one entry per virtual sample")
     a = attnpool_desc(x, keys, q, V, T, nq, x_samples or x.shape[0], 0 if q_shared else nq * Dm, x_drop, out_drop,
-                      attn, pooled, out, lengths=lengths, tickets=tickets)
+                      attn, pooled, out, dim=dim, lengths=lengths, tickets=tickets)
     a._keep_lengths = lengths
-    need = lib.sdumc_attnpool_fwd_workspace_bytes(V, T, nq)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    a.bf16, a.partial_only = 1 if bf16 else 0, 1 if partial_only else 0
+    need = lib.sdumc_attnpool_fwd_workspace_bytes_dim(V, T, nq, dim) if dim else lib.sdumc_attnpool_fwd_workspace_bytes(V, T, nq)
+    ws = _out(need, dtype=torch.uint8, device=dev)
     a.workspace, a.workspace_bytes = ptr(ws), need
+    if partial_only:
+        a._keep_ws = ws.view(torch.float32)
     check(lib.sdumc_attnpool_fwd(C.byref(a), _st()), "sdumc_attnpool_fwd")
     return out, attn, pooled, a
 
 
-def attnpool_bwd(desc, dout, keep, shared_q_sum=False):
+def attnpool_bwd(desc, dout, keep, shared_q_sum=False, dout_masked=None, want_dxd=True):
     """desc: the AttnPool returned by attnpool_fwd; keep: tensors that must stay alive.  shared_q_sum (descriptors with a shared
-    query, q_stride 0): dq comes back as the [1, nq, dim] SUM over the samples, from the backward's own single reduce launch."""
+    query, q_stride 0): dq comes back as the [1, nq, dim] SUM over the samples, from the backward's own single reduce launch.
+    dout_masked: an fp32 [V, nq, dim] tensor that receives dout * out-dropout mask (sdumc_attnpool_bwd.dout_masked); want_dxd=False:
+    dxd is left to the consumer (NULL in the descriptor) and comes back as None."""
     V, T, nq = desc.V, desc.T, desc.nq
     dev = dout.device
     Dm = desc.dim or _lib.D
     fdt = torch.bfloat16 if desc.bf16 else torch.float32
-    dz = torch.empty(V, T, Dm, device=dev, dtype=fdt)
-    dxd = torch.empty(V, T, Dm, device=dev, dtype=fdt)
-    dq = torch.empty(1 if shared_q_sum else V, nq, Dm, device=dev)
+    dz = _out(V, T, Dm, device=dev, dtype=fdt)
+    dxd = _out(V, T, Dm, device=dev, dtype=fdt) if want_dxd else None
+    dq = _out(1 if shared_q_sum else V, nq, Dm, device=dev)
     need = lib.sdumc_attnpool_bwd_workspace_bytes_dim(V, T, nq, Dm)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _out(need, dtype=torch.uint8, device=dev)
     b = _lib.AttnPoolBwd()
     b.f = desc
-    b.dout, b.dz, b.dxd = ptr(dout), ptr(dz), ptr(dxd)
+    b.dout, b.dz, b.dxd, b.dout_masked = ptr(dout), ptr(dz), ptr(dxd), ptr(dout_masked)
     if shared_q_sum:
         b.dq_sum = ptr(dq)
     else:
@@ -394,14 +409,14 @@ def umca_fwd(x, W, b, q, nq, x_samples=None, q_shared=False, x_drop=None, out_dr
     xs, T, Dm = x.shape
     V = V or (q.shape[0] if not q_shared else xs)
     dev = x.device
-    attn = torch.empty(V, T, nq, device=dev)
-    pooled = torch.empty(V, nq, Dm, device=dev)
-    out = torch.empty(V, nq, Dm, device=dev)
-    keys = torch.empty(V, T, Dm, device=dev) if want_keys else None
+    attn = _out(V, T, nq, device=dev)
+    pooled = _out(V, nq, Dm, device=dev)
+    out = _out(V, nq, Dm, device=dev)
+    keys = _out(V, T, Dm, device=dev) if want_keys else None
     a = attnpool_desc(x, keys, q, V, T, nq, x_samples or xs, 0 if q_shared else nq * Dm, x_drop, out_drop, attn, pooled, out,
                       lengths=lengths, tickets=False)
     need = lib.sdumc_attnpool_fwd_workspace_bytes(V, T, nq)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _out(need, dtype=torch.uint8, device=dev)
     a.workspace, a.workspace_bytes = ptr(ws), need
     u = _lib.Umca()
     u.a = a
@@ -418,20 +433,23 @@ def umca_fwd(x, W, b, q, nq, x_samples=None, q_shared=False, x_drop=None, out_dr
 
 def attnpool_fwd_multi(sites):
     """sites: list of dicts with the keyword arguments of attnpool_fwd (x, keys, q, nq, ...); ONE launch pair for all of them
-    (sdumc_attnpool_fwd_multi).  -> list of (out, attn, pooled, desc)."""
+    (sdumc_attnpool_fwd_multi).  -> list of (out, attn, pooled, desc).  bf16 / partial_only as for attnpool_fwd, per site."""
     arr = (_lib.AttnPool * len(sites))()
     res, keep = [], []
     for i, kw in enumerate(sites):
         x, keys, q, nq = kw["x"], kw["keys"], kw["q"], kw["nq"]
         V, T, Dm = keys.shape
         dev = keys.device
-        attn, pooled, out = torch.empty(V, T, nq, device=dev), torch.empty(V, nq, Dm, device=dev), torch.empty(V, nq, Dm, device=dev)
+        attn, pooled, out = _out(V, T, nq, device=dev), _out(V, nq, Dm, device=dev), _out(V, nq, Dm, device=dev)
         a = attnpool_desc(x, keys, q, V, T, nq, kw.get("x_samples") or x.shape[0], 0 if kw.get("q_shared") else nq * Dm,
                           kw.get("x_drop"), kw.get("out_drop"), attn, pooled, out, lengths=kw.get("lengths"),
                           tickets=kw.get("tickets", True))
+        a.bf16, a.partial_only = 1 if kw.get("bf16") else 0, 1 if kw.get("partial_only") else 0
         need = lib.sdumc_attnpool_fwd_workspace_bytes(V, T, nq)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _out(need, dtype=torch.uint8, device=dev)
         a.workspace, a.workspace_bytes = ptr(ws), need
+        if kw.get("partial_only"):
+            a._keep_ws = ws.view(torch.float32)
         arr[i] = a
         keep.append(ws)
         res.append((out, attn, pooled, a))
@@ -441,22 +459,25 @@ def attnpool_fwd_multi(sites):
 
 
 def attnpool_bwd_multi(descs, douts):
-    """One launch pair for the backward of several sites (sdumc_attnpool_bwd_multi) -> list of (dz, dxd, dq)."""
+    """One launch pair for the backward of several sites (sdumc_attnpool_bwd_multi) -> list of (dz, dxd, dq).  bf16 descriptors: dz and
+    dxd are bf16.  Descriptors with partial_only: dq is NOT written; the per-chunk slabs [V, nchunk, nq, 256] come back in its place."""
     arr = (_lib.AttnPoolBwd * len(descs))()
     res, keep = [], []
     for i, (desc, dout) in enumerate(zip(descs, douts)):
         V, T, nq, Dm = desc.V, desc.T, desc.nq, _lib.D
         dev = dout.device
-        dz, dxd, dq = torch.empty(V, T, Dm, device=dev), torch.empty(V, T, Dm, device=dev), torch.empty(V, nq, Dm, device=dev)
+        fdt = torch.bfloat16 if desc.bf16 else torch.float32
+        dz, dxd = _out(V, T, Dm, device=dev, dtype=fdt), _out(V, T, Dm, device=dev, dtype=fdt)
+        dq = _out(V, nq, Dm, device=dev)
         need = lib.sdumc_attnpool_bwd_workspace_bytes(V, T, nq)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _out(need, dtype=torch.uint8, device=dev)
         b = _lib.AttnPoolBwd()
         b.f = desc
         b.dout, b.dz, b.dxd, b.dq = ptr(dout), ptr(dz), ptr(dxd), ptr(dq)
         b.workspace, b.workspace_bytes = ptr(ws), need
         arr[i] = b
-        keep.append(ws)
-        res.append((dz, dxd, dq))
+        keep.append((ws, dq))
+        res.append((dz, dxd, ws.view(torch.float32).view(V, -1, nq, Dm) if desc.partial_only else dq))
     check(lib.sdumc_attnpool_bwd_multi(arr, len(descs), _st()), "sdumc_attnpool_bwd_multi")
     torch.cuda.current_stream().synchronize()
     return res

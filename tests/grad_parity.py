@@ -49,12 +49,14 @@ def old_rule_compared(names, ref):
     return [k for k in names if rms[k] >= OLD_SKIP * G]
 
 
-def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=(), nosignal=NO_SIGNAL, max_between=MAX_BETWEEN):
+def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=(), nosignal=NO_SIGNAL, max_between=MAX_BETWEEN,
+                  keep_old=True):
     """Own-norm error of every live tensor of `got` against `ref_hi`, each held to its class's bar (module docstring); prints one
     summary line and returns a TensorErrors.  lay: a ParamLayout, or the list of tensor names.  zeros: the tensors the caller
     expects to be exactly zero in the reference.  between: where a case has more than MAX_BETWEEN tensors in between, the caller
     names them all, as it names its zeros, and says why; the class may then hold those and no other.  nosignal / max_between: the two
-    caps, for a caller whose graph is not the step's (default: the module's NO_SIGNAL and MAX_BETWEEN)."""
+    caps, for a caller whose graph is not the step's (default: the module's NO_SIGNAL and MAX_BETWEEN).  keep_old=False: a family the
+    former skip rule never applied to (tests/attn_pool_cases.py): the class of every tensor follows from its e_ref alone."""
     names = list(lay.live_names()) if hasattr(lay, "live_names") else list(lay)
     assert set(names) <= set(ref_hi) and set(names) <= set(ref_lo) and set(names) <= set(got)
     hi = {k: ref_hi[k].detach().cpu().double() for k in names}
@@ -76,7 +78,7 @@ def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=(), 
             continue
         e_ref = float((ref_lo[k].detach().cpu().double().reshape(hi[k].shape) - hi[k]).norm()) / ref
         res.e_ref[k] = e_ref
-        if k in old or e_ref <= bar / 4:
+        if (keep_old and k in old) or e_ref <= bar / 4:
             res.bars[k] = bar
         elif e_ref <= 0.1:
             res.between.append(k)
