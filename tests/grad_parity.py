@@ -56,8 +56,11 @@ def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=(), 
     expects to be exactly zero in the reference.  between: where a case has more than MAX_BETWEEN tensors in between, the caller
     names them all, as it names its zeros, and says why; the class may then hold those and no other.  nosignal / max_between: the two
     caps, for a caller whose graph is not the step's (default: the module's NO_SIGNAL and MAX_BETWEEN).  keep_old=False: a family the
-    former skip rule never applied to (tests/attn_pool_cases.py): the class of every tensor follows from its e_ref alone."""
+    former skip rule never applied to (tests/attn_pool_cases.py): the class of every tensor follows from its e_ref alone.  bar: one
+    own-norm tolerance, or name -> tolerance where every tensor has its own (tests/gemm_cases.py); the classes and every assert are
+    the same, each tensor against its own bar."""
     names = list(lay.live_names()) if hasattr(lay, "live_names") else list(lay)
+    bar_of = bar if isinstance(bar, dict) else dict.fromkeys(names, bar)
     assert set(names) <= set(ref_hi) and set(names) <= set(ref_lo) and set(names) <= set(got)
     hi = {k: ref_hi[k].detach().cpu().double() for k in names}
     G = max(_rms(hi[k]) for k in names)
@@ -78,11 +81,11 @@ def tensor_errors(lay, got, ref_hi, ref_lo, bar, zeros=(), what="", between=(), 
             continue
         e_ref = float((ref_lo[k].detach().cpu().double().reshape(hi[k].shape) - hi[k]).norm()) / ref
         res.e_ref[k] = e_ref
-        if (keep_old and k in old) or e_ref <= bar / 4:
-            res.bars[k] = bar
+        if (keep_old and k in old) or e_ref <= bar_of[k] / 4:
+            res.bars[k] = bar_of[k]
         elif e_ref <= 0.1:
             res.between.append(k)
-            res.bars[k] = max(bar, 4 * e_ref)
+            res.bars[k] = max(bar_of[k], 4 * e_ref)
         else:
             res.nosignal.append(k)
             small_errs[k] = d / np.sqrt(hi[k].numel())
