@@ -1013,6 +1013,40 @@ typedef struct sdumc_norm_seg {
 size_t sdumc_tensor_norms_scratch_bytes(const sdumc_norm_seg* segs, int32_t n);
 int sdumc_tensor_norms(const sdumc_norm_seg* segs, int32_t n, float* norm, int32_t* nonfinite, float* diff_norm, void* scratch,
                        size_t scratch_bytes, void* stream);
+/* Global-norm gradient clipping and the non-finite step guard on the device: three launches, stream-ordered, no host
+ * synchronisation, no atomics.  Over the n floats of `grads` (the fused step's bucket, sdumc_step_grads_offset):
+ *   guard[0]  the L2 norm BEFORE clipping: fp64 sum of squares, fixed order, rounded once to fp32 (the reduce of sdumc_tensor_norms:
+ *             chunks cut by the count alone, partials added in index order by a one-workgroup launch -- the same input gives the
+ *             same bits on every call; a norm beyond the fp32 range reads +Inf here while the coefficient is taken from the fp64 value)
+ *   guard[1]  coef = min(1, max_norm / (norm + 1e-6)), evaluated in double from the fp64 norm and rounded once to fp32 -- the
+ *             expression of torch.nn.utils.clip_grad_norm_, 1e-6 included; max_norm <= 0: no clipping, coef = 1.  A NaN norm gives
+ *             a NaN coefficient, as torch's clamp does.
+ *   guard[2]  the number of elements that are NaN or +-Inf (exact below 2^24)
+ *   guard[3]  skipped: 1 when skip_nonfinite == 1 and guard[2] > 0, else 0
+ * and then grads[i] = grads[i] * coef in place, ONE fp32 multiply per element -- unless coef == 1 or the step is skipped: every
+ * workgroup of the third launch reads guard first and then leaves without reading or writing the gradients, so an unclipped bucket
+ * keeps its bits (-0.0 and subnormals included).  Scaling in place, not inside Adam: Adam's expression stays what it was, and a
+ * clipped step is bit for bit "multiply the bucket by guard[1], then sdumc_adam_step".
+ * hyper (optional): sdumc_step_cfg.hyper.  A skipped step sets hyper[1] -= 1, the step count as before the step -- the fused step
+ * advances it in its loss stage, before a gradient exists.  hyper[2..3] are derived from hyper[1] and are NOT restored: the next
+ * step's advance rewrites both before anyone reads them (the skipped step's own Adam launch applies nothing).
+ * Nothing but 4-byte alignment is assumed of grads: 16-byte accesses from a chunk's first aligned element on, single elements in
+ * front and behind.  scratch: caller-owned, sdumc_grad_guard_scratch_bytes(n) bytes (0 for n < 1), 16-byte aligned; every call
+ * writes what it reads of it; one call at a time per scratch.
+ * SDUMC_EINVAL, before anything is launched: grads / scratch / guard NULL, n < 1, max_norm NaN, skip_nonfinite other than 0 / 1,
+ * grads, hyper or guard not 4-byte aligned, scratch not 16-byte aligned.
+ * sdumc_grad_guard_multi: the same over the per-parameter gradient tensors of a loop that keeps p.grad, found through
+ * sdumc_tensor_norms' segment table (HOST memory, read by the call; 1 .. SDUMC_TENSOR_NORMS_MAX_SEGS segments, y must be NULL; the
+ * segments are SCALED in place although x is declared const): ONE norm over all segments, every segment scaled by the one
+ * coefficient.  No hyper and no skip: guard[3] = 0.  Scratch by sdumc_grad_guard_multi_scratch_bytes of the same table (0 = a table
+ * the entry refuses).  SDUMC_EINVAL: a table sdumc_tensor_norms would refuse, a segment with a y, scratch / guard NULL or misaligned
+ * as above, max_norm NaN; SDUMC_ENOMEM: scratch_bytes short.  Both before anything is launched. */
+size_t sdumc_grad_guard_scratch_bytes(int64_t n);
+int sdumc_grad_guard(float* grads, int64_t n, float max_norm, int32_t skip_nonfinite, float* hyper, void* scratch, float* guard,
+                     void* stream);
+size_t sdumc_grad_guard_multi_scratch_bytes(const sdumc_norm_seg* segs, int32_t nseg);
+int sdumc_grad_guard_multi(const sdumc_norm_seg* segs, int32_t nseg, float max_norm, void* scratch, size_t scratch_bytes,
+                           float* guard, void* stream);
 /* dst[r, 0:cols] = src[r, 0:cols] for r < rows, with leading dimensions */
 /* dst[r, 0:cols] += src[r, 0:cols] */
 int sdumc_axpy2d(const float* src, int32_t ld_src, float* dst, int32_t ld_dst, int32_t rows, int32_t cols, void* stream);
@@ -1353,6 +1387,17 @@ typedef struct sdumc_step_cfg {
   float* hyper;          /* device float[4], see sdumc_adam_step */
   float* losses;         /* device float[8]: total, mse_full, mse_missing, rmse_text, rmse_query, rmse_fused, rnc, 0.
                             MSE entries are the LOCAL sum / B_global (sum over ranks = global value). */
+  /* Gradient-norm clipping and the non-finite guard (sdumc_grad_guard, which see); all zero/NULL = the step without them, launch
+   * for launch.  guard != NULL: between the backward and Adam, on the caller's stream, sdumc_grad_guard(bucket, live count,
+   * clip_norm, skip_nonfinite, hyper, guard_scratch, guard) runs, and Adam applies nothing when it skipped the step (guard[3]):
+   * parameters, moments and the step count hyper[1] stay as they were, while the dropout call counter advances by 2 and losses[0..6]
+   * are written as for any step (losses[7] and a NaN total stay the cluster-failure signal alone).  SDUMC_EINVAL before the forward is
+   * enqueued: clip_norm / skip_nonfinite / guard_scratch set while guard is NULL, and whatever sdumc_grad_guard refuses.
+   * (The four sit here, in the middle: tests pin `distill` and the contrastive fields as the struct's tail.) */
+  float clip_norm;       /* max_norm; <= 0: no clipping (the norm, the count and the guard are still computed) */
+  int32_t skip_nonfinite;   /* 1: a bucket with a NaN or +-Inf element skips the step */
+  float* guard;          /* device float[4]: L2 norm before clipping, clip coefficient, non-finite count, skipped (0 / 1) */
+  void* guard_scratch;   /* sdumc_grad_guard_scratch_bytes(live count) bytes, 16-byte aligned */
   /* data-parallel exactness; all zero/NULL on one GPU */
   int32_t B_global;      /* 0 -> B */
   const float* ssd_global;        /* device float[3]: all-reduced sums of squared differences (text, query, fused) */

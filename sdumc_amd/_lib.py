@@ -157,11 +157,23 @@ class FrameDx(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
+def _guard_abi():
+    """False only for an A/B against an older build (SDUMC_LIB, tools/grad_guard_bench.py) from before sdumc_grad_guard: that library
+    reads sdumc_step_cfg WITHOUT the four guard fields, which sit in the struct's middle, so StepCfg leaves them out for it."""
+    if not os.environ.get("SDUMC_LIB") or not os.path.exists(LIB_PATH):
+        return True
+    return hasattr(C.CDLL(LIB_PATH), "sdumc_grad_guard")
+
+
+GUARD_ABI = _guard_abi()
+_GUARD_FIELDS = [("clip_norm", C.c_float), ("skip_nonfinite", C.c_int32), ("guard", C.c_void_p), ("guard_scratch", C.c_void_p)]
+
+
 class StepCfg(C.Structure):
     _fields_ = [("weights", C.c_float * 6), ("temperature", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
-                ("losses", C.c_void_p),
+                ("losses", C.c_void_p)] + (_GUARD_FIELDS if GUARD_ABI else []) + [
                 ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
                 ("rnc_labels_global", C.c_void_p), ("rnc_row0", C.c_int32 * 2),
                 ("contrast", C.c_int32), ("supcon_label_mode", C.c_int32), ("supcon_temperature", C.c_float),
@@ -176,6 +188,23 @@ def distill_code(name):
     if not isinstance(name, str) or name not in DISTILL:
         raise SdumcError(f"distill must be one of {sorted(DISTILL)}, not {name!r}")
     return DISTILL[name]
+
+
+def guard_args(clip_norm, skip_nonfinite):
+    """TrainStep / FusedTrainer (clip_norm=, skip_nonfinite=) -> (sdumc_step_cfg.clip_norm, .skip_nonfinite); (0.0, 0) = both off,
+    the step without sdumc_grad_guard.  clip_norm: None or a positive finite Python number (no bool, no string, no tensor);
+    skip_nonfinite: a bool."""
+    import math
+    clip = 0.0
+    if clip_norm is not None:
+        if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float)) or not math.isfinite(clip_norm) or clip_norm <= 0:
+            raise SdumcError(f"clip_norm must be a positive finite number or None, not {clip_norm!r}")
+        clip = float(clip_norm)
+        if C.c_float(clip).value in (0.0, float("inf")):      # (what the kernel would see)
+            raise SdumcError(f"clip_norm must be a positive finite fp32 value, not {clip_norm!r}")
+    if not isinstance(skip_nonfinite, bool):
+        raise SdumcError(f"skip_nonfinite must be True or False, not {skip_nonfinite!r}")
+    return clip, int(skip_nonfinite)
 
 
 # sdumc_step_cfg.contrast: the contrastive criterion over the rnc rows (SDUMC_CONTRAST_*); .supcon_label_mode: which labels count as
@@ -330,6 +359,10 @@ _SIGS = {
     "sdumc_tensor_norms_scratch_bytes": (C.c_size_t, [C.POINTER(NormSeg), C.c_int32]),
     "sdumc_tensor_norms": (C.c_int, [C.POINTER(NormSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "sdumc_grad_guard_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "sdumc_grad_guard": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdumc_grad_guard_multi_scratch_bytes": (C.c_size_t, [C.POINTER(NormSeg), C.c_int32]),
+    "sdumc_grad_guard_multi": (C.c_int, [C.POINTER(NormSeg), C.c_int32, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "sdumc_profile_enable": (C.c_int, [C.c_int]),
     "sdumc_profile_report": (C.c_int, [C.POINTER(ProfEntry), C.c_int]),
     "sdumc_gemm_workspace_bytes": (C.c_size_t, [C.POINTER(Gemm)]),

@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   // garbage, so NOTHING is applied -- parameters and moments stay as they were (every thread reads the word; it is sticky
   // until sdumc_chain_cluster_reset_error)
   const bool poisoned = tl.chain_err != nullptr && *tl.chain_err != 0;
-  if (i < n4 && !poisoned) {
+  // ... and a step sdumc_grad_guard skipped (non-finite gradients, guard[3]) applies nothing either; its dropout counter and its
+  // total below are those of a finite step
+  const bool hold = poisoned || (tl.guard != nullptr && tl.guard[3] != 0.f);
+  if (i < n4 && !hold) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       // fail loudly: a clustered utterance-level kernel whose spin ran into its cap finished with wrong data
       if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
     }
-    for (int64_t t = n4 * 4; t < n && !poisoned; ++t)
+    for (int64_t t = n4 * 4; t < n && !hold; ++t)
       adam_update(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
   }
 }
@@ -142,6 +145,7 @@ extern "C" int sdumc_adam_apply_(float* param, const float* grad, float* exp_avg
   sdumc_total_loss tl;
   tl.losses = nullptr;
   tl.chain_err = nullptr;
+  tl.guard = nullptr;
   for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
   if (total) tl = *total;
   // (callers without a loss record -- the data-parallel step, sdumc_adam_step -- are guarded by the device's error word too)

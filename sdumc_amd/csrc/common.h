@@ -52,6 +52,7 @@ struct sdumc_total_loss {
   float* losses;   // [8] or nullptr
   float w[6];
   const int32_t* chain_err;   // chain_cluster.hip's error word (a cluster spin ran into its cap) or nullptr: poisons the total with NaN
+  const float* guard;         // sdumc_grad_guard's float[4] or nullptr: guard[3] != 0 (a skipped step) applies nothing; the total stays
 };
 extern "C" {
 // sdumc_zpool_bwd with dz := dz + dz_add (dz_add may be NULL): folds the external gradient of cross_fused_feat in
@@ -66,6 +67,9 @@ int sdumc_adam_hyper_(float* hyper, float beta1, float beta2, void* stream);
 int sdumc_adam_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
                       uint32_t rng_inc, const struct sdumc_total_loss* total, void* stream);
+// grad_guard.hip: what sdumc_grad_guard would refuse for these arguments, without a launch
+int sdumc_grad_guard_check_(const float* grads, int64_t n, float max_norm, int32_t skip_nonfinite, const float* hyper,
+                            const void* scratch, const float* guard);
 }
 
 // ---------------------------------------------------------------------------

@@ -537,6 +537,7 @@ extern "C" int sdumc_preload_chain_(void);
 extern "C" int sdumc_preload_chain_cluster_(void);
 extern "C" int sdumc_preload_transformer_(void);
 extern "C" int sdumc_preload_frame_dx_(void);
+extern "C" int sdumc_preload_grad_guard_(void);
 namespace {
 __global__ void sdumc_preload_engine_kernel() {}
 // every code object of the library loaded on the current device, once per device (see the note at the end of any kernel source);
@@ -562,6 +563,7 @@ void preload_code_objects() {
     ok = sdumc_preload_chain_cluster_() == SDUMC_OK && ok;
     ok = sdumc_preload_transformer_() == SDUMC_OK && ok;
     ok = sdumc_preload_frame_dx_() == SDUMC_OK && ok;
+    ok = sdumc_preload_grad_guard_() == SDUMC_OK && ok;
     return ok;
   });
 }
@@ -3043,6 +3045,12 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   const StepLayout sl = step_layout(*d);
   if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   char* base = static_cast<char*>(io->workspace);
+  // clipping and the non-finite guard (grad_guard.hip) are asked for through `guard`: options without it, and whatever
+  // sdumc_grad_guard itself would refuse, come back before the forward is enqueued
+  if (!cfg->guard && (cfg->clip_norm != 0.f || cfg->skip_nonfinite != 0 || cfg->guard_scratch)) return SDUMC_EINVAL;
+  if (cfg->guard)
+    RET(sdumc_grad_guard_check_(reinterpret_cast<float*>(base + sl.grads), (int64_t)sl.live, cfg->clip_norm, cfg->skip_nonfinite,
+                                cfg->hyper, cfg->guard_scratch, cfg->guard));
   sdumc_net_io nio = *io;
   nio.workspace = base + sl.net;
   nio.workspace_bytes = sl.total - sl.net;
@@ -3072,12 +3080,18 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   RET(backward(bc, g, sch));
   mark(static_cast<hipStream_t>(stream), 9);
   sdumc_total_loss tl;
-  tl.losses = cfg->losses;
+  tl.losses = total_pending ? cfg->losses : nullptr;      // (else the loss stage's own last launch wrote the total)
   tl.chain_err = sdumc_chain_cluster_err_ptr_();
+  tl.guard = cfg->guard;
   for (int i = 0; i < 6; ++i) tl.w[i] = cfg->weights[i];
+  // behind the backward's final join, on the caller's stream: norm, coefficient and non-finite count of the bucket, the bucket
+  // scaled in place, and for a skipped step the step count taken back (the loss stage advanced it before a gradient existed)
+  if (cfg->guard)
+    RET(sdumc_grad_guard(g.grads, (int64_t)sl.live, cfg->clip_norm, cfg->skip_nonfinite, cfg->hyper, cfg->guard_scratch, cfg->guard,
+                         stream));
   RET(sdumc_adam_apply_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
                         cfg->eps, cfg->weight_decay, 1.0f, d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr, 2u,
-                        total_pending ? &tl : nullptr, stream));
+                        total_pending || cfg->guard ? &tl : nullptr, stream));
   mark(static_cast<hipStream_t>(stream), 10);
   return SDUMC_OK;      // (the backward's last act joined lane 3: the next batch's assembly, too, is ordered before whatever follows)
 }

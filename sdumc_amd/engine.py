@@ -366,6 +366,12 @@ class _OptStateMixin:
 
 _NO4 = (None,) * 4
 
+
+def _guard_buffers(live, dev):
+    """(guard float[4], scratch) of sdumc_grad_guard over a bucket of `live` floats"""
+    nb = int(lib.sdumc_grad_guard_scratch_bytes(int(live)))
+    return torch.zeros(4, device=dev), torch.empty(nb, dtype=torch.uint8, device=dev)
+
 # One input source of a TrainStep (TrainStep._bind): feats = the (audio, text, video, feat4) tensors the step reads -- padded [B, T, d]
 # batches, or a store's packed [rows, d] tensors when maps is given --, planes = their four bf16-plane tensors or None, maps = four
 # int32 row maps or None, store_rows = the packed tensors' row counts (0 without maps), labels [B].  The record's references are what
@@ -388,8 +394,16 @@ class TrainStep(_OptStateMixin):
 
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
-                 bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq'):
-        """contrast: the contrastive criterion over the [2B, 64] rnc rows (losses[6]): 'rnc' (Rank-N-Contrast, main :140 as it
+                 bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
+                 skip_nonfinite=False):
+        """clip_norm (None or a positive number) / skip_nonfinite: gradient-norm clipping and the non-finite guard, on the device
+        between the backward and Adam (sdumc_grad_guard: three launches, no synchronisation).  With either on, .guard is the device
+        float[4] the step writes -- the bucket's L2 norm before clipping, the coefficient min(1, clip_norm / (norm + 1e-6)) the
+        bucket was scaled by in place (1 without clip_norm), its number of NaN / Inf elements, and 1 when skip_nonfinite skipped the
+        step: parameters, moments and step count then stay as they were, the dropout counter advances as for any step.  Both off
+        (the default): .guard is None and the step is launch for launch the one without them.  A step with a guard is not
+        captured (capture() raises).
+        contrast: the contrastive criterion over the [2B, 64] rnc rows (losses[6]): 'rnc' (Rank-N-Contrast, main :140 as it
         stands) or 'supcon' (SupConLoss, loss.py:143-240: the two streams are the two views of a sample, rows L2-normalised in
         the kernel, positives = samples of one class: contrast_classes 'eq' equal labels, 'round' equal rint(label));
         contrast_temperature: None = the criterion's own default (2.0 / 0.07).
@@ -405,6 +419,10 @@ class TrainStep(_OptStateMixin):
         Ta, Tt, Tv, T4 = T
         distill_code = _lib.distill_code(distill)
         self.distill = distill
+        clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
+        if (clip or skip) and not _lib.GUARD_ABI:
+            raise _lib.SdumcError("clip_norm / skip_nonfinite: the library named by SDUMC_LIB is from before sdumc_grad_guard")
+        self.clip_norm, self.skip_nonfinite, self.guard = clip_norm, bool(skip), None
         _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)      # (rejected before any device work)
         self.contrast, self.contrast_temperature, self.contrast_classes = contrast, contrast_temperature, contrast_classes
         self.layout = ParamLayout.get(dims[0], dims[1], dims[2])
@@ -489,6 +507,14 @@ class TrainStep(_OptStateMixin):
         cfg.adam_m, cfg.adam_v = ptr(self.adam_m), ptr(self.adam_v)
         cfg.hyper, cfg.losses = ptr(self.hyper), ptr(self.losses)
         cfg.distill = distill_code
+        if clip or skip:
+            # the guard vector and the reduce's scratch: the run's (share.guard, one vector for every shape of a FusedTrainer) or its own
+            if getattr(share, "guard", None) is not None:
+                self.guard, self.guard_scratch = share.guard, share.guard_scratch
+            else:
+                self.guard, self.guard_scratch = _guard_buffers(self.layout.live, dev)
+            cfg.clip_norm, cfg.skip_nonfinite = clip, skip
+            cfg.guard, cfg.guard_scratch = ptr(self.guard), ptr(self.guard_scratch)
         self.graph = None
         goff = lib.sdumc_step_grads_offset(C.byref(self.dims))      # the same for every shape: the bucket leads the workspace
         self.grads = self.workspace[goff:goff + 4 * self.layout.live].view(torch.float32)
@@ -638,6 +664,8 @@ class TrainStep(_OptStateMixin):
         """Capture one step into a hipGraph; run() then replays it.  For embedding the step in a captured region, not for speed:
         the capture records a plain three-lane fork/join (no background lane, chain.hip instead of the clustered kernels) and
         measured slower than the eager four-lane launches, which are the production path."""
+        if self.guard is not None:
+            raise _lib.SdumcError("capture: a step with clip_norm / skip_nonfinite is not captured (not built)")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
@@ -760,9 +788,15 @@ class FusedTrainer:
     straight into one of the arena's two input sets -- by the PREVIOUS step, beside its latency-bound middle and its backward
     (sdumc_net_io.prefetch) -- and every step tells the engine the next batch's shape, so that the next keep-bits are laid out for it."""
 
+    guard = None      # with clip_norm / skip_nonfinite: the run's device float[4] every step writes (sdumc_grad_guard)
+
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
-                 inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', **step_kwargs):
+                 inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
+                 skip_nonfinite=False, **step_kwargs):
         """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        clip_norm / skip_nonfinite: gradient-norm clipping and the non-finite guard of every step (TrainStep); .guard is the run's
+        ONE device float[4] {norm, coefficient, non-finite count, skipped}, rewritten by every step whatever its shape (None with
+        both off); train_epoch keeps a copy per step.
         contrast: 'rnc' | 'supcon', contrast_temperature, contrast_classes: its contrastive criterion (TrainStep).
         capacity = (B_max, (T_audio, T_text, T_video, T_feat4) maxima) of the run: ONE arena then backs every batch shape
         (no per-shape workspace, the per-shape step is a few ctypes structs and tensor views: cache as many as you like) and
@@ -773,14 +807,19 @@ class FusedTrainer:
         through per-batch row maps (4 bytes per frame; sdumc_net_io.row_map)."""
         _lib.distill_code(distill)
         self.distill = distill
+        clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
         _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)
         self.contrast = (contrast, contrast_temperature, contrast_classes)
         _require_cuda(flat_params)
         self.params, self.dims, self.max_cached = flat_params, tuple(dims), max(1, int(max_cached))
         self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill, contrast=contrast, contrast_temperature=contrast_temperature,
-                       contrast_classes=contrast_classes)
+                       contrast_classes=contrast_classes, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         self.state = _RunState(flat_params, lay.live, lr, seed)     # (params, rng, adam_m, adam_v, hyper, losses)
+        self.guard = None
+        if clip or skip:
+            self.guard, self.state.guard_scratch = _guard_buffers(lay.live, flat_params.device)
+        self.state.guard = self.guard
         self._steps = {}          # shape -> TrainStep, insertion order = recency
         self.arena = None
         self._arena_kw = dict(bf16=step_kwargs.get("bf16", False), sets=sets, planes=planes,
@@ -927,7 +966,11 @@ class FusedTrainer:
         by_tensor=True: one more call per step (sdumc_tensor_norms, two launches) cuts the same raw bucket at ParamLayout's offsets ->
         rec.by_tensor (record.TensorNorms): every live tensor's gradient norm and non-finite count per step.  by_tensor='updates': a
         second such call over the flat parameters against a snapshot the record owns (one device copy in front of the first step) adds
-        each tensor's weight norm after the step and the norm of the step's actual update.  Both only read what the step left."""
+        each tensor's weight norm after the step and the norm of the step's actual update.  Both only read what the step left.
+        A trainer with clip_norm / skip_nonfinite: rec.guard [steps, 4] keeps every step's guard vector (one asynchronous device copy
+        per step; rec.skipped_steps()).  The record reads the bucket as the step LEFT it: with clipping on, the log's grad_norm column
+        and the record by tensor see the gradients AFTER scaling -- rec.guard[:, 0] is the norm before.  A skipped step's bucket is
+        unscaled, its non-finite elements are counted by both."""
         self._need_sets("train_epoch")
         from .evaluate import checked_plan
         from .record import NormTable, TrainRecord, by_tensor_mode
@@ -937,11 +980,12 @@ class FusedTrainer:
         n = len(plan if plan is not None else batches)
         lay = ParamLayout.get(*self.dims[:3])
         n_grads = lay.live if grad_norm else 0
-        if out is not None and not (isinstance(out, TrainRecord) and out.fits(n_store, n, dev, embeddings, n_grads, by_tensor, lay)):
+        guard = self.guard is not None
+        if out is not None and not (isinstance(out, TrainRecord) and out.fits(n_store, n, dev, embeddings, n_grads, by_tensor, lay, guard)):
             raise _lib.SdumcError("train_epoch: out= is not a record of this store's size and device, these many steps and these options")
         if plan is None:
             plan = store.plan_epoch(batches)
-        rec = (out if out is not None else TrainRecord.empty(n_store, n, dev, embeddings, n_grads, by_tensor, lay)).reset()
+        rec = (out if out is not None else TrainRecord.empty(n_store, n, dev, embeddings, n_grads, by_tensor, lay, guard)).reset()
         descs, st = {}, _lib.current_stream()
         bt, tables = rec.by_tensor, {}
         if by_tensor == "updates":
@@ -973,6 +1017,8 @@ class FusedTrainer:
             check(lib.sdumc_epoch_record(C.byref(r), st), "sdumc_epoch_record")
             if by_tensor:
                 record_by_tensor(i, ts)
+            if guard:
+                rec.guard[i].copy_(self.guard, non_blocking=True)
 
         rec.steps = self._epoch(store, plan, key_padding, on_step, record)
         return rec

@@ -1,7 +1,8 @@
 """Drop-in replacement of the optimizer line of the reference's training loop
 (main_frame_val_text_missing.py:317, `torch.optim.Adam(model.parameters(), lr=..., weight_decay=...)`; stepped at
 :150): the same signature, param_groups, state_dict format and LambdaLR behaviour, with the whole step as ONE
-sdumc_adam_multi launch over the per-parameter gradient tensors autograd left in `p.grad`.
+sdumc_adam_multi launch over the per-parameter gradient tensors autograd left in `p.grad`.  clip_grad_norm_ is the line that
+often stands in front of it, torch.nn.utils.clip_grad_norm_, as three launches over the same tensors and no host synchronisation.
 
 The one divergence from torch.optim.Adam: ONE step count is shared by all parameters (torch keeps one per
 parameter).  That is the model's own situation -- every live parameter receives a gradient on every step -- and it
@@ -14,12 +15,64 @@ There is no CPU or eager fallback: fp32 CUDA parameters on one device, or SdumcE
 """
 import torch
 
-from . import ops
+from . import _lib, ops
 from ._lib import SdumcError
 
 
 def _ceil4(n):
     return (n + 3) & ~3
+
+
+_clip_cache = {}      # the last gradient set's pointer tuple -> (segment table, scratch)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ over the .grad tensors of `parameters` (sdumc_grad_guard_multi): the total L2 norm in fp64 and a
+    fixed order, coef = min(1, max_norm / (norm + 1e-6)), every gradient scaled in place by one fp32 multiply -- untouched, bit for
+    bit, when coef == 1.  Three launches whatever the number of tensors, nothing synchronises.  Returns the total norm BEFORE
+    clipping as a 0-dim device tensor (torch's return value).  Non-finite gradients behave as in torch with
+    error_if_nonfinite=False: a NaN norm gives a NaN coefficient.  foreach is accepted and ignored.
+    Not built, SdumcError: norm_type != 2, error_if_nonfinite=True (it would cost the synchronisation this call exists to avoid),
+    more than _lib.TENSOR_NORMS_MAX_SEGS gradient tensors; and there is no fallback for CPU, non-fp32, sparse or non-contiguous
+    gradients.  max_norm: a positive finite Python number."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    if isinstance(norm_type, bool) or not isinstance(norm_type, (int, float)) or float(norm_type) != 2.0:
+        raise SdumcError(f"sdumc_amd.optim.clip_grad_norm_: norm_type={norm_type!r} is not built (the L2 norm only)")
+    if error_if_nonfinite:
+        raise SdumcError("sdumc_amd.optim.clip_grad_norm_: error_if_nonfinite=True is not built (it needs a host synchronisation)")
+    if max_norm is None:
+        raise SdumcError("sdumc_amd.optim.clip_grad_norm_: max_norm must be a positive finite number")
+    clip, _ = _lib.guard_args(max_norm, False)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)      # (torch's answer for no gradients)
+    dev = grads[0].device
+    for g in grads:
+        if not g.is_cuda or g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous():
+            raise SdumcError("sdumc_amd.optim.clip_grad_norm_: expected dense contiguous fp32 CUDA gradients (there is no fallback)")
+        if g.device != dev:
+            raise SdumcError("sdumc_amd.optim.clip_grad_norm_: the gradients are on different devices")
+    if len(grads) > _lib.TENSOR_NORMS_MAX_SEGS:
+        raise SdumcError(f"sdumc_amd.optim.clip_grad_norm_: more than {_lib.TENSOR_NORMS_MAX_SEGS} gradient tensors is not built")
+    key = (dev,) + tuple(g.data_ptr() for g in grads) + tuple(g.numel() for g in grads)
+    with torch.cuda.device(dev):
+        hit = _clip_cache.get(key)
+        if hit is None:
+            segs = (_lib.NormSeg * len(grads))()
+            for sg, g in zip(segs, grads):
+                sg.x, sg.y, sg.count = g.data_ptr(), None, g.numel()
+            nb = int(_lib.lib.sdumc_grad_guard_multi_scratch_bytes(segs, len(grads)))
+            if nb == 0:
+                raise SdumcError("sdumc_grad_guard_multi_scratch_bytes refused the gradient table")
+            _clip_cache.clear()
+            hit = _clip_cache[key] = (segs, torch.empty(nb, dtype=torch.uint8, device=dev))
+        segs, scratch = hit
+        guard = torch.empty(4, device=dev)
+        _lib.check(_lib.lib.sdumc_grad_guard_multi(segs, len(grads), clip, _lib.ptr(scratch), scratch.numel(), _lib.ptr(guard),
+                                                   _lib.current_stream()), "sdumc_grad_guard_multi")
+    return guard[0]
 
 
 class Adam(torch.optim.Optimizer):

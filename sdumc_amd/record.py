@@ -182,9 +182,13 @@ class TrainRecord:
     train-mode values: dropout on, parameters as they were BEFORE the step's update), seen [N], embeddings None or the four tensors of
     evaluate.EMBEDDINGS.  Rows not visited, and log rows from `steps` on, hold NaN.  Device or CPU tensors.
     scratch: the gradient reduce's device scratch (None without grad_norm): the record owns it, no step workspace is written.
-    by_tensor: None, or the TensorNorms of an epoch that ran with by_tensor=True | 'updates'."""
+    by_tensor: None, or the TensorNorms of an epoch that ran with by_tensor=True | 'updates'.
+    guard: None, or [capacity, 4] of a trainer with clip_norm / skip_nonfinite: row i = step i's guard vector (sdumc_grad_guard: the
+    bucket's L2 norm BEFORE clipping, the clip coefficient, its non-finite elements, 1 when the step was skipped).  With clipping on,
+    the log's grad_norm column and by_tensor see the bucket AFTER scaling."""
 
-    def __init__(self, log, preds, seen, embeddings=None, steps=0, scratch=None, n_grads=0, by_tensor=None):
+    def __init__(self, log, preds, seen, embeddings=None, steps=0, scratch=None, n_grads=0, by_tensor=None, guard=None):
+        self.guard = guard
         self.log, self.preds, self.seen, self.embeddings = log, preds, seen, embeddings
         self._steps, self.scratch, self.n_grads, self.by_tensor = int(steps), scratch, int(n_grads), by_tensor
         self.steps = steps
@@ -200,9 +204,10 @@ class TrainRecord:
             self.by_tensor.steps = int(k)
 
     @classmethod
-    def empty(cls, n, n_steps, device, embeddings=False, n_grads=0, by_tensor=False, layout=None):
+    def empty(cls, n, n_steps, device, embeddings=False, n_grads=0, by_tensor=False, layout=None, guard=False):
         """n utterances, room for n_steps steps; n_grads > 0: with the scratch of a gradient bucket of that many floats;
-        by_tensor=True | 'updates' (with layout, the run's engine.ParamLayout): with the record by tensor (TensorNorms)"""
+        by_tensor=True | 'updates' (with layout, the run's engine.ParamLayout): with the record by tensor (TensorNorms);
+        guard=True: with the [n_steps, 4] guard column"""
         emb = scratch = bt = None
         mode = by_tensor_mode(by_tensor)
         if mode:
@@ -214,10 +219,16 @@ class TrainRecord:
         if n_grads > 0:
             scratch = torch.zeros(int(lib.sdumc_epoch_record_scratch_bytes(int(n_grads))), dtype=torch.uint8, device=device)
         return cls(torch.empty(int(n_steps), LOG_COLS, device=device), torch.empty(2, n, device=device),
-                   torch.empty(n, dtype=torch.uint8, device=device), emb, 0, scratch, n_grads if n_grads > 0 else 0, bt)
+                   torch.empty(n, dtype=torch.uint8, device=device), emb, 0, scratch, n_grads if n_grads > 0 else 0, bt,
+                   torch.empty(int(n_steps), 4, device=device) if guard else None)
 
-    def fits(self, n, n_steps, device, embeddings, n_grads=0, by_tensor=False, layout=None):
+    def fits(self, n, n_steps, device, embeddings, n_grads=0, by_tensor=False, layout=None, guard=False):
         dev = torch.device(device)
+        if (self.guard is not None) != bool(guard):
+            return False
+        if guard and not (self.guard.dim() == 2 and self.guard.shape[1] == 4 and self.guard.shape[0] >= n_steps
+                          and self.guard.device == dev and self.guard.is_contiguous() and self.guard.dtype == torch.float32):
+            return False
         mode = by_tensor_mode(by_tensor)
         if (self.by_tensor is not None) != bool(mode):
             return False
@@ -237,8 +248,16 @@ class TrainRecord:
             t.fill_(float("nan"))
         if self.by_tensor is not None:
             self.by_tensor.reset()
+        if self.guard is not None:
+            self.guard.fill_(float("nan"))
         self.steps = 0
         return self
+
+    def skipped_steps(self):
+        """The steps the non-finite guard skipped (guard[:, 3] != 0 over rows [0, steps)), a list of step indices; one device -> host copy"""
+        if self.guard is None:
+            raise _lib.SdumcError("TrainRecord.skipped_steps: the epoch ran without clip_norm / skip_nonfinite")
+        return np.flatnonzero(self.guard[:self.steps, 3].cpu().numpy() != 0).tolist()
 
     def _visited(self):
         rows = np.flatnonzero(self.seen.cpu().numpy().reshape(-1) != 0)
