@@ -5,11 +5,10 @@ happens in libsdumc_hip.so; there is no CPU or torch fallback.
 """
 import collections
 import ctypes as C
-import math
 
 import torch
 
-from . import _lib
+from . import _lib, epoch
 from ._lib import lib, check, ptr
 
 D, H, NQ, RNC_DIM = _lib.D, _lib.H, _lib.NQ, _lib.RNC_DIM
@@ -379,6 +378,24 @@ def _guard_buffers(live, dev):
 _Source = collections.namedtuple("_Source", "feats planes maps store_rows labels")
 
 
+def _bind_source(io, src):
+    """Points the inputs of `io` (an sdumc_net_io) at `src` (a _Source; None = at nothing).  The ONLY code that writes its feature,
+    plane, row-map and store_rows fields."""
+    feats, planes, maps, rows = src[:4] if src is not None else (_NO4, None, None, (0,) * 4)
+    io.audio, io.text[0], io.video, io.text[1] = (ptr(t) for t in feats)
+    io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in planes or _NO4)
+    for i, m in enumerate(maps or _NO4):
+        io.row_map[i] = ptr(m)
+        io.store_rows[i] = rows[i]
+
+
+def _store_source(store, st, labels):
+    """`store` read in place through the row maps of input set `st`: its packed tensors, and their planes where it holds some"""
+    feats = tuple([store.packed[m] for m in store.MODS])
+    planes = tuple([store.packed_p3[m] for m in store.MODS]) if store.packed_p3 is not None else None
+    return _Source(feats, planes, st.ensure_maps(), tuple([t.shape[0] for t in feats]), labels)
+
+
 class TrainStep(_OptStateMixin):
     """The fused two-stream self-distillation step (main :119-150) on one GPU:
     forward(both streams) -> 6 losses -> backward -> Adam, ~150 launches on one stream,
@@ -523,18 +540,12 @@ class TrainStep(_OptStateMixin):
 
     def _bind(self, src):
         """Installs `src` (a _Source; None = nothing: launch() then refuses) as what the step reads.  The ONLY code that writes the
-        feature, plane, row-map and label pointers of io / cfg and the step's .audio .text .video .feat4 .labels."""
+        label pointer of cfg and the step's .audio .text .video .feat4 .labels; io's pointers are _bind_source's."""
         self._src = src
-        feats, planes, maps, rows, labels = src if src is not None else (_NO4, None, None, (0,) * 4, None)
-        self.audio, self.text, self.video, self.feat4 = feats
-        self.labels = labels
-        io = self.io
-        io.audio, io.text[0], io.video, io.text[1] = (ptr(t) for t in feats)
-        io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in planes or _NO4)
-        for i, m in enumerate(maps or _NO4):
-            io.row_map[i] = ptr(m)
-            io.store_rows[i] = rows[i]
-        self.cfg.labels = ptr(labels)
+        self.audio, self.text, self.video, self.feat4 = src.feats if src is not None else _NO4
+        self.labels = src.labels if src is not None else None
+        _bind_source(self.io, src)
+        self.cfg.labels = ptr(self.labels)
 
     @property
     def _planes(self):
@@ -568,15 +579,11 @@ class TrainStep(_OptStateMixin):
         input set `k` (written by the store's gather_desc(maps_out=...) launch): the step's feature pointers are the store's packed
         tensors, no padded copy of the batch exists.  Labels / lengths come from the set as with use_set."""
         a = self._arena
-        hf = self.dims.bf16 == 2
-        if a is None or self.dims.bf16 == 1 or (not hf and store.packed_p3 is None) or store.packed['audio'].dtype != self.feature_dtype:
+        if a is None or store.packed['audio'].dtype != self.feature_dtype \
+                or not epoch.in_place(True, self.feature_dtype, a._planes_ok, self._fdims, store):
             raise _lib.SdumcError("use_store: an arena step in fp32 storage with a store that holds planes, or in bf16 storage with a bf16 store")
-        st = a.sets[k]
-        mods = ('audio', 'text', 'video', 'feat4')
-        feats = tuple(store.packed[m] for m in mods)
-        planes = None if hf else tuple(store.packed_p3[m] for m in mods)
         self._home = (k, True)
-        self._bind(_Source(feats, planes, st.ensure_maps(), tuple(int(t.shape[0]) for t in feats), st.labels[:self.B]))
+        self._bind(_store_source(store, a.sets[k], a.sets[k].labels[:self.B]))
         return self
 
     def set_batch(self, audio, text, video, feat4, labels):
@@ -648,12 +655,12 @@ class TrainStep(_OptStateMixin):
         if not pregen and self.graph is None:
             io.bits_next = None
         io.bits_next_dims = C.addressof(next_step.dims) if next_step is not None else None
-        io.prefetch = C.addressof(prefetch) if prefetch is not None else None
         io.prefetch_workgroups = a.prefetch_workgroups if a is not None else 0
         try:
-            check(lib.sdumc_train_step(C.byref(self.dims), C.byref(io), C.byref(self.cfg), st), "sdumc_train_step")
+            check(epoch.with_prefetch(io, prefetch, lib.sdumc_train_step, C.byref(self.dims), C.byref(io), C.byref(self.cfg), st),
+                  "sdumc_train_step")
         finally:
-            io.bits_next, io.bits_next_dims, io.prefetch = saved, None, None
+            io.bits_next, io.bits_next_dims = saved, None
         if pregen or self.graph is not None:
             if shared:
                 a.bits_phase ^= 1
@@ -723,52 +730,63 @@ class _InputSet:
         return self.maps
 
 
-class _StepArena:
-    """Device memory of one training run, sized once for its largest batch (B, T_audio, T_text, T_video, T_feat4):
-    the step workspace (whose leading gradient bucket is zeroed here, once), `sets` input sets the batches are assembled in --
-    DeviceFeatureStore gathers straight into them; two sets let the NEXT batch be assembled while a step runs --, the five outputs,
-    and (fp32 train steps) the two keep-bits sets every shape of the run shares (their tags name the shape they were laid out for)."""
+class _Arena:
+    """Device memory of epochs over a store, sized for the largest batch (B, (T_audio, T_text, T_video, T_feat4)) seen so far: the
+    workspace, the five [2 B, w] outputs, and `sets` input sets the batches are assembled in (row maps, labels, lengths; padded input
+    buffers and planes only once a batch is gathered) -- two sets let the NEXT batch be assembled while a call runs."""
 
-    def __init__(self, flat_params, B, T, dims, bf16=False, sets=1, planes=False, bits_next=True, prefetch_workgroups=0):
-        dev = flat_params.device
-        self.B, self.T, self.dims = int(B), tuple(int(t) for t in T), tuple(dims)
-        d = make_dims(self.B, 2, self.T[0], self.T[2], (self.T[1], self.T[3]), dims, True, 0, bf16=bf16)
-        nbytes = lib.sdumc_step_workspace_bytes(C.byref(d))
-        if nbytes == 0:
-            raise _lib.SdumcError("invalid arena dimensions")
+    def __init__(self, dev, B, T, fdims, dtype, nbytes, sets=2):
+        self.B, self.T = int(B), tuple(int(t) for t in T)
+        self._fdims = tuple(fdims)
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        lay = ParamLayout.get(dims[0], dims[1], dims[2])
-        goff = lib.sdumc_step_grads_offset(C.byref(d))
-        self.workspace[goff:goff + 4 * lay.live].zero_()
-        self._fdims = fd = (dims[0], dims[1], dims[2], dims[1])
-        rows = [self.B * self.T[i] for i in range(4)]
-        n = [rows[i] * fd[i] for i in range(4)]
-        self.feature_dtype = torch.bfloat16 if d.bf16 == 2 else torch.float32
-        # planes: True = the input sets carry P3 planes from the start; None = as soon as a store with planes (or a resident batch)
-        # asks for them (ensure_planes); False = never
-        self._planes_ok = planes is not False and planes_wanted(True, dims, bf16)
-        self.sets = [_InputSet(n, self.B, self.feature_dtype, dev, rows) for _ in range(max(1, int(sets)))]
-        if planes is True:
-            self.ensure_planes()
-        V = 2 * self.B
-        self.outs = [torch.empty(V * k, device=dev) for k in (1, H, RNC_DIM, D, NQ * H)]
-        nb = lib.sdumc_net_bits_next_bytes(C.byref(d)) if bits_next else 0
-        self.bits = torch.zeros(nb, dtype=torch.uint8, device=dev) if nb else None
-        self.bits_phase = 0
-        self.prefetch_workgroups = int(prefetch_workgroups)
+        self.outs = [torch.empty(2 * self.B * w, device=dev) for w in epoch.OUT_WIDTHS]
+        rows = [self.B * t for t in self.T]
+        self.sets = [_InputSet([r * d for r, d in zip(rows, self._fdims)], self.B, dtype, dev, rows) for _ in range(max(1, int(sets)))]
+
+    @property
+    def nbytes(self):
+        """the byte sizes of the buffers that grow with the batch shape beside the sets: what fits takes after (B, T)"""
+        return (self.workspace.numel(),)
+
+    def fits(self, B, T, nbytes=0):
+        return B <= self.B and all(t <= c for t, c in zip(T, self.T)) and nbytes <= self.workspace.numel()
 
     def ensure_planes(self):
-        """The plane buffers of every input set (1.5x the fp32 input bytes each), allocated on first need; False when the arena's
-        mode has none (bf16 storage, widths that are not whole k-tiles, planes=False)."""
-        if not self._planes_ok:
-            return False
+        """The plane buffers of every input set (1.5x the fp32 input bytes each), allocated on first need"""
         for st in self.sets:
             if st.planes is None:
                 st.planes = [_planes_buffer(r, d, self.workspace.device) for r, d in zip(st._rows, self._fdims)]
         return True
 
-    def fits(self, B, T, nbytes=0):
-        return B <= self.B and all(t <= c for t, c in zip(T, self.T)) and nbytes <= self.workspace.numel()
+
+class _StepArena(_Arena):
+    """Device memory of one training run, sized once for its largest batch: an _Arena over the step workspace (whose leading gradient
+    bucket is zeroed here, once) -- DeviceFeatureStore gathers straight into its input sets --, and (fp32 train steps) the two keep-bits
+    sets every shape of the run shares (their tags name the shape they were laid out for)."""
+
+    def __init__(self, flat_params, B, T, dims, bf16=False, sets=1, planes=False, bits_next=True, prefetch_workgroups=0):
+        self.dims = tuple(dims)
+        d = make_dims(int(B), 2, int(T[0]), int(T[2]), (int(T[1]), int(T[3])), dims, True, 0, bf16=bf16)
+        nbytes = lib.sdumc_step_workspace_bytes(C.byref(d))
+        if nbytes == 0:
+            raise _lib.SdumcError("invalid arena dimensions")
+        self.feature_dtype = torch.bfloat16 if d.bf16 == 2 else torch.float32
+        super().__init__(flat_params.device, B, T, (dims[0], dims[1], dims[2], dims[1]), self.feature_dtype, nbytes, sets)
+        goff = lib.sdumc_step_grads_offset(C.byref(d))
+        self.workspace[goff:goff + 4 * ParamLayout.get(dims[0], dims[1], dims[2]).live].zero_()
+        # planes: True = the input sets carry P3 planes from the start; None = as soon as a store with planes (or a resident batch)
+        # asks for them (ensure_planes); False = never
+        self._planes_ok = planes is not False and planes_wanted(True, dims, bf16)
+        if planes is True:
+            self.ensure_planes()
+        nb = lib.sdumc_net_bits_next_bytes(C.byref(d)) if bits_next else 0
+        self.bits = torch.zeros(nb, dtype=torch.uint8, device=flat_params.device) if nb else None
+        self.bits_phase = 0
+        self.prefetch_workgroups = int(prefetch_workgroups)
+
+    def ensure_planes(self):
+        """False when the arena's mode has no planes (bf16 storage, widths that are not whole k-tiles, planes=False)"""
+        return self._planes_ok and super().ensure_planes()
 
 
 StepArena = _StepArena      # (public name: bench.py and callers that rotate resident batches build one directly)
@@ -880,17 +898,7 @@ class FusedTrainer:
     def _in_place(self, store):
         """fp32 storage and a store with planes, or bf16 storage and a bf16 store (widths in whole 128-element tiles): batches are not
         copied at all -- the step reads the store's packed tensors through row maps."""
-        if not self.inplace:
-            return False
-        if self.arena.feature_dtype == torch.bfloat16:
-            return store.packed['audio'].dtype == torch.bfloat16 and all(int(d) % 128 == 0 for d in self.dims[:3])
-        return store.packed_p3 is not None and self.arena._planes_ok
-
-    def _gather_desc(self, store, idx_ptr, ts, k, key_padding, planes, inplace=False):
-        st = self.arena.sets[k]
-        if inplace:
-            return store.gather_desc(idx_ptr, ts.B, ts.T, None, st.labels, st.lengths if key_padding else None, maps_out=st.ensure_maps())
-        return store.gather_desc(idx_ptr, ts.B, ts.T, st.inputs, st.labels, st.lengths if key_padding else None, st.planes if planes else None)
+        return epoch.in_place(self.inplace, self.arena.feature_dtype, self.arena._planes_ok, self.dims, store)
 
     def step_from_store(self, store, indices, key_padding=False):
         """One optimisation step on the batch `indices` of a data.DeviceFeatureStore: the padded batch is assembled by the
@@ -904,7 +912,7 @@ class FusedTrainer:
         st = self.arena.sets[0]
         if self._in_place(store):
             idx_d = store._checked(indices).to(store.device, non_blocking=True)
-            g = self._gather_desc(store, idx_d.data_ptr(), ts, 0, key_padding, True, inplace=True)
+            g = epoch.gather_desc(store, idx_d.data_ptr(), B, T, st, key_padding, True, True)
             check(lib.sdumc_gather_batch(C.byref(g), 0, _lib.current_stream()), "sdumc_gather_batch")
             self._keep_idx = idx_d
             ts.use_store(store, 0)
@@ -932,28 +940,23 @@ class FusedTrainer:
     def _epoch(self, store, plan, key_padding, on_step, record=None):
         """The loop of run_epoch and train_epoch over a data.EpochPlan.  record(i, ts) is called right after step i has been enqueued
         (ts = the step that ran it), before on_step."""
-        n = len(plan)
-        # the arena must hold the epoch's largest batch BEFORE the first descriptor is built (growing it invalidates every cached step);
-        # the per-shape step objects themselves are made one step ahead of the GPU, inside the loop: the host runs ahead of the device
-        # anyway, so a shape seen for the first time costs no device time
+        # the arena must hold the epoch's largest batch BEFORE the first descriptor is built (growing it invalidates every cached step)
         self._fit_arena(max(B for B, _ in plan.shapes), tuple(max(T[i] for _, T in plan.shapes) for i in range(4)))
-        inplace = self._in_place(store)
+        sets, inplace = self.arena.sets, self._in_place(store)
         planes = inplace or self._store_planes(store)
-        nxt = self._get(*plan.shapes[0])
-        g0 = self._gather_desc(store, plan.idx_ptr(0), nxt, 0, key_padding, planes, inplace)
-        check(lib.sdumc_gather_batch(C.byref(g0), 0, _lib.current_stream()), "sdumc_gather_batch")
-        for i in range(n):
-            ts = nxt.use_store(store, i & 1) if inplace else nxt.use_set(i & 1, planes=planes)
-            ts.use_lengths(self.arena.sets[i & 1].lengths if key_padding else None)
-            nxt = self._get(*plan.shapes[i + 1]) if i + 1 < n else None
-            pf = self._gather_desc(store, plan.idx_ptr(i + 1), nxt, (i + 1) & 1, key_padding, planes, inplace) if nxt is not None else None
-            losses = self._launch(ts, next_step=nxt, prefetch=pf)
+
+        def bind(ts, k):
+            ts = ts.use_store(store, k) if inplace else ts.use_set(k, planes=planes)
+            ts.use_lengths(sets[k].lengths if key_padding else None)
+            return ts
+
+        def both(i, ts):
             if record is not None:
                 record(i, ts)
-            if on_step is not None:
-                on_step(i, losses)
-        self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers)
-        return n
+            on_step(i, ts.losses)
+
+        return epoch.run(self, store, plan, sets, key_padding, planes, inplace, self._get, bind, self._launch,
+                         record if on_step is None else both)
 
     def train_epoch(self, store, batches, key_padding=False, on_step=None, embeddings=False, grad_norm=False, out=None, by_tensor=False):
         """run_epoch with the epoch's record kept -> record.TrainRecord: what the reference's training pass returns (main :156-178: the
@@ -972,11 +975,10 @@ class FusedTrainer:
         and the record by tensor see the gradients AFTER scaling -- rec.guard[:, 0] is the norm before.  A skipped step's bucket is
         unscaled, its non-finite elements are counted by both."""
         self._need_sets("train_epoch")
-        from .evaluate import checked_plan
         from .record import NormTable, TrainRecord, by_tensor_mode
         by_tensor = by_tensor_mode(by_tensor)
         dev, n_store = self.params.device, len(store)
-        plan, batches = checked_plan(batches, n_store)
+        plan, batches = epoch.checked_plan(batches, n_store)
         n = len(plan if plan is not None else batches)
         lay = ParamLayout.get(*self.dims[:3])
         n_grads = lay.live if grad_norm else 0
@@ -1026,18 +1028,10 @@ class FusedTrainer:
     def _record_desc(self, rec, ts, embeddings, grad_norm):
         """sdumc_epoch_record's descriptor for steps of ts.B samples (idx and log_row are set per step): rows [0, B) of the arena's
         outputs to stream 0's tensors of the record, rows [B, 2 B) to stream 1's"""
-        from .evaluate import EMBEDDINGS
-        B, n = ts.B, rec.preds.shape[1]
-        pairs = [(self.arena.outs[0], rec.preds, 1)]
-        if embeddings:
-            pairs += [(self.arena.outs[j + 1], rec.embeddings[name], math.prod(shape)) for j, (name, shape, _) in enumerate(EMBEDDINGS)]
         r = _lib.EpochRec()
-        for j, (src, dst, w) in enumerate(pairs):
-            for s in range(2):
-                sg = r.seg[2 * j + s]
-                sg.src, sg.dst = src.data_ptr() + 4 * s * B * w, dst.data_ptr() + 4 * s * n * w
-                sg.rows, sg.cols, sg.dst_rows = B, w, n
-        r.nseg, r.B, r.mark = 2 * len(pairs), B, ptr(rec.seen)
+        for k, sg in enumerate(epoch.scatter_segments(self.arena.outs, rec, ts.B, embeddings)):
+            r.seg[k] = sg
+        r.nseg, r.B, r.mark = k + 1, ts.B, ptr(rec.seen)
         r.losses, r.hyper = ptr(self.state.losses), ptr(self.state.hyper)
         if grad_norm:
             r.grads, r.n_grads, r.scratch = ptr(ts.grads), ts.grads.numel(), ptr(rec.scratch)

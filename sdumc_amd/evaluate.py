@@ -2,16 +2,14 @@
 (main_frame_val_text_missing.py:333-353 calls train_or_eval_model three times per epoch; :151-166 is the eval branch -- both streams,
 no_grad, model.eval(); main_frame_val_text_missing_inference.py:100-215 is the same loop with the embeddings kept).
 
-`eval_epoch` is to those passes what FusedTrainer.run_epoch is to the training pass: the epoch's index vectors are uploaded once, the
-first batch is assembled in front of the first forward, and forward i (sdumc_net_forward, train = 0, both streams in one call: the
-audio / video frame projections run once) carries the assembly of batch i + 1 on its background lane (sdumc_net_io.prefetch).  With a
-store the training epoch would read in place, no padded copy of a batch exists: the forward reads the packed tensors through row maps.
-After every forward ONE launch (sdumc_scatter_rows_multi) moves the batch's stream-major outputs to the rows its utterances have in
-the store, so the results line up with store.names / store.vals whatever order the sampler used, and nothing crosses to the host
-inside the loop.  The metrics stay on the host (metric.py): [N] vectors cross once per epoch.
+`eval_epoch` is to those passes what FusedTrainer.run_epoch is to the training pass, and runs the same loop (epoch.run has its
+definition): the call of batch i is forward i (sdumc_net_forward, train = 0, both streams in one call: the audio / video frame
+projections run once).  After every forward ONE launch (sdumc_scatter_rows_multi) moves the batch's stream-major outputs to the rows
+its utterances have in the store, so the results line up with store.names / store.vals whatever order the sampler used.  The metrics
+stay on the host (metric.py): [N] vectors cross once per epoch.
 
-Evaluation owns its device memory (_EvalArena): workspace, outputs, two sets of row maps / labels / lengths (and input buffers when
-batches are gathered).  It reads the flat parameters and nothing else of a training run -- no step workspace, no keep-bits, no
+Evaluation owns its device memory (an engine._Arena): workspace, outputs, two sets of row maps / labels / lengths (and input buffers
+when batches are gathered).  It reads the flat parameters and nothing else of a training run -- no step workspace, no keep-bits, no
 Philox counter (rng_state = NULL) -- so a training run is bit for bit the same with or without evaluation epochs in between.
 
 attention=True keeps what the reference's inference pass plots per utterance (vector_attention of FRA2UTT_new / Cross_Attention,
@@ -20,23 +18,16 @@ model :68, :95; attention_masks, model :291; main_frame_val_text_missing_inferen
 both streams out of the forward's workspace to per-frame tensors in store order (EvalResult.attention)."""
 import ctypes as C
 
-import numpy as np
 import torch
 
-from . import _lib, engine
+from . import _lib, engine, epoch
 from ._lib import lib, check, ptr
+from .epoch import EMBEDDINGS, MODS, NQ, check_epoch_indices, checked_plan      # (callers reach these through evaluate too)
 
-D, H, NQ, RNC_DIM = _lib.D, _lib.H, _lib.NQ, _lib.RNC_DIM
-# the forward's outputs beside vals, in sdumc_net_io's order: name, trailing shape, (full, missing) keys of checkpoint.run_inference
-EMBEDDINGS = (("fused", (H,), ("full_rep", "missing_rep")),
-              ("rnc", (RNC_DIM,), ("full_rnc", "missing_rnc")),
-              ("text_hidden", (D,), ("text_rep_query_full", "text_rep_query_missing")),
-              ("cross_text", (NQ, H), ("text_rep_full", "text_rep_missing")))
 # the attention maps: per stream, the modalities its three pooling pairs read (stream 1's text slot is feat4); every tensor
 # [packed rows of that modality, ATTN_COLS]: column 0 FRA2UTT_new's weight, columns 1..7 Cross_Attention's in multi_query order
 ATTENTION = (("full", ("audio", "text", "video")), ("missing", ("audio", "feat4", "video")))
 ATTN_COLS = 1 + NQ
-MODS = ("audio", "text", "video", "feat4")
 
 
 def attention_rows(store):
@@ -44,45 +35,7 @@ def attention_rows(store):
     return {m: int(torch.as_tensor(store.length[m]).sum()) for m in MODS}
 
 
-def _rows_dict(rows):
-    if rows is None:
-        raise _lib.SdumcError("EvalResult: attention=True needs rows= (evaluate.attention_rows(store), or the four row counts)")
-    if not isinstance(rows, dict):
-        rows = dict(zip(MODS, rows))
-    return {m: int(rows[m]) for m in MODS}
-
-
-def check_epoch_indices(batches, n):
-    """Host-side check of an epoch's index vectors against a store of n utterances: every index in [0, n) and none visited twice
-    (the scatter writes every result row once; a second visit would race with the first).  Returns the concatenated int64 tensor."""
-    idxs = [torch.as_tensor(b, dtype=torch.int64).reshape(-1).cpu() for b in batches]
-    if not idxs or any(i.numel() == 0 for i in idxs):
-        raise _lib.SdumcError("eval_epoch: no batches, or an empty batch")
-    flat = torch.cat(idxs)
-    if int(flat.min()) < 0 or int(flat.max()) >= n:
-        raise _lib.SdumcError(f"eval_epoch: sample index out of range [0, {n})")
-    u, counts = torch.unique(flat, return_counts=True)
-    if u.numel() != flat.numel():
-        raise _lib.SdumcError(f"eval_epoch: index {int(u[counts > 1][0])} appears more than once in the epoch")
-    return flat
-
-
-def checked_plan(batches, n):
-    """check_epoch_indices over `batches` -- index vectors, or a data.EpochPlan (its host copy of the indices when it kept one) -- before
-    anything is uploaded or enqueued -> (the plan or None, the batches as int64 tensors or None)."""
-    from .data import EpochPlan
-    if isinstance(batches, EpochPlan):
-        host = getattr(batches, "idx_h", None)
-        host = batches.idx_d.cpu() if host is None else host
-        bounds = list(batches.offsets) + [int(host.numel())]
-        check_epoch_indices([host[a:b] for a, b in zip(bounds, bounds[1:])], n)
-        return batches, None
-    batches = [torch.as_tensor(b, dtype=torch.int64).reshape(-1) for b in batches]
-    check_epoch_indices(batches, n)
-    return None, batches
-
-
-class EvalResult:
+class EvalResult(epoch.StoreOrdered):
     """Results of one evaluation epoch in STORE order (row i = utterance i of the store): preds [2, N] (row 0 the full stream, row 1
     the text-missing one), seen [N] (uint8 / bool: visited this epoch), embeddings None or {'fused' [2, N, 128], 'rnc' [2, N, 64],
     'text_hidden' [2, N, 256], 'cross_text' [2, N, 7, 128]}, attention None or {'full': {'audio', 'text', 'video'}, 'missing':
@@ -96,35 +49,20 @@ class EvalResult:
     @classmethod
     def empty(cls, n, device, embeddings=False, attention=False, rows=None):
         """attention=True: rows = attention_rows(store) (or the four row counts, audio / text / video / feat4)"""
-        emb = att = None
-        if embeddings:
-            emb = {name: torch.empty((2, n) + shape, device=device) for name, shape, _ in EMBEDDINGS}
+        att = None
         if attention:
-            rows = _rows_dict(rows)
+            rows = epoch.rows_dict(rows)
             att = {s: {m: torch.empty(rows[m], ATTN_COLS, device=device) for m in mods} for s, mods in ATTENTION}
-        return cls(torch.empty(2, n, device=device), torch.empty(n, dtype=torch.uint8, device=device), emb, att)
+        return cls(*cls._empty(n, device, embeddings), att)
 
     def fits(self, n, device, embeddings, attention=False, rows=None):
-        ok = (self.preds.shape == (2, n) and self.preds.device == torch.device(device) and self.seen.numel() == n
-              and self.seen.element_size() == 1 and (self.embeddings is not None) == bool(embeddings)
-              and (self.attention is not None) == bool(attention))
-        if ok and attention:
-            rows = _rows_dict(rows)
-            ok = all(s in self.attention and m in self.attention[s] and self.attention[s][m].shape == (rows[m], ATTN_COLS)
-                     and self.attention[s][m].device == torch.device(device) and self.attention[s][m].dtype == torch.float32
-                     and self.attention[s][m].is_contiguous() for s, mods in ATTENTION for m in mods)
-        return ok
+        return (self._fits(n, device) and (self.embeddings is not None) == bool(embeddings)
+                and (self.attention is not None) == bool(attention)
+                and (not attention or self._frames_fit(self.attention, ATTENTION, epoch.rows_dict(rows), ATTN_COLS, device)))
 
     def reset(self):
         """NaN everywhere, nothing seen: once per epoch, in front of its first batch"""
-        self.preds.fill_(float("nan"))
-        self.seen.zero_()
-        for t in (self.embeddings or {}).values():
-            t.fill_(float("nan"))
-        for d in (self.attention or {}).values():
-            for t in d.values():
-                t.fill_(float("nan"))
-        return self
+        return self._reset(*(t for d in (self.attention or {}).values() for t in d.values()))
 
     def attention_of(self, store, i):
         """The attention maps of ONE utterance -- i = its index in the store, or its name -- as views: {'full': {'audio' [T_a, 8],
@@ -132,46 +70,14 @@ class EvalResult:
         tables.  Raises when the epoch kept no attention maps or did not visit the utterance."""
         if self.attention is None:
             raise _lib.SdumcError("EvalResult: this epoch kept no attention maps (eval_epoch(..., attention=True))")
-        if isinstance(i, str):
-            try:
-                i = store.names.index(i)
-            except ValueError:
-                raise _lib.SdumcError(f"EvalResult: no utterance named {i!r} in the store") from None
-        i = int(i)
-        if not 0 <= i < self.seen.numel():
-            raise _lib.SdumcError(f"EvalResult: utterance index {i} out of range [0, {self.seen.numel()})")
-        if int(self.seen.reshape(-1)[i]) == 0:
-            raise _lib.SdumcError(f"EvalResult: utterance {i} was not visited in this epoch")
-        out = {}
-        for s, mods in ATTENTION:
-            out[s] = {}
-            for m in mods:
-                a, n = int(store.start[m][i]), int(store.length[m][i])
-                out[s][m] = self.attention[s][m][a:a + n]
-        return out
-
-    def _visited(self):
-        rows = np.flatnonzero(self.seen.cpu().numpy().reshape(-1) != 0)
-        if rows.size == 0:
-            raise _lib.SdumcError("EvalResult: no row was visited")
-        return rows
+        return self._frames_of(store, i, {s: {m: self.attention[s][m] for m in mods} for s, mods in ATTENTION})
 
     def results(self, store):
         """The dictionary checkpoint.run_inference returns (same keys, array shapes and embedding names), over the visited rows in
         store order, names from store.names, labels from store.vals; plus val_mse_full (main :170; = val_mse).  One device -> host
         copy per tensor."""
-        rows = self._visited()
-        preds = self.preds.cpu().numpy()
-        labels = torch.as_tensor(store.vals).cpu().numpy().astype(np.float32).reshape(-1)[rows]
-        out = {"val_preds_full": preds[0][rows].reshape(-1, 1), "val_preds_missing": preds[1][rows].reshape(-1, 1),
-               "val_labels": labels}
-        for name, _, keys in EMBEDDINGS if self.embeddings is not None else ():
-            t = self.embeddings[name].cpu().numpy()
-            out[keys[0]], out[keys[1]] = t[0][rows], t[1][rows]
-        out["names"] = [store.names[i] for i in rows.tolist()]
-        out["val_mse"] = float(np.mean((labels - out["val_preds_full"].reshape(-1)) ** 2))
-        out["val_mse_full"] = out["val_mse"]
-        out["val_mse_missing"] = float(np.mean((labels - out["val_preds_missing"].reshape(-1)) ** 2))
+        out = super().results(store)
+        out["val_mse"] = out["val_mse_full"]
         return out
 
     def metrics(self, store):
@@ -182,28 +88,6 @@ class EvalResult:
         labels = torch.as_tensor(store.vals).cpu().numpy().reshape(-1)[rows]
         names = [store.names[i] for i in rows.tolist()]
         return {"full": eval_mosei_metric(preds[0][rows], labels, names), "missing": eval_mosei_metric(preds[1][rows], labels, names)}
-
-
-class _EvalArena:
-    """Device memory of evaluation, sized for the largest batch seen so far: the eval workspace, the forward's five [2 B, w] outputs
-    and two engine._InputSet (row maps, labels, lengths; padded input buffers and planes only once a batch is gathered)."""
-
-    def __init__(self, dev, B, T, fdims, dtype, nbytes):
-        self.B, self.T = int(B), tuple(int(t) for t in T)
-        self._fdims = fdims
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        V = 2 * self.B
-        self.outs = [torch.empty(V * k, device=dev) for k in (1, H, RNC_DIM, D, NQ * H)]
-        rows = [self.B * t for t in self.T]
-        self.sets = [engine._InputSet([r * d for r, d in zip(rows, fdims)], self.B, dtype, dev, rows) for _ in range(2)]
-
-    def fits(self, B, T, nbytes):
-        return B <= self.B and all(t <= c for t, c in zip(T, self.T)) and nbytes <= self.workspace.numel()
-
-    def ensure_planes(self):
-        for st in self.sets:
-            if st.planes is None:
-                st.planes = [engine._planes_buffer(r, d, self.workspace.device) for r, d in zip(st._rows, self._fdims)]
 
 
 class Evaluator:
@@ -224,12 +108,7 @@ class Evaluator:
         self._dims = {}       # (B, T) -> (sdumc_net_dims, workspace bytes)
 
     def _in_place(self, store):
-        """as FusedTrainer._in_place: fp32 storage and a store with planes, or bf16 storage and a bf16 store (widths % 128 == 0)"""
-        if not self.inplace:
-            return False
-        if self.feature_dtype == torch.bfloat16:
-            return store.packed['audio'].dtype == torch.bfloat16 and all(d % 128 == 0 for d in self.dims[:3])
-        return store.packed_p3 is not None and self._planes_ok
+        return epoch.in_place(self.inplace, self.feature_dtype, self._planes_ok, self.dims, store)
 
     def _shape(self, shape):
         """eval dims of one (B, T) and the workspace they need; a shape the engine refuses raises"""
@@ -243,19 +122,20 @@ class Evaluator:
             e = self._dims[shape] = (d, int(nb))
         return e
 
+    def _bytes(self, shapes):
+        """the byte sizes an arena for batches of `shapes` needs, in the order of the arena's .nbytes and of _new_arena"""
+        return (max(self._shape(s)[1] for s in shapes),)
+
+    def _new_arena(self, B, T, nbytes):
+        return engine._Arena(self.params.device, B, T, self._fdims, self.feature_dtype, nbytes)
+
     def _io(self, store, k, inplace, planes, key_padding):
         a, st = self.arena, self.arena.sets[k]
         io = _lib.NetIO()
         if inplace:
-            feats = [store.packed[m] for m in store.MODS]
-            p3 = [store.packed_p3[m] for m in store.MODS] if self.feature_dtype == torch.float32 else None
-            for i, m in enumerate(st.ensure_maps()):
-                io.row_map[i], io.store_rows[i] = ptr(m), int(feats[i].shape[0])
+            engine._bind_source(io, engine._store_source(store, st, st.labels))
         else:
-            feats, p3 = st.inputs, (st.planes if planes else None)
-        io.audio, io.text[0], io.video, io.text[1] = (ptr(t) for t in feats)
-        if p3 is not None:
-            io.audio_p3, io.text_p3[0], io.video_p3, io.text_p3[1] = (ptr(t) for t in p3)
+            engine._bind_source(io, engine._Source(st.inputs, st.planes if planes else None, None, (0,) * 4, st.labels))
         io.params, io.rng_state = ptr(self.params), None
         io.workspace, io.workspace_bytes = ptr(a.workspace), a.workspace.numel()
         io.vals, io.fused, io.rnc, io.text_hidden, io.cross_text = (ptr(t) for t in a.outs)
@@ -264,28 +144,6 @@ class Evaluator:
                 io.lengths[i] = ptr(t)
         io.prefetch_workgroups = self.prefetch_workgroups
         return io
-
-    def _desc(self, store, plan, i, inplace, planes, key_padding):
-        st = self.arena.sets[i & 1]
-        B, T = plan.shapes[i]
-        lens = st.lengths if key_padding else None
-        if inplace:
-            return store.gather_desc(plan.idx_ptr(i), B, T, None, st.labels, lens, maps_out=st.ensure_maps())
-        return store.gather_desc(plan.idx_ptr(i), B, T, st.inputs, st.labels, lens, st.planes if planes else None)
-
-    def _segments(self, res, B, embeddings):
-        """the scatter's segment table for batches of B: rows [0, B) of every output to stream 0's result, rows [B, 2 B) to stream 1's"""
-        pairs = [(self.arena.outs[0], res.preds, 1)]
-        if embeddings:
-            pairs += [(self.arena.outs[j + 1], res.embeddings[name], int(np.prod(shape))) for j, (name, shape, _) in enumerate(EMBEDDINGS)]
-        n = res.preds.shape[1]
-        segs = (_lib.ScatterSeg * (2 * len(pairs)))()
-        for j, (src, dst, w) in enumerate(pairs):
-            for s in range(2):
-                sg = segs[2 * j + s]
-                sg.src, sg.dst = src.data_ptr() + 4 * s * B * w, dst.data_ptr() + 4 * s * n * w
-                sg.rows, sg.cols, sg.dst_rows = B, w, n
-        return segs
 
     def _export(self, store, res):
         """the export's descriptor for one epoch (idx is set per batch): the store's device tables, the result's six tensors"""
@@ -299,67 +157,76 @@ class Evaluator:
                 e.dst[s][j], e.dst_rows[s][j] = ptr(t), int(t.shape[0])
         return e
 
-    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
-        n_store = len(store)
-        # ---- host-side checks: nothing is enqueued (and nothing of `out` is touched) before all of them have passed ----
+    def _prepare(self, what, store, batches, out, cls, spec, spec_text):
+        """The pre-flight of a read-only epoch `what` (the caller's name, for the messages): every host-side check, then the memory ->
+        (plan, result after reset, read in place?, planes gathered?).  cls / spec: the result's class and what its fits / empty take
+        after (n, device).  Nothing is enqueued and nothing of `out` is touched before all the checks have passed."""
+        n_store, dev = len(store), self.params.device
         plan, batches = checked_plan(batches, n_store)
-        if store.packed['audio'].device != self.params.device:
-            raise _lib.SdumcError("eval_epoch: the store and the parameters live on different devices")
+        if store.packed['audio'].device != dev:
+            raise _lib.SdumcError(f"{what}: the store and the parameters live on different devices")
         inplace = self._in_place(store)
         if not inplace and store.packed['audio'].dtype != self.feature_dtype:
-            raise _lib.SdumcError("eval_epoch: gathering needs a store that holds the features in the storage mode's dtype "
+            raise _lib.SdumcError(f"{what}: gathering needs a store that holds the features in the storage mode's dtype "
                                   "(a bf16 store for bf16 storage, an fp32 store otherwise)")
         if tuple(store.get_featdim()) != self._fdims:
-            raise _lib.SdumcError(f"eval_epoch: the store's feature widths {store.get_featdim()} are not {self._fdims}")
-        rows = attention_rows(store) if attention else None
-        if attention and min(rows.values()) < 1:
-            raise _lib.SdumcError("eval_epoch: attention=True needs a store with at least one frame per modality")
-        if out is not None and not (isinstance(out, EvalResult) and out.fits(n_store, self.params.device, embeddings, attention, rows)):
-            raise _lib.SdumcError("eval_epoch: out= is not a result of this store's size, device, embeddings and attention setting")
+            raise _lib.SdumcError(f"{what}: the store's feature widths {store.get_featdim()} are not {self._fdims}")
+        if out is not None and not (isinstance(out, cls) and out.fits(n_store, dev, *spec)):
+            raise _lib.SdumcError(f"{what}: out= is not a result of this store's size, device, {spec_text}")
         if plan is None:
             plan = store.plan_epoch(batches)
         shapes = set(plan.shapes)
-        need = max(self._shape(s)[1] for s in shapes)
+        nbytes = self._bytes(shapes)
         Bmax, Tmax = max(B for B, _ in shapes), tuple(max(T[i] for _, T in shapes) for i in range(4))
-        # ---- memory ----
+        # ---- memory: an arena too small for this epoch gives way to one that holds both (it never shrinks) ----
         a = self.arena
-        if a is None or not a.fits(Bmax, Tmax, need):
+        if a is None or not a.fits(Bmax, Tmax, *nbytes):
             if a is not None:
-                Bmax, Tmax, need = max(Bmax, a.B), tuple(max(t, c) for t, c in zip(Tmax, a.T)), max(need, a.workspace.numel())
-            a = self.arena = _EvalArena(self.params.device, Bmax, Tmax, self._fdims, self.feature_dtype, need)
-        planes = False
-        if not inplace and store.packed_p3 is not None and self._planes_ok:
-            a.ensure_planes()
-            planes = True
-        res = (out if out is not None else EvalResult.empty(n_store, self.params.device, embeddings, attention, rows)).reset()
+                Bmax, Tmax = max(Bmax, a.B), tuple(max(t, c) for t, c in zip(Tmax, a.T))
+                nbytes = tuple(max(x, y) for x, y in zip(nbytes, a.nbytes))
+            a = self.arena = self._new_arena(Bmax, Tmax, *nbytes)
+        planes = not inplace and store.packed_p3 is not None and self._planes_ok and a.ensure_planes()
+        res = (out if out is not None else cls.empty(n_store, dev, *spec)).reset()
+        return plan, res, inplace, planes
+
+    def _run(self, store, plan, res, inplace, planes, key_padding, embeddings, middle=None):
+        """epoch.run for a read-only epoch: per batch one forward, middle(i, k, d, io, stream) when given, one scatter of the forward's
+        outputs to the store's rows of `res`.  No host synchronisation inside."""
+        a = self.arena
         ios = [self._io(store, k, inplace, planes, key_padding) for k in range(2)]
-        exp = self._export(store, res) if attention else None
         segs, mark, st = {}, ptr(res.seen), _lib.current_stream()
-        # ---- the epoch: no host synchronisation from here on ----
-        n = len(plan)
-        g = self._desc(store, plan, 0, inplace, planes, key_padding)
-        check(lib.sdumc_gather_batch(C.byref(g), 0, st), "sdumc_gather_batch")
-        nxt = self._shape(plan.shapes[0])[0]
-        for i in range(n):
-            d, io, B = nxt, ios[i & 1], plan.shapes[i][0]
+
+        def forward(cur, nxt, pf):
+            _, d, io = cur
+            check(epoch.with_prefetch(io, pf, lib.sdumc_net_forward, C.byref(d), C.byref(io), st), "sdumc_net_forward")
+
+        def tail(i, cur):
+            B = plan.shapes[i][0]
             sg = segs.get(B)
             if sg is None:
-                sg = segs[B] = self._segments(res, B, embeddings)
-            pf = None
-            if i + 1 < n:
-                nxt = self._shape(plan.shapes[i + 1])[0]
-                pf = self._desc(store, plan, i + 1, inplace, planes, key_padding)
-            io.prefetch = C.addressof(pf) if pf is not None else None
-            try:
-                check(lib.sdumc_net_forward(C.byref(d), C.byref(io), st), "sdumc_net_forward")
-            finally:
-                io.prefetch = None
-            if exp is not None:      # (the workspace holds this batch's weights until the next forward into it)
+                sg = segs[B] = epoch.scatter_segments(a.outs, res, B, embeddings)
+            if middle is not None:
+                middle(i, *cur, st)
+            check(lib.sdumc_scatter_rows_multi(sg, len(sg), plan.idx_ptr(i), B, mark, st), "sdumc_scatter_rows_multi")
+
+        epoch.run(self, store, plan, a.sets, key_padding, planes, inplace, lambda B, T: self._shape((B, T))[0],
+                  lambda d, k: (k, d, ios[k]), forward, tail)
+        return res
+
+    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
+        rows = attention_rows(store) if attention else None
+        if attention and min(rows.values()) < 1:
+            raise _lib.SdumcError("eval_epoch: attention=True needs a store with at least one frame per modality")
+        plan, res, inplace, planes = self._prepare("eval_epoch", store, batches, out, EvalResult, (embeddings, attention, rows),
+                                                   "embeddings and attention setting")
+        middle = None
+        if attention:
+            exp = self._export(store, res)
+
+            def middle(i, k, d, io, st):      # (the workspace holds this batch's weights until the next forward into it)
                 exp.idx = plan.idx_ptr(i)
                 check(lib.sdumc_net_export_attention(C.byref(d), C.byref(io), C.byref(exp), st), "sdumc_net_export_attention")
-            check(lib.sdumc_scatter_rows_multi(sg, len(sg), plan.idx_ptr(i), B, mark, st), "sdumc_scatter_rows_multi")
-        self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers and scatters)
-        return res
+        return self._run(store, plan, res, inplace, planes, key_padding, embeddings, middle)
 
 
 _evaluator = None      # eval_epoch's state: ONE evaluator (the last parameter buffer / mode asked for), so its arena is kept across epochs

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import lib
-from .evaluate import EMBEDDINGS
+from .epoch import StoreOrdered
 
 LOG_COLS = _lib.LOG_COLS
 # columns 0..7 of a log row: the step's loss vector (sdumc_step_cfg.losses).  Entries 3..5 hold the chosen distillation criterion's
@@ -175,7 +175,7 @@ class TensorNorms:
         return None if hit.shape[0] == 0 else (int(hit[0, 0]), self.names[int(hit[0, 1])])
 
 
-class TrainRecord:
+class TrainRecord(StoreOrdered):
     """One training epoch's record.  log [capacity, 12]: row i = step i (columns 0..7 the loss vector as the step wrote it, 8 grad_norm,
     9 non-finite gradient elements, 10 B, 11 learning rate; 8 is NaN and 9 is 0 when the epoch ran without grad_norm); steps = the rows
     the last epoch filled.  In STORE order, as evaluate.EvalResult: preds [2, N] (row 0 the full stream, row 1 the text-missing one,
@@ -208,18 +208,16 @@ class TrainRecord:
         """n utterances, room for n_steps steps; n_grads > 0: with the scratch of a gradient bucket of that many floats;
         by_tensor=True | 'updates' (with layout, the run's engine.ParamLayout): with the record by tensor (TensorNorms);
         guard=True: with the [n_steps, 4] guard column"""
-        emb = scratch = bt = None
+        scratch = bt = None
         mode = by_tensor_mode(by_tensor)
         if mode:
             if layout is None:
                 raise _lib.SdumcError("TrainRecord.empty: by_tensor needs layout= (the run's ParamLayout)")
             bt = TensorNorms.empty(layout, n_steps, device, updates=mode == "updates")
-        if embeddings:
-            emb = {name: torch.empty((2, n) + shape, device=device) for name, shape, _ in EMBEDDINGS}
         if n_grads > 0:
             scratch = torch.zeros(int(lib.sdumc_epoch_record_scratch_bytes(int(n_grads))), dtype=torch.uint8, device=device)
-        return cls(torch.empty(int(n_steps), LOG_COLS, device=device), torch.empty(2, n, device=device),
-                   torch.empty(n, dtype=torch.uint8, device=device), emb, 0, scratch, n_grads if n_grads > 0 else 0, bt,
+        return cls(torch.empty(int(n_steps), LOG_COLS, device=device), *cls._empty(n, device, embeddings), 0, scratch,
+                   n_grads if n_grads > 0 else 0, bt,
                    torch.empty(int(n_steps), 4, device=device) if guard else None)
 
     def fits(self, n, n_steps, device, embeddings, n_grads=0, by_tensor=False, layout=None, guard=False):
@@ -234,22 +232,16 @@ class TrainRecord:
             return False
         if mode and (layout is None or not self.by_tensor.fits(layout, n_steps, device, mode == "updates")):
             return False
-        return (self.preds.shape == (2, n) and self.preds.device == dev and self.seen.numel() == n and self.seen.element_size() == 1
+        return (self._fits(n, dev)
                 and self.log.dim() == 2 and self.log.shape[1] == LOG_COLS and self.log.shape[0] >= n_steps and self.log.device == dev
                 and self.log.is_contiguous() and (self.embeddings is not None) == bool(embeddings)
                 and max(0, int(n_grads)) == self.n_grads)
 
     def reset(self):
         """NaN everywhere -- unused log rows included --, nothing seen, no step filled: once per epoch, in front of its first step"""
-        self.log.fill_(float("nan"))
-        self.preds.fill_(float("nan"))
-        self.seen.zero_()
-        for t in (self.embeddings or {}).values():
-            t.fill_(float("nan"))
+        self._reset(self.log, *(() if self.guard is None else (self.guard,)))
         if self.by_tensor is not None:
             self.by_tensor.reset()
-        if self.guard is not None:
-            self.guard.fill_(float("nan"))
         self.steps = 0
         return self
 
@@ -258,29 +250,6 @@ class TrainRecord:
         if self.guard is None:
             raise _lib.SdumcError("TrainRecord.skipped_steps: the epoch ran without clip_norm / skip_nonfinite")
         return np.flatnonzero(self.guard[:self.steps, 3].cpu().numpy() != 0).tolist()
-
-    def _visited(self):
-        rows = np.flatnonzero(self.seen.cpu().numpy().reshape(-1) != 0)
-        if rows.size == 0:
-            raise _lib.SdumcError("TrainRecord: no row was visited")
-        return rows
-
-    def results(self, store):
-        """The dictionary the reference's training pass returns (main :168-175) over the visited rows in store order: val_mse_full,
-        val_mse_missing, val_preds_full [n, 1], val_preds_missing [n, 1], val_labels, names -- the MSE as EvalResult.results takes it;
-        with embeddings also EvalResult.results' embedding keys.  One device -> host copy per tensor."""
-        rows = self._visited()
-        preds = self.preds.cpu().numpy()
-        labels = torch.as_tensor(store.vals).cpu().numpy().astype(np.float32).reshape(-1)[rows]
-        out = {"val_preds_full": preds[0][rows].reshape(-1, 1), "val_preds_missing": preds[1][rows].reshape(-1, 1),
-               "val_labels": labels}
-        for name, _, keys in EMBEDDINGS if self.embeddings is not None else ():
-            t = self.embeddings[name].cpu().numpy()
-            out[keys[0]], out[keys[1]] = t[0][rows], t[1][rows]
-        out["names"] = [store.names[i] for i in rows.tolist()]
-        out["val_mse_full"] = float(np.mean((labels - out["val_preds_full"].reshape(-1)) ** 2))
-        out["val_mse_missing"] = float(np.mean((labels - out["val_preds_missing"].reshape(-1)) ** 2))
-        return out
 
     def summary(self):
         """The epoch in a few numbers, float64 on the host from log[:steps] (one copy): the B-weighted mean of each of the 8 loss entries

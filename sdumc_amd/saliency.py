@@ -8,9 +8,8 @@ utterance i and frame t < length_m[i], with g = d vals_out_s[i] / d feat_m[i, t,
     column 0 ('grad_x_input')  sum_c g[c] * feat_m[i, t, c]      gradient x input, signed
     column 1 ('grad_norm')     sqrt(sum_c g[c]^2)                gradient norm
 
-`saliency_epoch` has the shape of evaluate.Evaluator.eval_epoch: the epoch's index vectors are uploaded once, forward i
-(sdumc_net_forward, eval mode, both streams) carries the assembly of batch i + 1 (sdumc_net_io.prefetch), batches are read in place
-through row maps where the store allows it, and nothing crosses to the host inside the loop.  In eval mode the samples of a batch do
+`saliency_epoch` is evaluate.Evaluator.eval_epoch's loop (epoch.run has its definition) with the feature-gradient backwards between
+the forward (sdumc_net_forward, eval mode, both streams) and the scatter.  In eval mode the samples of a batch do
 not interact, so ONE backward (sdumc_net_backward) seeded with d_vals = 1 on the rows of stream s, 0 on the other stream's rows and
 every other output gradient NULL gives all per-sample feature gradients of that stream at once (the other stream adds exact zeros to
 the summed d_audio / d_video).  Per batch: one forward; per requested stream one backward with exactly the feature-gradient pointers
@@ -32,7 +31,8 @@ import torch
 
 from . import _lib, engine
 from ._lib import lib, check, ptr
-from .evaluate import ATTENTION as STREAMS, MODS, Evaluator, _EvalArena, attention_rows, checked_plan
+from .epoch import MODS, StoreOrdered, rows_dict
+from .evaluate import ATTENTION as STREAMS, Evaluator, attention_rows
 
 COLUMNS = ("grad_x_input", "grad_norm")
 NCOL = _lib.SALIENCY_COLS
@@ -65,13 +65,7 @@ def _stream_names(streams):
     return tuple(s for s in names if s in streams)
 
 
-def _rows_dict(rows):
-    if not isinstance(rows, dict):
-        rows = dict(zip(MODS, rows))
-    return {m: int(rows[m]) for m in MODS}
-
-
-class SaliencyResult:
+class SaliencyResult(StoreOrdered):
     """Results of one saliency epoch in STORE order: preds [2, N] (row 0 the full stream, row 1 the text-missing one), seen [N]
     (uint8: visited this epoch), maps {'full': {'audio', 'text', 'video'}, 'missing': {'audio', 'feat4', 'video'}} -- the requested
     streams only -- of [rows_m, 2] fp32 tensors, rows_m = the frames of all utterances of that modality in store order (row start[i] + t
@@ -85,50 +79,26 @@ class SaliencyResult:
     @classmethod
     def empty(cls, n, device, rows, streams=("full", "missing")):
         """rows = frame_rows(store) (or the four row counts, audio / text / video / feat4)"""
-        rows, streams = _rows_dict(rows), _stream_names(streams)
+        rows, streams = rows_dict(rows), _stream_names(streams)
         maps = {s: {m: torch.empty(rows[m], NCOL, device=device) for m in mods} for s, mods in STREAMS if s in streams}
-        return cls(torch.empty(2, n, device=device), torch.empty(n, dtype=torch.uint8, device=device), maps)
+        return cls(*cls._empty(n, device)[:2], maps)
 
     def fits(self, n, device, rows, streams=("full", "missing")):
-        rows, streams, device = _rows_dict(rows), _stream_names(streams), torch.device(device)
-        ok = (self.preds.shape == (2, n) and self.preds.device == device and self.seen.numel() == n
-              and self.seen.element_size() == 1 and tuple(self.maps) == streams)
-        return ok and all(m in self.maps[s] and self.maps[s][m].shape == (rows[m], NCOL) and self.maps[s][m].device == device
-                          and self.maps[s][m].dtype == torch.float32 and self.maps[s][m].is_contiguous()
-                          for s, mods in STREAMS if s in streams for m in mods)
+        rows, streams = rows_dict(rows), _stream_names(streams)
+        return (self._fits(n, device) and tuple(self.maps) == streams
+                and self._frames_fit(self.maps, [(s, mods) for s, mods in STREAMS if s in streams], rows, NCOL, device))
 
     def reset(self):
         """NaN everywhere, nothing seen: once per epoch, in front of its first batch"""
-        self.preds.fill_(float("nan"))
-        self.seen.zero_()
-        for d in self.maps.values():
-            for t in d.values():
-                t.fill_(float("nan"))
-        return self
+        return self._reset(*(t for d in self.maps.values() for t in d.values()))
 
     def of(self, store, i):
         """The maps of ONE utterance -- i = its index in the store, or its name -- as views: {stream: {modality: [T_i, 2]}}, sliced by
         the store's start / length tables.  Raises when the utterance is unknown or was not visited in this epoch."""
-        if isinstance(i, str):
-            try:
-                i = store.names.index(i)
-            except ValueError:
-                raise _lib.SdumcError(f"SaliencyResult: no utterance named {i!r} in the store") from None
-        i = int(i)
-        if not 0 <= i < self.seen.numel():
-            raise _lib.SdumcError(f"SaliencyResult: utterance index {i} out of range [0, {self.seen.numel()})")
-        if int(self.seen.reshape(-1)[i]) == 0:
-            raise _lib.SdumcError(f"SaliencyResult: utterance {i} was not visited in this epoch")
-        out = {}
-        for s, d in self.maps.items():
-            out[s] = {}
-            for m, t in d.items():
-                a, n = int(store.start[m][i]), int(store.length[m][i])
-                out[s][m] = t[a:a + n]
-        return out
+        return self._frames_of(store, i, self.maps)
 
 
-class _SaliencyArena(_EvalArena):
+class _SaliencyArena(engine._Arena):
     """Device memory of saliency epochs, sized for the largest batch seen so far: what evaluation holds (the eval workspace, the
     forward's five outputs, two input sets) plus the packed frame weights' scratch of the feature-gradient backward, a zeroed gradient
     bucket that backward may overwrite, the four padded d_feat buffers and two d_vals seed vectors per batch size."""
@@ -139,6 +109,10 @@ class _SaliencyArena(_EvalArena):
         self.bucket = torch.zeros(live, device=dev)
         self.d_feat = [torch.empty(self.B * t * d, device=dev) for t, d in zip(self.T, fdims)]
         self._seeds = {}
+
+    @property
+    def nbytes(self):
+        return (self.workspace.numel(), self.feat_scratch.numel())
 
     def fits(self, B, T, nbytes, scratch_bytes):
         return super().fits(B, T, nbytes) and scratch_bytes <= self.feat_scratch.numel()
@@ -200,74 +174,36 @@ class Saliency(Evaluator):
         """one stream's three feature gradients -> its maps (tools/saliency_bench.py times the epoch without this launch)"""
         check(lib.sdumc_frame_saliency(descs, len(descs), idx_ptr, st), "sdumc_frame_saliency")
 
-    def saliency_epoch(self, store, batches, key_padding=False, streams=("full", "missing"), out=None):
-        n_store = len(store)
-        # ---- host-side checks: nothing is enqueued (and nothing of `out` is touched) before all of them have passed ----
-        streams = _stream_names(streams)
-        plan, batches = checked_plan(batches, n_store)
-        if self.feature_dtype != torch.float32 or store.packed['audio'].dtype != torch.float32:
-            raise _lib.SdumcError("saliency_epoch: feature gradients exist in fp32 storage only (not in bf16 storage, not from a bf16 store)")
-        if store.packed['audio'].device != self.params.device:
-            raise _lib.SdumcError("saliency_epoch: the store and the parameters live on different devices")
-        if tuple(store.get_featdim()) != self._fdims:
-            raise _lib.SdumcError(f"saliency_epoch: the store's feature widths {store.get_featdim()} are not {self._fdims}")
-        rows = frame_rows(store)
-        if min(rows.values()) < 1:
-            raise _lib.SdumcError("saliency_epoch: needs a store with at least one frame per modality")
-        if out is not None and not (isinstance(out, SaliencyResult) and out.fits(n_store, self.params.device, rows, streams)):
-            raise _lib.SdumcError("saliency_epoch: out= is not a result of this store's size, device, frames and streams")
-        inplace = self._in_place(store)
-        if plan is None:
-            plan = store.plan_epoch(batches)
-        shapes = set(plan.shapes)
-        need = max(self._shape(s)[1] for s in shapes)
+    def _bytes(self, shapes):
         scratch = max(self._scratch_bytes(s) for s in shapes)
         if scratch < 1:
             raise _lib.SdumcError("saliency_epoch: the engine has no feature gradients for these dims")
-        Bmax, Tmax = max(B for B, _ in shapes), tuple(max(T[i] for _, T in shapes) for i in range(4))
-        # ---- memory ----
-        a = self.arena
-        if a is None or not a.fits(Bmax, Tmax, need, scratch):
-            if a is not None:
-                Bmax, Tmax = max(Bmax, a.B), tuple(max(t, c) for t, c in zip(Tmax, a.T))
-                need, scratch = max(need, a.workspace.numel()), max(scratch, a.feat_scratch.numel())
-            a = self.arena = _SaliencyArena(self.params.device, Bmax, Tmax, self._fdims, need, scratch, self._live)
-        planes = False
-        if not inplace and store.packed_p3 is not None and self._planes_ok:
-            a.ensure_planes()
-            planes = True
-        res = (out if out is not None else SaliencyResult.empty(n_store, self.params.device, rows, streams)).reset()
-        ios = [self._io(store, k, inplace, planes, key_padding) for k in range(2)]
+        return super()._bytes(shapes) + (scratch,)
+
+    def _new_arena(self, B, T, nbytes, scratch_bytes):
+        return _SaliencyArena(self.params.device, B, T, self._fdims, nbytes, scratch_bytes, self._live)
+
+    def saliency_epoch(self, store, batches, key_padding=False, streams=("full", "missing"), out=None):
+        # ---- saliency's own refusals, then the pre-flight it shares with eval_epoch ----
+        streams = _stream_names(streams)
+        if self.feature_dtype != torch.float32 or store.packed['audio'].dtype != torch.float32:
+            raise _lib.SdumcError("saliency_epoch: feature gradients exist in fp32 storage only (not in bf16 storage, not from a bf16 store)")
+        rows = frame_rows(store)
+        if min(rows.values()) < 1:
+            raise _lib.SdumcError("saliency_epoch: needs a store with at least one frame per modality")
+        plan, res, inplace, planes = self._prepare("saliency_epoch", store, batches, out, SaliencyResult, (rows, streams),
+                                                   "frames and streams")
         wanted = [(s, name) for s, (name, _) in enumerate(STREAMS) if name in streams]
-        for B in {B for B, _ in shapes}:
-            a.seeds(B)
-        segs, mark, st = {}, ptr(res.seen), _lib.current_stream()
-        # ---- the epoch: no host synchronisation from here on ----
-        n = len(plan)
-        g = self._desc(store, plan, 0, inplace, planes, key_padding)
-        check(lib.sdumc_gather_batch(C.byref(g), 0, st), "sdumc_gather_batch")
-        nxt = self._shape(plan.shapes[0])[0]
-        for i in range(n):
-            d, io, (B, T) = nxt, ios[i & 1], plan.shapes[i]
-            sg = segs.get(B)
-            if sg is None:
-                sg = segs[B] = self._segments(res, B, False)
-            pf = None
-            if i + 1 < n:
-                nxt = self._shape(plan.shapes[i + 1])[0]
-                pf = self._desc(store, plan, i + 1, inplace, planes, key_padding)
-            io.prefetch = C.addressof(pf) if pf is not None else None
-            try:
-                check(lib.sdumc_net_forward(C.byref(d), C.byref(io), st), "sdumc_net_forward")
-            finally:
-                io.prefetch = None
-            for s, name in wanted:      # (the backward leaves the forward's part of the workspace as it is: one forward serves both)
+        for B in {B for B, _ in plan.shapes}:
+            self.arena.seeds(B)
+
+        def backwards(i, k, d, io, st):      # (the backward leaves the forward's part of the workspace as it is: one forward serves both)
+            B, T = plan.shapes[i]
+            for s, name in wanted:
                 ng = self._grads(s, B)
                 check(lib.sdumc_net_backward(C.byref(d), C.byref(io), C.byref(ng), st), "sdumc_net_backward")
-                self._reduce(self._saliency_descs(store, res, name, s, i & 1, B, T, inplace), plan.idx_ptr(i), st)
-            check(lib.sdumc_scatter_rows_multi(sg, len(sg), plan.idx_ptr(i), B, mark, st), "sdumc_scatter_rows_multi")
-        self._keep_plan = plan      # (the index tensor must outlive the enqueued gathers and scatters)
-        return res
+                self._reduce(self._saliency_descs(store, res, name, s, k, B, T, inplace), plan.idx_ptr(i), st)
+        return self._run(store, plan, res, inplace, planes, key_padding, False, backwards)
 
 
 _saliency = None      # saliency_epoch's state: ONE object (the last parameter buffer asked for), so its arena is kept across epochs

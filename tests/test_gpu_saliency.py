@@ -409,6 +409,39 @@ def test_composition_bit_for_bit(env, L, key, key_padding):
         part.of(store, BATCHES[0][0])
 
 
+def _snapshot(res):
+    torch.cuda.synchronize()
+    return [res.preds.clone(), res.seen.float()] + [t.clone() for d in res.maps.values() for t in d.values()]
+
+
+@pytest.mark.parametrize("key", list(SHAPES))
+def test_a_later_epoch_grows_the_arena_and_an_earlier_plan_reuses_it(env, key):
+    """ONE Saliency object and ONE result (out= throughout) over an epoch of small batches, then over one whose largest batch has more
+    samples and a longer T in every modality: the arena gives way to a larger one and the epoch holds the bits of a fresh object's;
+    a third epoch over the first plan runs in the grown arena (the same workspace) and reproduces the first bit for bit."""
+    store, flat, dims = env.store[key], env.flat[key], SHAPES[key]
+    small = [torch.tensor(b, dtype=torch.int64) for b in ((3,), (6, 1))]
+    large = [torch.tensor(b, dtype=torch.int64) for b in ((4, 0, 2, 5), (6, 1, 3))]
+    sal = env.S.Saliency(flat, dims)
+    out = sal.saliency_epoch(store, small)
+    one, first = _snapshot(out), sal.arena
+    assert first.B == 2 and int((out.seen != 0).sum()) == 3 and bool(torch.isnan(out.maps["full"]["audio"]).any())
+    assert sal.saliency_epoch(store, large, out=out) is out
+    two, grown = _snapshot(out), sal.arena
+    assert grown is not first and grown.B == 4 and all(t > c for t, c in zip(grown.T, first.T))
+    fresh = _snapshot(env.S.Saliency(flat, dims).saliency_epoch(store, large))
+    assert int((out.seen != 0).sum()) == 7 and len(two) == len(fresh) == 8      # (every row visited: no NaN to step around)
+    for x, y in zip(two, fresh):
+        assert torch.equal(x, y)
+    ws = grown.workspace.data_ptr()
+    assert sal.saliency_epoch(store, small, out=out) is out
+    three = _snapshot(out)
+    assert sal.arena is grown and sal.arena.workspace.data_ptr() == ws and (sal.arena.B, sal.arena.T) == (4, grown.T)
+    for x, y in zip(three, one):
+        assert torch.equal(torch.isnan(x), torch.isnan(y)) and torch.equal(torch.nan_to_num(x), torch.nan_to_num(y))
+    assert bool(torch.isnan(three[0][:, [0, 2, 4, 5]]).all()) and bool(torch.isfinite(three[0][:, [1, 3, 6]]).all())
+
+
 @pytest.mark.parametrize("key", list(SHAPES))
 def test_predictions_are_eval_epochs(env, key):
     for kp in (False, True):
