@@ -1156,7 +1156,12 @@ typedef struct sdumc_net_io {
    * and widths multiples of 4; the packed tensors 16-byte aligned):
    * sdumc_net_backward, sdumc_net_backward_phase (EITHER phase) and sdumc_train_step decide their schedule first and return
    * SDUMC_EINVAL before anything of the call is enqueued -- no fill, no fork, for sdumc_train_step no forward and no loss stage;
-   * sdumc_net_forward does not read the fp32 tensors and accepts such a batch.  The bf16 weight-gradient kernel reads map entries four at a time: each map must be
+   * sdumc_net_forward does not read the fp32 tensors and accepts such a batch.  What the forward needs is a frame projection that
+   * reads through a map -- the plane GEMM (fp32 storage: planes given, SDUMC_P3 not 0, the wide-tile family's split arithmetic on:
+   * sdumc_set_split_ bit 1) or the fragment-major bf16 GEMM (bf16 storage: widths multiples of 128, SDUMC_P3 not 0); without one
+   * sdumc_net_forward and sdumc_train_step, which decide the forward's schedule first as well, return SDUMC_EINVAL before anything
+   * of the call is enqueued -- no lengths expansion, no fork, no event.
+   * The bf16 weight-gradient kernel reads map entries four at a time: each map must be
    * readable up to a multiple of four entries.  store_rows[i] (optional): rows of packed tensor i -- tensors (and planes) below
    * 4 GiB keep the kernels' descriptor addressing, which is faster than 64-bit addresses; 0 = unknown. */
   const int32_t* row_map[4];

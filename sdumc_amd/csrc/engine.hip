@@ -1072,6 +1072,64 @@ sdumc_attnpool attn_desc(const Ctx& c, int k, int m, const Seg& sg) {
   return a;
 }
 
+// The path of the utterance-level stages, decided once per call (plan_utterance).  Both schedules ARE one (FwdSchedule, BwdSchedule
+// derive from it), so a forward and the backward behind it cannot disagree, and the helpers both directions share -- chain_launch,
+// chain_args -- read it instead of asking again.
+struct UttPath {
+  bool chain = false;      // chain.hip / chain_cluster.hip: one launch per stage and direction instead of one per layer
+  bool cluster = false;    // ... the clustered kernels (chain_cluster.hip)
+  bool fra_fold = false;   // ... which combine the pooled sites' softmax partials (forward) and sum the dq slabs of 8' (backward) themselves
+};
+
+// The forward pass's schedule: plan_forward() decides it ONCE, before the first launch; forward(), its parts and the helpers they
+// call read the record.
+struct FwdSchedule : UttPath {
+  int rc = SDUMC_OK;               // SDUMC_EINVAL: the schedule cannot serve the io (row maps without a route that reads through them)
+  // the kernel family of the frame projections frame_dim_reshape_m and of the key projections behind them, one per call
+  enum Route {
+    P3,           // fp32 storage, features also given as bf16 planes: gemm_p3.hip, operands split once per tensor
+    B1,           // bf16 storage, widths in whole 128-element tiles: gemm_b1.hip, the weight fragment-major
+    BF16_TILES,   // bf16 storage otherwise (or SDUMC_P3=0): gemm_bf16.hip's LDS-staged tiles
+    F32           // lin_fwd: gemm_wide.hip / gemm_f32.hip (bf16 = 1: operands rounded while staged)
+  } route = F32;
+  struct Proj {                    // frame_dim_reshape_m on stream s (audio / video: s = 0 serves both streams)
+    int rows = 0;                  // B * T
+    bool both = false;             // text slot, s = 0: this launch also projects stream 1 (no launch for s = 1)
+    int splitk = 0;                // P3 / B1: K over this many workgroups (0 auto, 1 none); F32: the wide kernel's split (0: the launcher picks)
+    int tile = 0;                  // F32: sdumc_gemm.tile (14 = the wide LDS-DMA kernel)
+  } proj[3][2];
+  enum Bits { BITS_NONE, BITS_LANE3, BITS_WITH_XD } bits = BITS_NONE;   // where the keep-bits of the frame-level input dropouts come from
+  bool pregen = false;             // sdumc_net_io.bits_next: the head finds this call's set (tagged), the middle fills the next call's
+  bool wh_copies = false;          // bf16 storage: row-major / transposed bf16 copies of the frame-level weights ...
+  bool wh_lane3 = false;           // ... made on lane 3 (the forward itself reads fragment-major copies: B1)
+  bool wh_utterance = false;       // ... and of the utterance-level matrices chain.hip streams
+  bool refresh_wt = false;         // the transposed fp32 mirror of the utterance-level weights is refreshed (lane 3)
+  bool umca_planes = false;        // the fused projection + pooling kernel projects on planes
+  bool pool_grouped = false;       // 8: the Cross_Attention pooling of all modalities as ONE launch on the caller's stream (else fork / join)
+  enum CaKeys {                    // where a modality's Cross_Attention key projection runs
+    OWN_LANE_PARTIAL_JOIN,         // on the modality's lane, BEHIND the event the caller's stream waits for (the FRA2UTT site)
+    LANE3,                         // on the background lane, beside steps 2-7
+    INLINE,                        // on the modality's lane, behind the fused FRA2UTT kernel
+    INLINE_GROUPED_WITH_SITE0      // one grouped launch with the FRA2UTT key projection
+  };
+  struct Mod {
+    bool k3_site0 = false;         // FRA2UTT site: the fused projection + pooling kernel (K3) instead of the GEMM + pooling pair
+    CaKeys ca_keys = INLINE_GROUPED_WITH_SITE0;
+  } mod[3];
+};
+
+int din_of(const Ctx& c, int m) { return m == 0 ? c.d.da : (m == 1 ? c.d.dt : c.d.dv); }
+const float* feat_in(const Ctx& c, int m, int s) { return m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]); }
+const void* feat_p3(const Ctx& c, int m, int s) { return m == 0 ? c.io.audio_p3 : (m == 2 ? c.io.video_p3 : c.io.text_p3[s]); }
+// the row map of modality m's features, stream s (sdumc_net_io.row_map is ordered audio, text, video, feat4) or nullptr
+int feat_slot(int m, int s) { return m == 0 ? 0 : (m == 2 ? 2 : (s == 0 ? 1 : 3)); }
+const int32_t* feat_map(const Ctx& c, int m, int s) { return c.io.row_map[feat_slot(m, s)]; }
+// rows of the packed tensor(s) a mapped launch reads (the larger when it reads two; 0 = unknown: 64-bit addressing)
+int64_t feat_store_rows(const Ctx& c, int m, int s, bool both) {
+  const int64_t a = c.io.store_rows[feat_slot(m, s)], b = both ? c.io.store_rows[feat_slot(m, 1)] : a;
+  return (a > 0 && b > 0) ? std::max(a, b) : 0;
+}
+
 // keys = tanh(drop(x) W^T + b) of the attention sites [k0, k1) of modality m (FRA2UTT_new = 0, Cross_Attention = 1:
 // they read the same x with different masks and weights).  Both in one grouped launch fill the last dispatch round
 // of the 64x64 tiles better; one at a time lets the Cross_Attention half run on the background lane.
@@ -1091,53 +1149,74 @@ sdumc_gemm_bf16 GH_(int layout, int M, int N, int K, int groups = 1) {
   return g;
 }
 
-// bf16 storage: the NT products of the frame-level forward through gemm_b1.hip (the weight fragment-major, straight into registers).
-// SDUMC_P3=0 (the switch of "operands prepared once per tensor", shared with the fp32 planes path): A/B against gemm_bf16.hip's LDS-staged tiles.
+// Operands prepared once per tensor.  fp32 storage with the features also given as bf16 planes (sdumc_net_io.*_p3): the frame
+// projections and the key projections that would go through the wide NT kernel run on operands split once per tensor (gemm_p3.hip).
+// bf16 storage: the same NT products through gemm_b1.hip (the weight fragment-major, straight into registers).
+// SDUMC_P3=0 (one switch for both): A/B against the in-kernel split / against gemm_bf16.hip's LDS-staged tiles.
 bool prepared_operands_on() {
   static const int on = [] { const char* e = getenv("SDUMC_P3"); return e ? atoi(e) : 1; }();
   return on != 0;
 }
-bool b1_mode(const Ctx& c) { return prepared_operands_on() && c.h() && c.pl.wb1 != 0; }
+FwdSchedule::Route frame_route(const Ctx& c) {
+  if (c.h()) return prepared_operands_on() && c.pl.wb1 != 0 ? FwdSchedule::B1 : FwdSchedule::BF16_TILES;
+  const bool planes = prepared_operands_on() && c.d.bf16 == 0 && c.pl.wp3 != 0 && c.io.audio_p3 != nullptr && sdumc_split_on_(SDUMC_SPLIT_WIDE);
+  return planes ? FwdSchedule::P3 : FwdSchedule::F32;
+}
 char* wb1_ptr(const Ctx& c, int64_t byte_off) { return reinterpret_cast<char*>(c.p(c.pl.wb1)) + byte_off; }
-// modality m's three frame-level weights (frame_dim_reshape_m, the two input_proj) -> fragment-major bf16: one small launch at the head
-// of the modality's lane
-int b1_refresh_weights(const Ctx& c, int m) {
-  const int din[3] = {c.d.da, c.d.dt, c.d.dv};
+char* wp3_ptr(const Ctx& c, int64_t byte_off) { return reinterpret_cast<char*>(c.p(c.pl.wp3)) + byte_off; }
+// modality m's three frame-level weights (frame_dim_reshape_m, the two input_proj) in the route's form -- fragment-major planes (P3)
+// or fragment-major bf16 (B1): one small launch at the head of the modality's lane (the weights change every step)
+int refresh_frame_weight_forms(const Ctx& c, const FwdSchedule& fs, int m) {
   int64_t so[3], dofs[3];
   int32_t rows[3], cols[3];
-  so[0] = c.pm.frame[m].w; dofs[0] = c.pl.wp3_frame[m]; rows[0] = D; cols[0] = din[m];
+  so[0] = c.pm.frame[m].w; dofs[0] = c.pl.wp3_frame[m]; rows[0] = D; cols[0] = din_of(c, m);
   so[1] = c.pm.fra_proj[m].w; dofs[1] = c.pl.wp3_key[0][m]; rows[1] = D; cols[1] = D;
   so[2] = c.pm.ca_in[m].w; dofs[2] = c.pl.wp3_key[1][m]; rows[2] = D; cols[2] = D;
+  if (fs.route == FwdSchedule::P3) return sdumc_p3_split_frag_multi_(c.P, wp3_ptr(c, 0), so, dofs, rows, cols, 3, c.st);
   return sdumc_b1_frag_multi(c.P, wb1_ptr(c, 0), so, dofs, rows, cols, 3, c.st);
 }
-// frame_dim_reshape_m on bf16 features: x (bf16) of stream s (and, with feat2, of the next stream in the adjacent rows)
-const int32_t* feat_map(const Ctx& c, int m, int s);
-int64_t feat_store_rows(const Ctx& c, int m, int s, bool both);
-int b1_frame_proj(const Ctx& c, int m, int s, const void* feat, int rows, const void* feat2 = nullptr, int rows2 = 0) {
-  const int din[3] = {c.d.da, c.d.dt, c.d.dv};
-  sdumc_gemm_b1 g;
+// frame_dim_reshape_m on prepared operands, stream s (and, with pj.both, the next stream's rows behind them in x): what the plane
+// and the bf16 descriptor share
+template <class G>
+G frame_proj_desc(const Ctx& c, int m, int s, const FwdSchedule::Proj& pj) {
+  G g;
   memset(&g, 0, sizeof(g));
-  g.M = rows + rows2; g.N = D; g.K = din[m];
-  g.A = feat; g.lda = din[m];
-  g.a_map = feat_map(c, m, s);      // (a resident store's packed bf16 rows, read in place)
-  g.a_map_rows = feat_store_rows(c, m, s, feat2 != nullptr);
-  if (feat2) { g.A2 = feat2; g.a2_row0 = rows; g.a2_map = feat_map(c, m, 1); }
-  g.B = wb1_ptr(c, c.pl.wp3_frame[m]); g.ldb = (int64_t)(din[m] / 16) * 1024;
+  g.M = pj.rows + (pj.both ? c.pl.B * c.pl.T[m][1] : 0); g.N = D; g.K = din_of(c, m);
+  g.a_map = feat_map(c, m, s);      // (a resident store's packed rows, read in place)
+  g.a_map_rows = feat_store_rows(c, m, s, pj.both);
+  if (pj.both) { g.a2_row0 = pj.rows; g.a2_map = feat_map(c, m, 1); }      // (the second stream's rows follow the first's in x)
   g.bias = c.P + c.pm.frame[m].b;
   g.act = SDUMC_ACT_NONE;
-  g.C = c.ph(c.pl.x[m][s]); g.ldc = D; g.c_bf16 = 1;
-  // (the text slot, 4096 rows x 4096: K over 4 workgroups -- 0.8748-0.8841 ms against 0.8832-0.8871 with the 8 the plan picks for a launch
-  //  alone, 0.8763-0.8837 with 2, 0.8778-0.8917 with none: in the step a half-filled chip is filled by the other lanes)
-  if (g.M < 8192 && g.K >= 2048) g.splitk = 4;
+  g.ldc = D;
+  g.splitk = pj.splitk;
   g.workspace = c.scr;
   g.workspace_bytes = (size_t)c.pl.scratch_floats * sizeof(float);
+  return g;
+}
+int frame_proj_prepared(const Ctx& c, const FwdSchedule& fs, int m, int s) {
+  const FwdSchedule::Proj& pj = fs.proj[m][s];
+  const int64_t din = din_of(c, m);
+  if (fs.route == FwdSchedule::P3) {      // x in fp32 (for the pooling kernels and K3) and as planes (for the key projections)
+    sdumc_gemm_p3 g = frame_proj_desc<sdumc_gemm_p3>(c, m, s, pj);
+    g.A = feat_p3(c, m, s); g.lda = din * 6;
+    if (pj.both) g.A2 = feat_p3(c, m, 1);
+    g.B = wp3_ptr(c, c.pl.wp3_frame[m]); g.ldb = (din / 16) * 3072;
+    g.C = c.p(c.pl.x[m][s]);
+    g.C_p3 = c.p(c.pl.xp3[m][s]); g.ldc_p3 = (int64_t)D * 6;
+    return sdumc_gemm_p3_nt(&g, c.st);
+  }
+  sdumc_gemm_b1 g = frame_proj_desc<sdumc_gemm_b1>(c, m, s, pj);      // features and x in bf16
+  g.A = feat_in(c, m, s); g.lda = din;
+  if (pj.both) g.A2 = feat_in(c, m, 1);
+  g.B = wb1_ptr(c, c.pl.wp3_frame[m]); g.ldb = (din / 16) * 1024;
+  g.C = c.ph(c.pl.x[m][s]); g.c_bf16 = 1;
   return sdumc_gemm_b1_nt(&g, c.st);
 }
 
 // bf16-storage mode: keys = tanh(xd W^T + b) of the sites [k0, k1), xd = drop(x) materialised by forward() (train) or x (eval)
-int keys_gemm_fwd_h(const Ctx& c, int m, int k0, int k1) {
+int keys_gemm_fwd_h(const Ctx& c, const FwdSchedule& fs, int m, int k0, int k1) {
   const Plan& pl = c.pl;
-  if (b1_mode(c)) {
+  if (fs.route == FwdSchedule::B1) {
     for (int k = k0; k < k1; ++k)
       for (const Seg& sg : pl.segs[m]) {
         const Lin& L = k == 0 ? c.pm.fra_proj[m] : c.pm.ca_in[m];
@@ -1179,52 +1258,7 @@ int keys_gemm_fwd_h(const Ctx& c, int m, int k0, int k1) {
   return SDUMC_OK;
 }
 
-// fp32 storage with the features also given as bf16 planes (sdumc_net_io.*_p3): the frame projections and the key projections that
-// go through the wide NT kernel run on operands split once per tensor (gemm_p3.hip).  SDUMC_P3=0: A/B against the in-kernel split.
-bool p3_mode(const Ctx& c) {
-  return prepared_operands_on() && c.d.bf16 == 0 && c.pl.wp3 != 0 && c.io.audio_p3 != nullptr && sdumc_split_on_(SDUMC_SPLIT_WIDE);
-}
-char* wp3_ptr(const Ctx& c, int64_t byte_off) { return reinterpret_cast<char*>(c.p(c.pl.wp3)) + byte_off; }
-// fragment-major planes of modality m's three frame-level weights (frame_dim_reshape_m, the two input_proj): one small launch at the
-// head of the modality's lane (the weights change every step)
-int p3_refresh_weights(const Ctx& c, int m) {
-  const int din[3] = {c.d.da, c.d.dt, c.d.dv};
-  int64_t so[3], dofs[3];
-  int32_t rows[3], cols[3];
-  so[0] = c.pm.frame[m].w; dofs[0] = c.pl.wp3_frame[m]; rows[0] = D; cols[0] = din[m];
-  so[1] = c.pm.fra_proj[m].w; dofs[1] = c.pl.wp3_key[0][m]; rows[1] = D; cols[1] = D;
-  so[2] = c.pm.ca_in[m].w; dofs[2] = c.pl.wp3_key[1][m]; rows[2] = D; cols[2] = D;
-  return sdumc_p3_split_frag_multi_(c.P, wp3_ptr(c, 0), so, dofs, rows, cols, 3, c.st);
-}
-// frame_dim_reshape_m on feature planes: x (fp32, for the pooling kernels and K3) and its planes (for the key projections)
-// the row map of modality m's features, stream s (sdumc_net_io.row_map is ordered audio, text, video, feat4) or nullptr
-int feat_slot(int m, int s) { return m == 0 ? 0 : (m == 2 ? 2 : (s == 0 ? 1 : 3)); }
-const int32_t* feat_map(const Ctx& c, int m, int s) { return c.io.row_map[feat_slot(m, s)]; }
-// rows of the packed tensor(s) a mapped launch reads (the larger when it reads two; 0 = unknown: 64-bit addressing)
-int64_t feat_store_rows(const Ctx& c, int m, int s, bool both) {
-  const int64_t a = c.io.store_rows[feat_slot(m, s)], b = both ? c.io.store_rows[feat_slot(m, 1)] : a;
-  return (a > 0 && b > 0) ? std::max(a, b) : 0;
-}
-int p3_frame_proj(const Ctx& c, int m, int s, const void* feat_p3, int rows, int splitk, const void* feat2_p3 = nullptr, int rows2 = 0) {
-  const int din[3] = {c.d.da, c.d.dt, c.d.dv};
-  sdumc_gemm_p3 g;
-  memset(&g, 0, sizeof(g));
-  g.M = rows + rows2; g.N = D; g.K = din[m];
-  g.A = feat_p3; g.lda = (int64_t)din[m] * 6;
-  g.a_map = feat_map(c, m, s);      // (a resident store's packed planes, read in place)
-  g.a_map_rows = feat_store_rows(c, m, s, feat2_p3 != nullptr);
-  if (feat2_p3) { g.A2 = feat2_p3; g.a2_row0 = rows; g.a2_map = feat_map(c, m, 1); }      // (the second stream's rows follow the first's in x)
-  g.B = wp3_ptr(c, c.pl.wp3_frame[m]); g.ldb = (int64_t)(din[m] / 16) * 3072;
-  g.bias = c.P + c.pm.frame[m].b;
-  g.act = SDUMC_ACT_NONE;
-  g.C = c.p(c.pl.x[m][s]); g.ldc = D;
-  g.C_p3 = c.p(c.pl.xp3[m][s]); g.ldc_p3 = (int64_t)D * 6;
-  g.splitk = splitk;
-  g.workspace = c.scr;
-  g.workspace_bytes = (size_t)c.pl.scratch_floats * sizeof(float);
-  return sdumc_gemm_p3_nt(&g, c.st);
-}
-// input_proj of site (k, m) on the projected frames' planes: keys = tanh(drop(x) W^T + b)
+// fp32 storage on planes: input_proj of site (k, m) on the projected frames' planes: keys = tanh(drop(x) W^T + b)
 int p3_keys_fwd(const Ctx& c, int m, int k) {
   for (const Seg& sg : c.pl.segs[m]) {
     const Lin& L = k == 0 ? c.pm.fra_proj[m] : c.pm.ca_in[m];
@@ -1245,9 +1279,9 @@ int p3_keys_fwd(const Ctx& c, int m, int k) {
   return SDUMC_OK;
 }
 
-int keys_gemm_fwd(const Ctx& c, int m, int k0, int k1) {
-  if (c.h()) return keys_gemm_fwd_h(c, m, k0, k1);
-  if (p3_mode(c)) {
+int keys_gemm_fwd(const Ctx& c, const FwdSchedule& fs, int m, int k0, int k1) {
+  if (c.h()) return keys_gemm_fwd_h(c, fs, m, k0, k1);
+  if (fs.route == FwdSchedule::P3) {
     for (int k = k0; k < k1; ++k) RET(p3_keys_fwd(c, m, k));
     return SDUMC_OK;
   }
@@ -1281,9 +1315,14 @@ bool attn_multi_ok(const Ctx& c) {
   return n <= 4;
 }
 
-bool fra_fold(const Ctx& c);                                        // (defined with the chain launch helpers below)
-void fold_partial_only(const Ctx& c, int k, int m, sdumc_attnpool& a);
-int pool_fwd_multi(const Ctx& c, int k) {
+// site (k, m)'s descriptor for the partial-only pass (fra_fold: the clustered stage behind the launch combines the chunks)
+void fold_partial_only(const Ctx& c, int k, int m, sdumc_attnpool& a) {
+  a.partial_only = 1;
+  a.tickets = nullptr;
+  a.workspace = c.p(c.pl.fold_ws[k][m]);
+  a.workspace_bytes = sdumc_attnpool_fwd_workspace_bytes(a.V, a.T, a.nq);
+}
+int pool_fwd_multi(const Ctx& c, const FwdSchedule& fs, int k) {
   sdumc_attnpool a[4];
   int n = 0;
   float* ws = c.scr;
@@ -1295,7 +1334,7 @@ int pool_fwd_multi(const Ctx& c, int k) {
       a[n].workspace = ws;
       a[n].workspace_bytes = bytes;
       ws += (bytes / sizeof(float) + 63) / 64 * 64;
-      if (fra_fold(c)) fold_partial_only(c, k, order[oi], a[n]);      // (the clustered stage behind this launch combines)
+      if (fs.fra_fold) fold_partial_only(c, k, order[oi], a[n]);
       ++n;
     }
   return sdumc_attnpool_fwd_multi(a, n, c.st);
@@ -1318,7 +1357,7 @@ bool k3_ok(const Ctx& c, int m) {
     if (sg.T < 96) return false;
   return true;
 }
-int umca_site(const Ctx& c, int k, int m, bool keep) {
+int umca_site(const Ctx& c, const FwdSchedule& fs, int k, int m, bool keep) {
   for (const Seg& sg : c.pl.segs[m]) {
     sdumc_umca u;
     memset(&u, 0, sizeof(u));
@@ -1327,11 +1366,11 @@ int umca_site(const Ctx& c, int k, int m, bool keep) {
     if (!keep) u.a.keys = nullptr;
     u.a.workspace = c.scr;
     u.a.workspace_bytes = (size_t)c.pl.scratch_floats * sizeof(float);
-    if (fra_fold(c)) fold_partial_only(c, k, m, u.a);
+    if (fs.fra_fold) fold_partial_only(c, k, m, u.a);
     const Lin& L = k == 0 ? c.pm.fra_proj[m] : c.pm.ca_in[m];
     u.w_in = c.P + L.w;
     u.b_in = c.P + L.b;
-    if (p3_mode(c) && sdumc_split_on_(SDUMC_SPLIT_UMCA)) {      // the fused kernel's projection on planes (1.361-1.364 against 1.374-1.376 ms)
+    if (fs.umca_planes) {
       u.x_p3 = c.p(c.pl.xp3[m][sg.s0]);
       u.w_in_p3f = wp3_ptr(c, c.pl.wp3_key[k][m]);
     }
@@ -1340,12 +1379,12 @@ int umca_site(const Ctx& c, int k, int m, bool keep) {
   return SDUMC_OK;
 }
 
-int pool_fwd(const Ctx& c, int k, int m) {
+int pool_fwd(const Ctx& c, const FwdSchedule& fs, int k, int m) {
   for (const Seg& sg : c.pl.segs[m]) {
     sdumc_attnpool a = attn_desc(c, k, m, sg);
     a.workspace = c.scr;
     a.workspace_bytes = (size_t)c.pl.scratch_floats * sizeof(float);
-    if (fra_fold(c)) fold_partial_only(c, k, m, a);
+    if (fs.fra_fold) fold_partial_only(c, k, m, a);
     RET(sdumc_attnpool_fwd(&a, c.st));
   }
   return SDUMC_OK;
@@ -1359,39 +1398,26 @@ int pool_fwd(const Ctx& c, int k, int m) {
 // either path (A/B measurements; tests/test_gpu_perlayer.py holds the per-layer path to the oracle on both sides of the
 // threshold and, with SDUMC_CHAIN=0 in a child process, at the smallest shapes).
 // ------------------------------------------------------------------------------------------
-bool use_chain(const Ctx& c) {
+UttPath plan_utterance(const Ctx& c) {
+  UttPath u;
   static const int forced = [] { const char* e = getenv("SDUMC_CHAIN"); return e ? atoi(e) : -1; }();
-  if (forced >= 0) return forced != 0;
-  return c.pl.V <= 512;
-}
-
-// chain_cluster.hip instead of chain.hip: every workgroup of the clustered kernels must be resident at once (V <= 128 on
-// MI355X) and their launches wait on a per-device event, which a stream capture cannot contain
-bool use_cluster(const Ctx& c) {
-  if (!use_chain(c) || c.capturing || c.chain_cluster_opt == 0) return false;
-  return c.chain_cluster_opt == 1 ? sdumc_chain_cluster_fits_(c.pl.V) == 1 : sdumc_chain_cluster_ok_(c.pl.V) == 1;
-}
-
-// The clustered stage A combines the FRA2UTT sites' softmax partials in its own prologue (chain_cluster.hip::fra_combine): the
-// pooling launches of the three modality lanes then stop after their per-chunk pass (sdumc_attnpool.partial_only) and the three
-// combine launches -- 31-39 us each inside the step, on every lane's way to this stage -- are gone.  One run per modality (equal
-// text / feat4 lengths), at most 32 chunks per sample (the separate combine launches remain the path of the plain kernels).
-bool fra_fold(const Ctx& c) {
-  if (!use_cluster(c)) return false;
+  u.chain = forced >= 0 ? forced != 0 : c.pl.V <= 512;
+  // chain_cluster.hip instead of chain.hip: every workgroup of the clustered kernels must be resident at once (V <= 128 on
+  // MI355X) and their launches wait on a per-device event, which a stream capture cannot contain
+  if (u.chain && !c.capturing && c.chain_cluster_opt != 0)
+    u.cluster = c.chain_cluster_opt == 1 ? sdumc_chain_cluster_fits_(c.pl.V) == 1 : sdumc_chain_cluster_ok_(c.pl.V) == 1;
+  // The clustered stage A combines the FRA2UTT sites' softmax partials in its own prologue (chain_cluster.hip::fra_combine): the
+  // pooling launches of the three modality lanes then stop after their per-chunk pass (sdumc_attnpool.partial_only) and the three
+  // combine launches -- 31-39 us each inside the step, on every lane's way to this stage -- are gone.  One run per modality (equal
+  // text / feat4 lengths), at most 32 chunks per sample (the separate combine launches remain the path of the plain kernels).
+  u.fra_fold = u.cluster;
   for (int m = 0; m < 3; ++m)
-    if (c.pl.segs[m].size() != 1 || (c.pl.segs[m][0].T + 63) / 64 > 32) return false;
-  return true;
-}
-// site (k, m)'s descriptor for the partial-only pass
-void fold_partial_only(const Ctx& c, int k, int m, sdumc_attnpool& a) {
-  a.partial_only = 1;
-  a.tickets = nullptr;
-  a.workspace = c.p(c.pl.fold_ws[k][m]);
-  a.workspace_bytes = sdumc_attnpool_fwd_workspace_bytes(a.V, a.T, a.nq);
+    if (c.pl.segs[m].size() != 1 || (c.pl.segs[m][0].T + 63) / 64 > 32) u.fra_fold = false;
+  return u;
 }
 
-int chain_launch(const Ctx& c, const sdumc_chain_args& ca, int which) {
-  if (use_cluster(c)) {
+int chain_launch(const Ctx& c, const UttPath& utt, const sdumc_chain_args& ca, int which) {
+  if (utt.cluster) {
     const int rc = sdumc_chain_cluster_launch_(&ca, which, c.st);
     if (rc != 1) return rc;
   }
@@ -1420,11 +1446,8 @@ int chain_transpose(const Ctx& c) {
   int64_t offs[40];
   int32_t outs[40], ins[40];
   int n = 0;
-  if (use_chain(c)) {
-    const std::vector<const Lin*> ls = chain_lins(c.pm);
-    for (const Lin* L : ls) { offs[n] = L->w; outs[n] = L->out; ins[n] = L->in; ++n; }
-  }
-  if (n == 0) return SDUMC_OK;
+  const std::vector<const Lin*> ls = chain_lins(c.pm);
+  for (const Lin* L : ls) { offs[n] = L->w; outs[n] = L->out; ins[n] = L->in; ++n; }
   return sdumc_chain_transpose_(c.P, c.p(c.pl.wt), offs, outs, ins, n, c.st);
 }
 
@@ -1432,7 +1455,7 @@ int chain_transpose(const Ctx& c) {
 // stage_a: the launch is one of the stage-A kernels.  In bf16-storage mode only those stream bf16 weights: their layers are
 // 2-row products bound by the weight stream (fwd 104 -> 82 us, bwd 100 -> 86 us at C2), while stage B's 14-row layers are bound
 // by their FMAs and the bf16 unpacking made them slower (69 -> 85 us), so stage B keeps reading the fp32 weights.
-sdumc_chain_args chain_args(const Ctx& c, bool fwd, const sdumc_net_grads* og, bool stage_a) {
+sdumc_chain_args chain_args(const Ctx& c, const UttPath& utt, bool fwd, const sdumc_net_grads* og, bool stage_a) {
   const Plan& pl = c.pl;
   const ParamMap& pm = c.pm;
   sdumc_chain_args a;
@@ -1444,7 +1467,7 @@ sdumc_chain_args chain_args(const Ctx& c, bool fwd, const sdumc_net_grads* og, b
   const float* WB = fwd ? c.p(pl.wt) : c.P;
   // bf16-storage mode: the streamed matrices are read from the bf16 copies (transposed for the forward, as stored for the
   // backward: sdumc_weights_to_bf16_ in forward()); orgin_linear_change stays fp32 (64 columns: too narrow for 8-column lanes)
-  const bool wb = c.h() && stage_a && !use_cluster(c);
+  const bool wb = c.h() && stage_a && !utt.cluster;
   a.w_bf16 = wb ? 1 : 0;
   auto W = [&](const Lin& L) -> const float* {
     if (wb) return reinterpret_cast<const float*>(c.ph(fwd ? pl.wht : pl.wh, L.w));
@@ -1479,7 +1502,7 @@ sdumc_chain_args chain_args(const Ctx& c, bool fwd, const sdumc_net_grads* og, b
   if (!fwd && stage_a && c.dq_part[0]) {
     for (int m = 0; m < 3; ++m) { a.dq_part[m] = c.dq_part[m]; a.dq_nchunk[m] = c.dq_nchunk[m]; }
   }
-  if (fwd && fra_fold(c)) {      // stage A combines the FRA2UTT sites' partials, stage B the Cross_Attention sites'
+  if (fwd && utt.fra_fold) {      // stage A combines the FRA2UTT sites' partials, stage B the Cross_Attention sites'
     const int k = stage_a ? 0 : 1, nq = stage_a ? 1 : NQ;
     sdumc_chain_fold& f = stage_a ? a.fra : a.ca;
     for (int m = 0; m < 3; ++m) {
@@ -1520,38 +1543,116 @@ int issue_prefetch(const Ctx& c) {
   return sdumc_gather_batch(c.io.prefetch, wgs, c.sts[3]);
 }
 
-int forward(const Ctx& c) {
+// The forward pass.  plan_forward() decides the schedule -- the frame projections' kernel family and split, where the keep-bits come
+// from, K3 or the GEMM + pooling pair per modality, the lane of every Cross_Attention key projection, the utterance-level path --
+// ONCE, before the first launch; forward() and its parts read the record.
+// launches nothing, records no event, touches no stream: a function of dims, io, the context's options, the process-wide switches
+// (environment, setters) and whether the caller's stream is under capture (c.capturing, asked once by init_lanes)
+FwdSchedule plan_forward(const Ctx& c) {
+  FwdSchedule s;
+  static_cast<UttPath&>(s) = plan_utterance(c);
+  const Plan& pl = c.pl;
+  s.route = frame_route(c);
+  const bool prepared = s.route == FwdSchedule::P3 || s.route == FwdSchedule::B1;
+  if (c.io.row_map[0] && !prepared) s.rc = SDUMC_EINVAL;      // (only gemm_p3 / gemm_b1 fetch their rows through a map)
+  // the fused kernel's projection on planes (1.361-1.364 against 1.374-1.376 ms)
+  s.umca_planes = s.route == FwdSchedule::P3 && sdumc_split_on_(SDUMC_SPLIT_UMCA);
+  // bf16 storage: bf16 copies of the frame-level weights (+ the transposed input_proj copies the dX products read).  With gemm_b1.hip
+  // the forward reads fragment-major copies made on each modality's own lane; the row-major / transposed copies are then first read
+  // by the backward dX products: lane 3, off the head of the step.  chain.hip (not the clustered kernels) streams bf16 copies of the
+  // utterance-level matrices too.
+  s.wh_copies = c.h();
+  s.wh_lane3 = s.route == FwdSchedule::B1;
+  s.wh_utterance = c.h() && s.chain && !s.cluster;
+  s.refresh_wt = s.chain;      // the chain kernels stream W^T forward
+  // The keep-bits (Philox once per element instead of ~10x in the kernels that stage these tiles; VALU-bound) are generated
+  // on lane 3 in the shadow of the MFMA-bound frame projections, which read no mask; each modality's lane waits for its
+  // own bits before the key projections.
+  // bf16 storage: the keep-bits are produced together with the masked frames xd of both sites, behind the modality's frame
+  // projection on the modality's own lane (one pass over x instead of a bits launch on lane 3 plus one mask_apply per site)
+  s.bits = !c.d.train ? FwdSchedule::BITS_NONE : (c.h() ? FwdSchedule::BITS_WITH_XD : FwdSchedule::BITS_LANE3);
+  s.pregen = bits_pregen(c);
+  s.pool_grouped = attn_multi_ok(c);
+  // Frame projections.  The few-row / long-K ones (the text slot: 2048 x 256 x 4096 per stream at C2) split K over workgroups:
+  //  P3: alone: split 8 34.6 us, 4 37.9, 2 63.8 per stream; both streams in one launch: 4.
+  //  B1: the text slot, 4096 rows x 4096: K over 4 workgroups -- 0.8748-0.8841 ms against 0.8832-0.8871 with the 8 the launcher picks
+  //      for a launch alone, 0.8763-0.8837 with 2, 0.8778-0.8917 with none: in the step a half-filled chip is filled by the other lanes.
+  //  F32: through the wide LDS-DMA kernel (tile 14) with K split over workgroups instead of the 64x64 register-staged kernel's
+  //      automatic split: split 8 (512 workgroups, 32 k-tiles each) fp32 C2 step 1.665-1.669 vs 1.671-1.676 ms (split 4: 1.674-1.678,
+  //      split 2: 1.705-1.710).  With the products on the bf16 matrix pipe the k-loop is shorter and half as many slabs win: split 4
+  //      1.424-1.438 against split 8 1.444-1.450 and split 2 1.440-1.450 (three alternations)
+  constexpr int p3_text_split = 4, b1_text_split = 4, text_wide = 4;
+  auto few_rows_long_k = [](int rows, int K) { return rows < 8192 && K >= 2048; };
+  for (int m = 0; m < 3; ++m)
+    for (int st = 0; st < (m == 1 ? pl.S : 1); ++st) {
+      FwdSchedule::Proj& pj = s.proj[m][st];
+      const int K = din_of(c, m);
+      pj.rows = pl.B * pl.T[m][st];
+      const bool few = few_rows_long_k(pj.rows, K);
+      // The text slot's two streams leave as ONE launch (their x rows are adjacent; the second tensor starts at a whole 64-row tile):
+      // on the routes that take two tensors -- on planes only where the launch is split anyway
+      pj.both = prepared && m == 1 && pl.S == 2 && st == 0 && pj.rows % 64 == 0 && (s.route == FwdSchedule::B1 || few);
+      if (s.route == FwdSchedule::P3) pj.splitk = pj.both ? p3_text_split : (few ? 2 * p3_text_split : 1);
+      if (s.route == FwdSchedule::B1) pj.splitk = few_rows_long_k(pj.rows + (pj.both ? pl.B * pl.T[1][1] : 0), K) ? b1_text_split : 0;
+      if (s.route == FwdSchedule::F32 && !c.d.bf16 && few && K % (16 * text_wide) == 0 && pj.rows % 64 == 0) {
+        pj.tile = 14;
+        pj.splitk = text_wide;
+      }
+    }
+  // Audio's Cross_Attention keys (the largest of the three key projections) stay on audio's own lane, BEHIND a partial
+  // join: the caller's stream (stage A) waits only for the FRA2UTT site, the keys are awaited before step 8.  Lane 3 then
+  // carries two key projections instead of three and the pooling of step 8 waits ~10 us less for it (fp32 C2 1.726-1.731
+  // against 1.733-1.738 ms, bf16 1.046-1.047 against 1.053-1.057; video's instead: 1.756-1.772, both: 1.732-1.738).
+  // The others: not needed before step 8 -- the background lane, beside steps 2-7.  Without a background lane (option 0, or under
+  // capture) they stay inline: behind the fused FRA2UTT kernel, else grouped with the FRA2UTT key projection.
+  constexpr int ca_own = 1;
+  for (int m = 0; m < 3; ++m) {
+    FwdSchedule::Mod& M = s.mod[m];
+    M.k3_site0 = k3_ok(c, m);
+    if (c.bg && (ca_own & (1 << m)) && LANE_OF[m] != 0 && c.multi && !c.capturing) M.ca_keys = FwdSchedule::OWN_LANE_PARTIAL_JOIN;
+    else if (c.bg) M.ca_keys = FwdSchedule::LANE3;
+    else M.ca_keys = M.k3_site0 ? FwdSchedule::INLINE : FwdSchedule::INLINE_GROUPED_WITH_SITE0;
+  }
+  return s;
+}
+
+// events between the parts of one forward (nullptr: both ends are on one stream)
+struct FwdEvents {
+  hipEvent_t wt_done = nullptr;                              // lane 3: the transposed mirror is written
+  hipEvent_t bits_done[3] = {nullptr, nullptr, nullptr};     // lane 3: modality m's keep-bits
+  hipEvent_t fra_done[3] = {nullptr, nullptr, nullptr};      // modality m's lane: its FRA2UTT site (OWN_LANE_PARTIAL_JOIN)
+  hipEvent_t ca_done[3] = {nullptr, nullptr, nullptr};       // ... its Cross_Attention keys
+};
+int record_here(const Ctx& c, hipEvent_t& e) {      // on the current lane
+  e = next_event(c);
+  return hipEventRecord(e, c.st) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
+}
+int await_on(hipStream_t st, hipEvent_t e) { return !e || hipStreamWaitEvent(st, e, 0) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH; }
+
+// lengths, fork, bf16 weight copies, transposed mirror, keep-bits on lane 3 with their tag
+int fwd_head(const Ctx& c, const FwdSchedule& fs, FwdEvents& ev) {
   const Plan& pl = c.pl;
   const ParamMap& pm = c.pm;
   const int B = pl.B, S = pl.S, V = pl.V;
-  const int din[3] = {c.d.da, c.d.dt, c.d.dv};
   if (c.io.lengths[0]) {
     hipLaunchKernelGGL(expand_lengths_kernel, dim3((3 * V + 255) / 256), dim3(256), 0, c.st, c.io.lengths[0], c.io.lengths[1],
                        c.io.lengths[2], S == 2 ? c.io.lengths[3] : c.io.lengths[1], B, S,
                        reinterpret_cast<int32_t*>(c.p(pl.lens)));
     SDUMC_CHECK_LAUNCH();
   }
-  // 1+2. three independent per-modality chains, one per lane:
-  //      keep-bits of the two frame-level input dropouts -> frame_dim_reshape_m (model :282-284; audio/video once
-  //      for both streams) -> keys of fra2utt_m AND cross_att_fra2utt_m -> FRA2UTT pooling (model :288-290)
-  if (c.io.row_map[0] && !p3_mode(c) && !b1_mode(c)) return SDUMC_EINVAL;      // (only gemm_p3 / gemm_b1 fetch their rows through a map)
   RET(fork_all(c));
-  const bool chain = use_chain(c);
-  hipEvent_t wt_done = nullptr;
-  if (c.h()) {   // bf16 copies of the frame-level weights (+ the transposed input_proj copies the dX products read)
+  if (fs.wh_copies) {
     int64_t offs[16];
     int32_t outs[16], ins[16], wantt[16];
     int n = 0;
-    for (int m = 0; m < 3; ++m) { offs[n] = pm.frame[m].w; outs[n] = D; ins[n] = din[m]; wantt[n] = 0; ++n; }
+    for (int m = 0; m < 3; ++m) { offs[n] = pm.frame[m].w; outs[n] = D; ins[n] = din_of(c, m); wantt[n] = 0; ++n; }
     for (int m = 0; m < 3; ++m) {
       offs[n] = pm.fra_proj[m].w; outs[n] = D; ins[n] = D; wantt[n] = 1; ++n;
       offs[n] = pm.ca_in[m].w; outs[n] = D; ins[n] = D; wantt[n] = 1; ++n;
     }
-    // (with gemm_b1.hip the forward reads fragment-major copies made on each modality's own lane; these row-major / transposed
-    //  copies are first read by the backward dX products: lane 3, off the head of the step)
-    if (b1_mode(c)) { RET(link(c, 0, 3)); c.use(3); }
+    if (fs.wh_lane3) { RET(link(c, 0, 3)); c.use(3); }
     RET(sdumc_weights_to_bf16_(c.P, c.ph(pl.wh), c.ph(pl.wht), offs, outs, ins, wantt, n, c.st));
-    if (chain && !use_cluster(c)) {   // + the utterance-level matrices chain.hip streams (both layouts: forward and backward)
+    if (fs.wh_utterance) {   // + the utterance-level matrices chain.hip streams (both layouts: forward and backward)
       const std::vector<const Lin*> ls = chain_lins(pm);
       n = 0;
       for (size_t i = 0; i <= ls.size(); ++i) {
@@ -1562,29 +1663,18 @@ int forward(const Ctx& c) {
         if (i < ls.size()) { offs[n] = ls[i]->w; outs[n] = ls[i]->out; ins[n] = ls[i]->in; wantt[n] = 1; ++n; }
       }
     }
-    if (b1_mode(c)) c.use(0);
+    if (fs.wh_lane3) c.use(0);
     else RET(fork_all(c));      // (the lanes forked above did not see these launches)
   }
-  if (chain) {   // transposed mirror (first needed after the frame-level part): lane 3
+  if (fs.refresh_wt) {   // transposed mirror (first needed after the frame-level part): lane 3
     RET(link(c, 0, 3));
     c.use(3);
     RET(chain_transpose(c));
-    if (c.sts[3] != c.sts[0]) {
-      wt_done = next_event(c);
-      if (hipEventRecord(wt_done, c.st) != hipSuccess) return SDUMC_ELAUNCH;
-    }
+    if (c.sts[3] != c.sts[0]) RET(record_here(c, ev.wt_done));
     c.use(0);
   }
-  // The keep-bits (Philox once per element instead of ~10x in the kernels that stage these tiles; VALU-bound) are generated
-  // on lane 3 in the shadow of the MFMA-bound frame projections, which read no mask; each modality's lane waits for its
-  // own bits before the key projections.  Heaviest modality first.
-  hipEvent_t bits_done[3] = {nullptr, nullptr, nullptr};
-  // bf16 storage: the keep-bits are produced together with the masked frames xd of both sites, behind the modality's frame
-  // projection on the modality's own lane (one pass over x instead of a bits launch on lane 3 plus one mask_apply per site)
-  const bool bits_with_xd = c.h() && c.d.train;
-  const bool pregen = bits_pregen(c);
-  const sdumc_bits_shape shape_now = bits_shape(c.d);
-  if (c.d.train && !bits_with_xd) {
+  if (fs.bits == FwdSchedule::BITS_LANE3) {      // heaviest modality first
+    const sdumc_bits_shape shape_now = bits_shape(c.d);
     RET(link(c, 0, 3));
     c.use(3);
     const int order[3] = {0, 2, 1};
@@ -1595,14 +1685,11 @@ int forward(const Ctx& c) {
         uint8_t* outs[2] = {bits_ptr(c, 0, m) + sg.row0 * (D / 4), bits_ptr(c, 1, m) + sg.row0 * (D / 4)};
         // (bits_next: nothing to do when the previous call filled this set for this call and shape -- its tag says so)
         RET(sdumc_dropout_bits_multi_ex_(&d, sg.V / B, 2, SITE_IN[1][m] - SITE_IN[0][m], outs,
-                                         pregen ? reinterpret_cast<const uint32_t*>(bits_set(c, 0)) : nullptr, 0, &shape_now, c.st));
+                                         fs.pregen ? reinterpret_cast<const uint32_t*>(bits_set(c, 0)) : nullptr, 0, &shape_now, c.st));
       }
-      if (c.sts[3] != c.sts[LANE_OF[m]]) {
-        bits_done[m] = next_event(c);
-        if (hipEventRecord(bits_done[m], c.st) != hipSuccess) return SDUMC_ELAUNCH;
-      }
+      if (c.sts[3] != c.sts[LANE_OF[m]]) RET(record_here(c, ev.bits_done[m]));
     }
-    if (pregen) {
+    if (fs.pregen) {
       // Whatever the set's tag said, the set now holds THIS call's masks: say so (behind the three launches that read the tag, on their
       // lane).  A set regenerated under a foreign tag would otherwise keep naming the call it was once filled for, and a counter that
       // comes back to that value (a rewind, a phase that was not flipped) would find stale masks under a matching tag.
@@ -1610,128 +1697,117 @@ int forward(const Ctx& c) {
       RET(sdumc_bits_tag_(&d0, reinterpret_cast<uint32_t*>(bits_set(c, 0)), 0, &shape_now, c.st));
     }
   }
-  hipEvent_t fra_done[3] = {nullptr, nullptr, nullptr}, ca_done[3] = {nullptr, nullptr, nullptr};
-  // frame_dim_reshape_m on feature planes (gemm_p3.hip), all streams of the modality, on the current lane
-  auto p3_frames = [&](int m) -> int {
-    // (the text slot: 2048 x 256 x 4096 per stream -- K split over workgroups; both streams in one launch, their x rows are adjacent)
-    constexpr int p3_text_split = 4;      // (alone: split 8 34.6 us, 4 37.9, 2 63.8 per stream; both streams in one launch: 4)
-    RET(p3_refresh_weights(c, m));
-    for (int s = 0; s < (m == 1 ? S : 1); ++s) {
-      const void* fp = m == 0 ? c.io.audio_p3 : (m == 2 ? c.io.video_p3 : c.io.text_p3[s]);
-      const int rows_p = B * pl.T[m][s];
-      const bool few = rows_p < 8192 && din[m] >= 2048;
-      if (m == 1 && S == 2 && few && rows_p % 64 == 0) {
-        RET(p3_frame_proj(c, m, 0, fp, rows_p, p3_text_split, c.io.text_p3[1], B * pl.T[1][1]));
-        break;
-      }
-      RET(p3_frame_proj(c, m, s, fp, rows_p, few ? 2 * p3_text_split : 1));
+  return SDUMC_OK;
+}
+
+// frame_dim_reshape_m (model :282-284; audio / video once for both streams), every stream of the modality, on the current lane
+int fwd_frame_proj(const Ctx& c, const FwdSchedule& fs, int m) {
+  const Plan& pl = c.pl;
+  const bool prepared = fs.route == FwdSchedule::P3 || fs.route == FwdSchedule::B1;
+  if (prepared) RET(refresh_frame_weight_forms(c, fs, m));
+  for (int s = 0; s < (m == 1 ? pl.S : 1); ++s) {
+    const FwdSchedule::Proj& pj = fs.proj[m][s];
+    const int din = din_of(c, m);
+    if (prepared) {
+      RET(frame_proj_prepared(c, fs, m, s));
+      if (pj.both) break;
+    } else if (fs.route == FwdSchedule::BF16_TILES) {    // features and projected frames in bf16
+      sdumc_gemm_bf16 g = GH_(SDUMC_NT, pj.rows, D, din);
+      g.A[0] = feat_in(c, m, s);
+      g.lda = din;
+      g.B[0] = c.ph(pl.wh, c.pm.frame[m].w);
+      g.ldb = din;
+      g.bias[0] = c.P + c.pm.frame[m].b;
+      g.C[0] = c.ph(pl.x[m][s]);
+      g.ldc = D;
+      g.c_bf16 = 1;
+      RET(run_h(c, g));
+    } else {
+      RET(lin_fwd(c, c.pm.frame[m], feat_in(c, m, s), din, pj.rows, c.p(pl.x[m][s]), D, SDUMC_ACT_NONE, nullptr, c.d.bf16 != 0,
+                  pj.tile, pj.splitk));
     }
-    return SDUMC_OK;
-  };
-  // (measured and dropped: the three modalities' projections one after the other on one lane, every modality's lane waiting for
-  //  its own -- 1.50-1.53 against 1.37-1.39 ms: side by side the lanes' kernels do fill each other's bandwidth bursts)
-  for (int m = 0; m < 3; ++m) {
-    c.use(LANE_OF[m]);
-    if (p3_mode(c)) RET(p3_frames(m));
-    if (b1_mode(c)) RET(b1_refresh_weights(c, m));
-    for (int s = 0; s < (m == 1 ? S : 1) && !p3_mode(c); ++s) {
-      const float* in = m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]);
-      if (b1_mode(c)) {    // (the text slot's two streams in one launch: their x rows are adjacent)
-        const int rows_p = B * pl.T[m][s];
-        if (m == 1 && S == 2 && rows_p % 64 == 0) {
-          RET(b1_frame_proj(c, m, 0, in, rows_p, c.io.text[1], B * pl.T[1][1]));
-          break;
-        }
-        RET(b1_frame_proj(c, m, s, in, rows_p));
-        continue;
-      }
-      if (c.h()) {    // features and projected frames in bf16
-        sdumc_gemm_bf16 g = GH_(SDUMC_NT, B * pl.T[m][s], D, din[m]);
-        g.A[0] = in;
-        g.lda = din[m];
-        g.B[0] = c.ph(pl.wh, pm.frame[m].w);
-        g.ldb = din[m];
-        g.bias[0] = c.P + pm.frame[m].b;
-        g.C[0] = c.ph(pl.x[m][s]);
-        g.ldc = D;
-        g.c_bf16 = 1;
-        RET(run_h(c, g));
-        continue;
-      }
-      // few-row / long-K projections (the text slot: 2048 x 256 x 4096 per stream at C2) through the wide LDS-DMA kernel with K split
-      // 8 ways over workgroups (512 of them, 32 k-tiles each) instead of the 64x64 register-staged kernel's automatic split:
-      // fp32 C2 step 1.665-1.669 vs 1.671-1.676 ms (split 4: 1.674-1.678, split 2: 1.705-1.710).  With the products on the bf16
-      // matrix pipe the k-loop is shorter and half as many slabs win: split 4 1.424-1.438 against split 8 1.444-1.450 and split
-      // 2 1.440-1.450 (three alternations)
-      constexpr int text_wide = 4;
-      const int rows_ms = B * pl.T[m][s];
-      const bool wide_split = text_wide > 0 && !c.d.bf16 && rows_ms < 8192 && din[m] >= 2048 && (din[m] % (16 * text_wide)) == 0 && (rows_ms % 64) == 0;
-      RET(lin_fwd(c, pm.frame[m], in, din[m], rows_ms, c.p(pl.x[m][s]), D, SDUMC_ACT_NONE, nullptr, c.d.bf16 != 0,
-                  wide_split ? 14 : 0, wide_split ? text_wide : 0));
+  }
+  return SDUMC_OK;
+}
+
+// 1+2. modality m's chain on its own lane: weight forms -> frame_dim_reshape_m -> keep-bits awaited (or made with xd) -> keys of
+//      fra2utt_m AND cross_att_fra2utt_m, the latter where the schedule places them -> FRA2UTT pooling (model :288-290)
+// (measured and dropped: the three modalities' projections one after the other on one lane, every modality's lane waiting for
+//  its own -- 1.50-1.53 against 1.37-1.39 ms: side by side the lanes' kernels do fill each other's bandwidth bursts)
+int fwd_frame(const Ctx& c, const FwdSchedule& fs, int m, FwdEvents& ev) {
+  const Plan& pl = c.pl;
+  const FwdSchedule::Mod& M = fs.mod[m];
+  c.use(LANE_OF[m]);
+  RET(fwd_frame_proj(c, fs, m));
+  mark(c.st, 28 + 4 * m);      // (debug marks 28..39: this modality's lane, frame-level forward: projection done)
+  RET(await_on(c.st, ev.bits_done[m]));
+  if (fs.bits == FwdSchedule::BITS_WITH_XD) {
+    for (const Seg& sg : pl.segs[m]) {
+      const sdumc_dropout d = mkdrop(c, SITE_IN[0][m], c.d.p_frame, sg.T, D, sg.s0);
+      uint8_t* bo[2] = {reinterpret_cast<uint8_t*>(c.p(pl.bits[0][m])) + sg.row0 * (D / 4),
+                        reinterpret_cast<uint8_t*>(c.p(pl.bits[1][m])) + sg.row0 * (D / 4)};
+      void* xo[2] = {c.ph(pl.xd[0][m], sg.row0 * D), c.ph(pl.xd[1][m], sg.row0 * D)};
+      RET(sdumc_dropout_bits_apply_bf16(&d, sg.V / pl.B, SITE_IN[1][m] - SITE_IN[0][m], bo, c.ph(sg.x_off), (int64_t)sg.x_samples * sg.T,
+                                        xo, c.st));
     }
-    mark(c.st, 28 + 4 * m);      // (debug marks 28..39: this modality's lane, frame-level forward: projection done)
-    if (bits_done[m] && hipStreamWaitEvent(c.st, bits_done[m], 0) != hipSuccess) return SDUMC_ELAUNCH;
-    if (bits_with_xd) {
-      for (const Seg& sg : pl.segs[m]) {
-        const sdumc_dropout d = mkdrop(c, SITE_IN[0][m], c.d.p_frame, sg.T, D, sg.s0);
-        uint8_t* bo[2] = {reinterpret_cast<uint8_t*>(c.p(pl.bits[0][m])) + sg.row0 * (D / 4),
-                          reinterpret_cast<uint8_t*>(c.p(pl.bits[1][m])) + sg.row0 * (D / 4)};
-        void* xo[2] = {c.ph(pl.xd[0][m], sg.row0 * D), c.ph(pl.xd[1][m], sg.row0 * D)};
-        RET(sdumc_dropout_bits_apply_bf16(&d, sg.V / B, SITE_IN[1][m] - SITE_IN[0][m], bo, c.ph(sg.x_off), (int64_t)sg.x_samples * sg.T,
-                                          xo, c.st));
-      }
-    }
-    mark(c.st, 29 + 4 * m);      // keep-bits awaited
-    const bool k3_site0 = k3_ok(c, m);
-    // Audio's Cross_Attention keys (the largest of the three key projections) stay on audio's own lane, BEHIND a partial
-    // join: the caller's stream (stage A) waits only for the FRA2UTT site, the keys are awaited before step 8.  Lane 3 then
-    // carries two key projections instead of three and the pooling of step 8 waits ~10 us less for it (fp32 C2 1.726-1.731
-    // against 1.733-1.738 ms, bf16 1.046-1.047 against 1.053-1.057; video's instead: 1.756-1.772, both: 1.732-1.738).
-    constexpr int ca_own = 1;
-    if (c.bg && (ca_own & (1 << m)) && LANE_OF[m] != 0 && c.multi && !c.capturing) {
-      if (k3_site0) RET(umca_site(c, 0, m, true));
-      else { RET(keys_gemm_fwd(c, m, 0, 1)); RET(pool_fwd(c, 0, m)); }
-      fra_done[m] = next_event(c);
-      if (hipEventRecord(fra_done[m], c.st) != hipSuccess) return SDUMC_ELAUNCH;
-      RET(keys_gemm_fwd(c, m, 1, 2));
-      ca_done[m] = next_event(c);
-      if (hipEventRecord(ca_done[m], c.st) != hipSuccess) return SDUMC_ELAUNCH;
-    } else if (c.bg) {   // the Cross_Attention keys are not needed before step 8: background lane, beside steps 2-7
-      if (k3_site0) RET(umca_site(c, 0, m, true));
-      else RET(keys_gemm_fwd(c, m, 0, 1));
+  }
+  mark(c.st, 29 + 4 * m);      // keep-bits awaited
+  switch (M.ca_keys) {
+    case FwdSchedule::OWN_LANE_PARTIAL_JOIN:
+      if (M.k3_site0) RET(umca_site(c, fs, 0, m, true));
+      else { RET(keys_gemm_fwd(c, fs, m, 0, 1)); RET(pool_fwd(c, fs, 0, m)); }
+      RET(record_here(c, ev.fra_done[m]));
+      RET(keys_gemm_fwd(c, fs, m, 1, 2));
+      RET(record_here(c, ev.ca_done[m]));
+      break;
+    case FwdSchedule::LANE3:
+      if (M.k3_site0) RET(umca_site(c, fs, 0, m, true));
+      else RET(keys_gemm_fwd(c, fs, m, 0, 1));
       RET(link(c, LANE_OF[m], 3));
       c.use(3);
-      RET(keys_gemm_fwd(c, m, 1, 2));
+      RET(keys_gemm_fwd(c, fs, m, 1, 2));
       c.use(LANE_OF[m]);
-      if (!k3_site0) RET(pool_fwd(c, 0, m));
-    } else if (k3_site0) {
-      RET(umca_site(c, 0, m, true));
-      RET(keys_gemm_fwd(c, m, 1, 2));
-    } else {
-      RET(keys_gemm_fwd(c, m, 0, 2));
-      RET(pool_fwd(c, 0, m));
-    }
-    mark(c.st, 30 + 4 * m);      // FRA2UTT site done
+      if (!M.k3_site0) RET(pool_fwd(c, fs, 0, m));
+      break;
+    case FwdSchedule::INLINE:
+      RET(umca_site(c, fs, 0, m, true));
+      RET(keys_gemm_fwd(c, fs, m, 1, 2));
+      break;
+    case FwdSchedule::INLINE_GROUPED_WITH_SITE0:
+      RET(keys_gemm_fwd(c, fs, m, 0, 2));
+      RET(pool_fwd(c, fs, 0, m));
+      break;
   }
-  mark(c.sts[3], 40);            // lane 3: keep-bits + Cross_Attention key projections done
+  mark(c.st, 30 + 4 * m);      // FRA2UTT site done
+  return SDUMC_OK;
+}
+
+// the caller's stream joins the modality lanes -- a lane that left an event behind its FRA2UTT site only up to that event -- and the
+// NEXT batch's assembly leaves beside everything from here on (sdumc_net_io.prefetch)
+int fwd_join_frames(const Ctx& c, const FwdEvents& ev) {
   c.use(0);
   for (int lane = 1; lane <= 2; ++lane) {
     int m_of = -1;
-    for (int m = 0; m < 3; ++m) if (LANE_OF[m] == lane && fra_done[m]) m_of = m;
-    if (m_of >= 0) {
-      if (hipStreamWaitEvent(c.sts[0], fra_done[m_of], 0) != hipSuccess) return SDUMC_ELAUNCH;
-    } else {
-      RET(link(c, lane, 0));
-    }
+    for (int m = 0; m < 3; ++m) if (LANE_OF[m] == lane && ev.fra_done[m]) m_of = m;
+    if (m_of >= 0) RET(await_on(c.sts[0], ev.fra_done[m_of]));
+    else RET(link(c, lane, 0));
   }
-  RET(issue_prefetch(c));      // the NEXT batch's assembly, beside everything from here on (sdumc_net_io.prefetch)
-  if (chain) {   // steps 3-7 in one launch
-    if (wt_done && hipStreamWaitEvent(c.st, wt_done, 0) != hipSuccess) return SDUMC_ELAUNCH;
-    const sdumc_chain_args ca = chain_args(c, true, nullptr, true);
+  return issue_prefetch(c);
+}
+
+// steps 3-7: one launch, or per layer
+int fwd_stage_a(const Ctx& c, const FwdSchedule& fs, const FwdEvents& ev) {
+  const Plan& pl = c.pl;
+  const ParamMap& pm = c.pm;
+  const int V = pl.V;
+  if (fs.chain) {
+    RET(await_on(c.st, ev.wt_done));
+    const sdumc_chain_args ca = chain_args(c, fs, true, nullptr, true);
     mark(c.st, 1);
-    RET(chain_launch(c, ca, 0));
+    RET(chain_launch(c, fs, ca, 0));
     mark(c.st, 2);
-  } else {
+    return SDUMC_OK;
+  }
   // 3. audio/text/video_mlp (model :293-295), grouped over the modality
   {
     sdumc_gemm g = G_(SDUMC_NT, V, D, D, 3);
@@ -1793,65 +1869,69 @@ int forward(const Ctx& c) {
     g.lda = g.ldb = g.ldc = D;
     RET(run(c, g));
   }
-  }   // !chain
-  // 8. cross_att_fra2utt_{0,1,2} (model :334-336): one grouped launch on the caller's stream (a fork/join around three 17-30 us
-  //    kernels cost 86-91 us between the two utterance-level launches, of which ~35 us were cross-queue event latency)
-  // their keys: lane 3 collects the own-lane projections' events, so that the caller's stream -- the critical chain -- takes ONE
-  // cross-stream wait between stage A and the pooling instead of one per lane
-  for (int m = 0; m < 3; ++m)
-    if (ca_done[m] && hipStreamWaitEvent(c.sts[3], ca_done[m], 0) != hipSuccess) return SDUMC_ELAUNCH;
-  RET(link(c, 3, 0));
-  if (pregen) {
-    // The keep-bits of the NEXT call (call index + 2: sdumc_train_step's advance) into the OTHER set, on lane 3 -- idle from here to
-    // the backward's early launch -- beside the latency-bound utterance-level stages: the Philox launches (VALU-bound, ~100 us of lane
-    // time at C2 where they competed with the frame projections, 23 + 17 + 7 us here) leave the head of the step.  The other set's tag
-    // is cleared before the set is refilled and written behind it, all on this lane; the next call -- the caller flips bits_phase --
-    // reads that set, and its head launch finds the tag on the same lane, behind its fork.  Issued BEHIND the event the caller's
-    // stream waits for in front of the Cross_Attention pooling: that wait must not include these launches.
-    c.use(3);
-    uint8_t* const nx = bits_set(c, 1);
-    uint32_t* tag = reinterpret_cast<uint32_t*>(nx);
-    // the NEXT call's dims (a ragged epoch announces them: sdumc_net_io.bits_next_dims) decide the layout of the set it will read
-    const sdumc_net_dims& nd = c.io.bits_next_dims ? *c.io.bits_next_dims : c.d;
-    Plan pn_own;
-    if (c.io.bits_next_dims && !make_plan(nd, pn_own)) return SDUMC_EINVAL;
-    const Plan& pn = c.io.bits_next_dims ? pn_own : pl;
-    const sdumc_bits_shape shape_next = bits_shape(nd);
-    auto mkdrop_next = [&](int site, int T, int s0) {
-      sdumc_dropout d = mkdrop(c, site, c.d.p_frame, T, D, s0);
-      d.samples = (uint32_t)nd.B;
-      d.sample0 = (uint32_t)nd.sample0;
-      return d;
-    };
-    const sdumc_dropout d0 = mkdrop_next(SITE_IN[0][0], pn.segs[0][0].T, 0);
-    RET(sdumc_bits_tag_(&d0, tag, -1, &shape_next, c.st));
-    const int order[3] = {0, 2, 1};
-    for (int oi = 0; oi < 3; ++oi) {
-      const int m = order[oi];
-      for (const Seg& sg : pn.segs[m]) {
-        sdumc_dropout d = mkdrop_next(SITE_IN[0][m], sg.T, sg.s0);
-        uint8_t* outs[2] = {nx + bits_next_off(pn, 0, m) + sg.row0 * (D / 4), nx + bits_next_off(pn, 1, m) + sg.row0 * (D / 4)};
-        RET(sdumc_dropout_bits_multi_ex_(&d, sg.V / pn.B, 2, SITE_IN[1][m] - SITE_IN[0][m], outs, nullptr, 2, nullptr, c.st));
-      }
+  return SDUMC_OK;
+}
+
+// The keep-bits of the NEXT call (call index + 2: sdumc_train_step's advance) into the OTHER set, on lane 3 -- idle from here to
+// the backward's early launch -- beside the latency-bound utterance-level stages: the Philox launches (VALU-bound, ~100 us of lane
+// time at C2 where they competed with the frame projections, 23 + 17 + 7 us here) leave the head of the step.  The other set's tag
+// is cleared before the set is refilled and written behind it, all on this lane; the next call -- the caller flips bits_phase --
+// reads that set, and its head launch finds the tag on the same lane, behind its fork.  Issued BEHIND the event the caller's
+// stream waits for in front of the Cross_Attention pooling: that wait must not include these launches.
+int fwd_next_bits(const Ctx& c) {
+  c.use(3);
+  uint8_t* const nx = bits_set(c, 1);
+  uint32_t* tag = reinterpret_cast<uint32_t*>(nx);
+  // the NEXT call's dims (a ragged epoch announces them: sdumc_net_io.bits_next_dims) decide the layout of the set it will read
+  const sdumc_net_dims& nd = c.io.bits_next_dims ? *c.io.bits_next_dims : c.d;
+  Plan pn_own;
+  if (c.io.bits_next_dims && !make_plan(nd, pn_own)) return SDUMC_EINVAL;
+  const Plan& pn = c.io.bits_next_dims ? pn_own : c.pl;
+  const sdumc_bits_shape shape_next = bits_shape(nd);
+  auto mkdrop_next = [&](int site, int T, int s0) {
+    sdumc_dropout d = mkdrop(c, site, c.d.p_frame, T, D, s0);
+    d.samples = (uint32_t)nd.B;
+    d.sample0 = (uint32_t)nd.sample0;
+    return d;
+  };
+  const sdumc_dropout d0 = mkdrop_next(SITE_IN[0][0], pn.segs[0][0].T, 0);
+  RET(sdumc_bits_tag_(&d0, tag, -1, &shape_next, c.st));
+  const int order[3] = {0, 2, 1};
+  for (int oi = 0; oi < 3; ++oi) {
+    const int m = order[oi];
+    for (const Seg& sg : pn.segs[m]) {
+      sdumc_dropout d = mkdrop_next(SITE_IN[0][m], sg.T, sg.s0);
+      uint8_t* outs[2] = {nx + bits_next_off(pn, 0, m) + sg.row0 * (D / 4), nx + bits_next_off(pn, 1, m) + sg.row0 * (D / 4)};
+      RET(sdumc_dropout_bits_multi_ex_(&d, sg.V / pn.B, 2, SITE_IN[1][m] - SITE_IN[0][m], outs, nullptr, 2, nullptr, c.st));
     }
-    RET(sdumc_bits_tag_(&d0, tag, 2, &shape_next, c.st));
-    c.use(0);
   }
-  if (attn_multi_ok(c)) {
-    RET(pool_fwd_multi(c, 1));
-  } else {
-    RET(fork_all(c));
-    for (int m = 0; m < 3; ++m) {
-      c.use(LANE_OF[m]);
-      RET(pool_fwd(c, 1, m));
-    }
-    c.use(0);
-    RET(join_all(c));
+  RET(sdumc_bits_tag_(&d0, tag, 2, &shape_next, c.st));
+  c.use(0);
+  return SDUMC_OK;
+}
+
+// 8. cross_att_fra2utt_{0,1,2} (model :334-336): one grouped launch on the caller's stream (a fork/join around three 17-30 us
+//    kernels cost 86-91 us between the two utterance-level launches, of which ~35 us were cross-queue event latency)
+int fwd_cross_pool(const Ctx& c, const FwdSchedule& fs) {
+  if (fs.pool_grouped) return pool_fwd_multi(c, fs, 1);
+  RET(fork_all(c));
+  for (int m = 0; m < 3; ++m) {
+    c.use(LANE_OF[m]);
+    RET(pool_fwd(c, fs, 1, m));
   }
-  if (chain) {   // steps 9-12 and the outputs in one launch
-    const sdumc_chain_args ca = chain_args(c, true, nullptr, false);
+  c.use(0);
+  return join_all(c);
+}
+
+// steps 9-12 and the outputs: one launch, or per layer
+int fwd_stage_b(const Ctx& c, const FwdSchedule& fs) {
+  const Plan& pl = c.pl;
+  const ParamMap& pm = c.pm;
+  const int V = pl.V;
+  if (fs.chain) {
+    const sdumc_chain_args ca = chain_args(c, fs, true, nullptr, false);
     mark(c.st, 3);
-    RET(chain_launch(c, ca, 1));
+    RET(chain_launch(c, fs, ca, 1));
     mark(c.st, 4);
     return SDUMC_OK;
   }
@@ -1906,6 +1986,23 @@ int forward(const Ctx& c) {
     if (n) RET(sdumc_copy2d_multi(sg, n, c.st));
   }
   return SDUMC_OK;
+}
+
+int forward(const Ctx& c, const FwdSchedule& fs) {
+  RET(fs.rc);
+  FwdEvents ev;
+  RET(fwd_head(c, fs, ev));
+  for (int m = 0; m < 3; ++m) RET(fwd_frame(c, fs, m, ev));      // three independent per-modality chains, one per lane
+  mark(c.sts[3], 40);            // lane 3: keep-bits + Cross_Attention key projections done
+  RET(fwd_join_frames(c, ev));
+  RET(fwd_stage_a(c, fs, ev));
+  // the Cross_Attention keys: lane 3 collects the own-lane projections' events, so that the caller's stream -- the critical chain --
+  // takes ONE cross-stream wait between stage A and the pooling instead of one per lane
+  for (int m = 0; m < 3; ++m) RET(await_on(c.sts[3], ev.ca_done[m]));
+  RET(link(c, 3, 0));
+  if (fs.pregen) RET(fwd_next_bits(c));
+  RET(fwd_cross_pool(c, fs));
+  return fwd_stage_b(c, fs);
 }
 
 // the pooling-backward descriptor of run sg of site (k, m), without its workspace
@@ -2162,18 +2259,16 @@ int keys_gemm_bwd(const Ctx& c, int m, int k0, int k1, int parts = 3, int rows_c
 
 // The backward pass.  plan_backward() decides the schedule -- which modality's Cross_Attention dX goes early and on which lane,
 // which weight gradients ride in which grouped launch -- ONCE, before the first launch; backward() and its parts read the record.
-struct BwdSchedule {
+struct BwdSchedule : UttPath {     // chain: 12'-9' and 7'-3' as one launch each; fra_fold: 8' leaves its dq slabs unsummed, the clustered stage 7'-3' sums the chunks
   int rc = SDUMC_OK;               // SDUMC_EINVAL: the schedule cannot serve the io (row maps with a per-layer frame dW, below)
   bool utterance = true;           // phases bit 0: the utterance-level part (finishes every gradient in [0, pm.early))
   bool frame = true;               // phases bit 1: the frame-level part
-  bool chain = false;              // 12'-9' and 7'-3' as one launch each (chain.hip) instead of per layer
   bool dw_grouped = false;         // the frame-level weight gradients leave in the grouped launches (gg_frame)
   bool pool_grouped = false;       // 8': the Cross_Attention pooling backward of all modalities as ONE launch on the caller's stream
   bool early_one_launch = false;   // the early Cross_Attention sites of every early modality: ONE rows launch on lane 3
   bool flush1_after_pool = false;  // batch 1 of the weight gradients leaves ahead of 8' (else it rides with the input_proj dW)
   bool flush2_after_query = false; // batch 2 (query_proj, the query MLPs) leaves behind 6' (grouped mode: it waits for batch 3)
   bool flush3_after_utt = false;   // batch 3 leaves behind 3' (else it rides with the FRA2UTT input_proj dW of the frame-level part)
-  bool fra_fold = false;           // 8' leaves its dq slabs unsummed: the clustered stage 7'-3' sums the chunks
   struct Mod {
     bool early = false;            // the Cross_Attention key-projection backward runs early, beside steps 7'-3'
     int early_lane = 3;            // ... on this lane: the modality's own, or lane 3
@@ -2192,14 +2287,13 @@ struct BwdSchedule {
     char* wfrag[3] = {nullptr, nullptr, nullptr};      // where modality m's packed transposed weight goes (widths % 256 == 0)
   } feat;
 };
-const float* feat_in(const Ctx& c, int m, int s) { return m == 0 ? c.io.audio : (m == 2 ? c.io.video : c.io.text[s]); }
 // launches nothing, records no event, touches no stream: a function of dims, io, the context's options, the process-wide switches
 // (environment, setters) and whether the caller's stream is under capture (c.capturing, asked once by init_lanes)
-BwdSchedule plan_backward(const Ctx& c, int phases) {
+BwdSchedule plan_backward(const Ctx& c, const UttPath& utt, int phases) {
   BwdSchedule s;
+  static_cast<UttPath&>(s) = utt;
   s.utterance = (phases & 1) != 0;
   s.frame = (phases & 2) != 0;
-  s.chain = use_chain(c);
   s.dw_grouped = gg_frame(c);
   s.pool_grouped = attn_multi_ok(c);
   // batch 1 of the weight gradients (heads, cross_attention_mlp, cross_*_mlp) -- in the grouped mode together with the
@@ -2209,7 +2303,6 @@ BwdSchedule plan_backward(const Ctx& c, int phases) {
   // they stay queued and ride with the FRA2UTT input_proj dW in one launch.
   s.flush3_after_utt = !(s.dw_grouped && s.frame);
   s.flush2_after_query = !s.chain && !gg_utt(c);
-  s.fra_fold = fra_fold(c);
   // Early Cross_Attention key-projection backward (bit m of c.bgb): a modality that owns a side lane keeps going on that lane --
   // the caller's stream waits only for the pooling backward before it, so the GEMMs run beside steps 7'-3' and, in phased
   // calls (the data-parallel step), beside whatever the caller does between the phases; a modality on the caller's stream
@@ -2338,8 +2431,8 @@ int bwd_heads(const Ctx& c, const sdumc_net_grads& og, const BwdSchedule& sch) {
   const float s_mlp = c.d.train ? 1.0f / (1.0f - (float)c.d.p_mlp) : 1.0f;
   auto dx = [&](int64_t off) { return per_layer ? c.p(off) : nullptr; };
   if (sch.chain) {
-    const sdumc_chain_args ca = chain_args(c, false, &og, false);
-    RET(chain_launch(c, ca, 2));
+    const sdumc_chain_args ca = chain_args(c, sch, false, &og, false);
+    RET(chain_launch(c, sch, ca, 2));
     mark(c.st, 6);
   }
   // 12'. heads: r = L2(relu(L0(z))), vals = fc_out_v(z), plus the external gradient of cross_fused_feat
@@ -2376,9 +2469,9 @@ int bwd_stage_a(const Ctx& c, const sdumc_net_grads& og, const BwdSchedule& sch)
   const float s_mlp = c.d.train ? 1.0f / (1.0f - (float)c.d.p_mlp) : 1.0f;
   auto dx = [&](int64_t off) { return per_layer ? c.p(off) : nullptr; };
   if (sch.chain) {
-    const sdumc_chain_args ca = chain_args(c, false, &og, true);
+    const sdumc_chain_args ca = chain_args(c, sch, false, &og, true);
     mark(c.st, 7);
-    RET(chain_launch(c, ca, 3));
+    RET(chain_launch(c, sch, ca, 3));
     mark(c.st, 8);
   }
   // 7'. query_proj: dW/db per modality, d_q = sum_m d_qp[m] W_q[m]
@@ -2849,21 +2942,20 @@ int ctx_init(Ctx& c) {
   c.init_lanes();
   return SDUMC_OK;
 }
-// join_bits: order the middle's fill of the other keep-bits set (lane 3, issued behind the last lane-3 -> caller link of forward())
-// before `stream` on return.  sdumc_train_step leaves that to its backward's final join; a forward on its own must not return with
-// lane 3 still reading rng_state / writing bits_next behind the caller's back (and, under capture, with an unjoined branch).
-int net_forward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, void* stream, bool join_bits) {
+}  // namespace
+// the schedule is decided -- and a batch it cannot serve refused -- before anything of the call is enqueued
+extern "C" int sdumc_net_forward(const sdumc_net_dims* d, const sdumc_net_io* io, void* stream) {
   RET(check_io(d, io));
   const SplitScope split_scope(io);
   Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
   RET(ctx_init(c));
-  RET(forward(c));
-  if (join_bits && (bits_pregen(c) || io->prefetch)) RET(link(c, 3, 0));
+  const FwdSchedule fs = plan_forward(c);
+  RET(forward(c, fs));
+  // order the middle's fill of the other keep-bits set (lane 3, issued behind the last lane-3 -> caller link of forward()) before
+  // `stream` on return.  sdumc_train_step leaves that to its backward's final join; a forward on its own must not return with
+  // lane 3 still reading rng_state / writing bits_next behind the caller's back (and, under capture, with an unjoined branch).
+  if (fs.pregen || io->prefetch) RET(link(c, 3, 0));
   return SDUMC_OK;
-}
-}  // namespace
-extern "C" int sdumc_net_forward(const sdumc_net_dims* d, const sdumc_net_io* io, void* stream) {
-  return net_forward_impl(d, io, stream, true);
 }
 
 namespace {
@@ -2877,7 +2969,7 @@ int net_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sdu
   Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
   RET(ctx_init(c));
   c.G = g->grads;
-  BwdSchedule sch = plan_backward(c, phases);
+  BwdSchedule sch = plan_backward(c, plan_utterance(c), phases);
   sch.feat = feat;
   return backward(c, *g, sch);
 }
@@ -3064,20 +3156,23 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   g.d_text_hidden = g.d_rnc + RD * V;
   g.d_cross_text = g.d_text_hidden + D * V;
   g.grads = reinterpret_cast<float*>(base + sl.grads);
-  // the backward's schedule first: a batch it cannot serve is rejected before the forward, the loss or a fork is enqueued
+  // both schedules first, on the step's one context: a batch either cannot serve is rejected before the forward, the loss or a fork
+  // is enqueued
   const SplitScope split_scope(&nio);
-  Ctx bc{*d, nio, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
-  RET(ctx_init(bc));
-  bc.G = g.grads;
-  const BwdSchedule sch = plan_backward(bc, 3);
+  Ctx c{*d, nio, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
+  RET(ctx_init(c));
+  c.G = g.grads;
+  const FwdSchedule fs = plan_forward(c);
+  const BwdSchedule sch = plan_backward(c, fs, 3);
+  RET(fs.rc);
   RET(sch.rc);
   mark(static_cast<hipStream_t>(stream), 0);
-  RET(net_forward_impl(d, &nio, stream, false));
+  RET(forward(c, fs));
   // the Adam bias-correction update rides in the loss's last launch, the dropout call counter in the Adam launch
   bool total_pending = false;
   RET(loss_backward_impl(d, &nio, cfg, &g, base + sl.loss, sl.net - sl.loss, stream, cfg->hyper, &total_pending));
   mark(static_cast<hipStream_t>(stream), 5);
-  RET(backward(bc, g, sch));
+  RET(backward(c, g, sch));
   mark(static_cast<hipStream_t>(stream), 9);
   sdumc_total_loss tl;
   tl.losses = total_pending ? cfg->losses : nullptr;      // (else the loss stage's own last launch wrote the total)

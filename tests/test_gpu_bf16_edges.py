@@ -12,6 +12,8 @@ itself sits 1-4 % from the plain oracle per gradient tensor, so those bars canno
   4     (64, 64, 64, 64)      2  (130, 3, 129, 5)   two whole chunks + 2 / + 1 frames
   5     (192, 64, 128, 64)    7  (64, 64, 64, 64)   odd B, whole chunks
   6     (128, 128, 128, 128)  4  (70, 9, 33, 6)     key-padding lengths (those of test_train_step_with_lengths_vs_oracle)
+  7     (128, 128, 128, 128)  2  (70, 9, 33, 32)    feat4's B T = 64 rows are a whole tile, text's 18 are not: one projection launch per
+                                                    stream (the one-launch rule of the text slot is read off stream 0's rows alone)
 
 One TrainStep(bf16=True) in train mode with Philox masks each: the loss and its six terms and the five outputs of both streams at
 BF16_EMU_OUT_TOL, every gradient tensor through tests/grad_parity.py at BF16_EMU_GRAD_TOL (the project's numbers:
@@ -39,7 +41,8 @@ CASES = {1: ((128, 128, 128, 128), 1, (1, 1, 1, 1), False),
          3: ((128, 256, 128, 256), 5, (70, 9, 33, 4), False),
          4: ((64, 64, 64, 64), 2, (130, 3, 129, 5), False),
          5: ((192, 64, 128, 64), 7, (64, 64, 64, 64), False),
-         6: ((128, 128, 128, 128), 4, (70, 9, 33, 6), True)}
+         6: ((128, 128, 128, 128), 4, (70, 9, 33, 6), True),
+         7: ((128, 128, 128, 128), 2, (70, 9, 33, 32), False)}
 
 
 def site_tensors(m):

@@ -1,5 +1,5 @@
 """GPU parity tests of the PER-LAYER utterance path: engine.hip::forward steps 3-7 / 9-12 and the mirror backward, built from
-grouped sdumc_gemm_f32 launches and the small kernels of elementwise.hip.  It is taken when use_chain() is false: V = streams x B
+grouped sdumc_gemm_f32 launches and the small kernels of elementwise.hip.  It is taken when plan_utterance()'s `chain` is false: V = streams x B
 > 512, or SDUMC_CHAIN=0.  The clustered and the one-launch-per-stage kernels (V <= 128, V <= 512) are held to the oracle all over
 the suite; this file holds the third path to the same bars:
   (a) forward + backward with external output gradients on both sides of the switch (V = 512 -> chain.hip, V = 514 / 513 -> per
@@ -53,6 +53,11 @@ def norm_err(got, want):
 
 def gemm_launches(fn):
     """Number of sdumc_gemm_f32 launches `fn` makes (one lane, as bench.py's roofline leg counts them)."""
+    return sum(gemm_variants(fn).values())
+
+
+def gemm_variants(fn):
+    """{kernel variant: launches} of the GEMM launches `fn` makes (sdumc_profile_report; one lane)."""
     from sdumc_amd import _lib
     lib = _lib.lib
     torch.cuda.synchronize()
@@ -67,7 +72,7 @@ def gemm_launches(fn):
         lib.sdumc_profile_enable(0)
         lib.sdumc_set_concurrency(1)
     assert n > 0, "sdumc_profile_report failed"
-    return int(sum(arr[i].launches for i in range(n)))
+    return {arr[i].name.decode(): int(arr[i].launches) for i in range(n) if arr[i].launches}
 
 
 def net_case(E, B, Tn, streams, mode, zero_video=None, pseed=11, bseed=5, seed=99, call0=4):
@@ -204,7 +209,7 @@ def _forward_launches(E, B, Tn):
 
 def test_per_layer_path_launches_the_utterance_gemms(E):
     """chain.hip runs the utterance-level layers inside its own kernels; the per-layer path launches them as sdumc_gemm_f32.  If
-    use_chain()'s threshold moves, B = 257 stops testing the per-layer path and this assertion says so."""
+    plan_utterance()'s threshold moves, B = 257 stops testing the per-layer path and this assertion says so."""
     n256, n257 = _forward_launches(E, 256, TN), _forward_launches(E, 257, TN)
     print(f"\nsdumc_gemm_f32 launches per forward: B=256 {n256}, B=257 {n257}")
     assert n257 > n256

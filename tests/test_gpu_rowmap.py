@@ -355,3 +355,98 @@ def test_forward_still_accepts_the_batch_the_backward_rejects(env, streams, reas
     torch.cuda.synchronize()
     for a, b in zip(got, want):
         assert torch.equal(a, b)
+
+
+# ---- a row-mapped batch the FORWARD's schedule cannot serve (plan_forward's rc) is refused before anything of the call runs ----
+# Only the plane GEMM (fp32 storage) and the fragment-major bf16 GEMM fetch their A rows through a map.  A context whose split option
+# turns the wide-tile family's split arithmetic off (SDUMC_SPLIT_WIDE) has no plane route; the grouped weight-gradient launch keeps its
+# own (SDUMC_SPLIT_GROUP), so the backward's schedule accepts the batch and the refusal is the forward's.
+_SPLIT_NO_WIDE = 13      # every family but the wide-tile one
+_LENS = tuple((t, max(1, t // 2)) for t in _RT)      # key-padding lengths per modality (audio, text, video, feat4), _RB samples
+
+
+def _refused_forward(_lib, streams, rejected_first):
+    """one train-mode sdumc_net_forward of the servable batch; with rejected_first the same context and call object saw the refused
+    call before"""
+    from sdumc_amd import engine
+    ctx = engine.ExecContext()
+    flat = _flat_params()
+    rb = _resident_batch(streams, 70)
+    call = _net_call(flat, rb, streams, True, ctx)
+    _map_io(call, rb)
+    call.set_lengths(_LENS[:3] if streams == 1 else _LENS)
+    if rejected_first:
+        ctx.set_option("split", _SPLIT_NO_WIDE)
+        outs = (call.vals, call.fused, call.rnc, call.text_hidden, call.cross_text)
+        for t in outs:
+            t.fill_(-77.0)
+        rng = call._keep[4]
+        state = (call.workspace, flat, rng.t)
+        before = [t.clone() for t in state]
+        torch.cuda.synchronize()
+        with pytest.raises(_lib.SdumcError, match="SDUMC_EINVAL"):
+            call.forward()
+        torch.cuda.synchronize()
+        for t in outs:
+            assert bool((t == -77.0).all()), "a launch of the refused forward wrote an output"
+        for name, t, b in zip(("workspace", "parameters", "dropout counter"), state, before):
+            assert torch.equal(t, b), f"the refused forward changed the {name}"
+        ctx.set_option("split", None)
+    got = [t.clone() for t in call.forward()]
+    torch.cuda.synchronize()
+    return got
+
+
+@pytest.mark.parametrize("streams", [1, 2])
+def test_row_mapped_forward_without_a_plane_route_is_refused_before_anything_runs(env, streams):
+    """sdumc_net_forward with row maps, key-padding lengths and no plane route: SDUMC_EINVAL with the five outputs, the whole
+    workspace (the expanded lengths included), the parameters and the dropout counter untouched; the same context then runs the
+    batch bit for bit like a context that never saw the refused call."""
+    _lib, ops = env
+    after, fresh = _refused_forward(_lib, streams, True), _refused_forward(_lib, streams, False)
+    assert bool(torch.isfinite(fresh[0]).all())
+    for a, b in zip(after, fresh):
+        assert torch.equal(a, b), "a forward after the refused call differs from one on a fresh context"
+
+
+def test_row_mapped_train_step_without_a_plane_route_is_refused_before_anything_runs(env):
+    """sdumc_train_step on the same batch and context: the backward's schedule accepts it, the forward's does not -- SDUMC_EINVAL
+    with the outputs, the loss record, the whole step workspace, the parameters, the Adam state and the dropout counter untouched;
+    the same context then runs the step bit for bit like a fresh one."""
+    _lib, ops = env
+    from sdumc_amd import engine
+    rb = _resident_batch(2, 70)
+    steps = []
+    for rejected_first in (True, False):
+        flat = _flat_params()
+        ctx = engine.ExecContext()
+        step = engine.TrainStep(flat, _RB, _RT, _RD, seed=3, planes=True, ctx=ctx)
+        _bind_store(step, rb, 7)
+        step.set_lengths(_LENS)
+        if rejected_first:
+            ctx.set_option("split", _SPLIT_NO_WIDE)
+            outs = (step.vals, step.fused, step.rnc, step.text_hidden, step.cross_text, step.losses, step.grads)
+            for t in outs:
+                t.fill_(-77.0)
+            step.adam_m.fill_(0.25)
+            step.adam_v.fill_(0.5)
+            state = (step.workspace, flat, step.adam_m, step.adam_v, step.hyper, step.rng.t)
+            before = [t.clone() for t in state]
+            torch.cuda.synchronize()
+            with pytest.raises(_lib.SdumcError, match="SDUMC_EINVAL"):
+                step.launch()
+            torch.cuda.synchronize()
+            for t in outs:
+                assert bool((t == -77.0).all()), "a launch of the refused step wrote an output"
+            for name, t, b in zip(("workspace", "parameters", "adam_m", "adam_v", "hyper", "dropout counter"), state, before):
+                assert torch.equal(t, b), f"the refused step changed the {name}"
+            ctx.set_option("split", None)
+            step.adam_m.zero_()
+            step.adam_v.zero_()
+            step.grads.zero_()
+        losses = step.run().clone()
+        torch.cuda.synchronize()
+        steps.append((losses, flat, step.adam_m, step.adam_v, step.hyper))
+    assert bool(torch.isfinite(steps[0][0]).all()) and float(steps[0][2].abs().max()) > 0
+    for a, b in zip(*steps):
+        assert torch.equal(a, b), "a step after the refused call differs from one on a fresh context"
