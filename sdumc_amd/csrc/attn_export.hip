@@ -20,8 +20,6 @@
 #include "common.h"
 
 namespace {
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-
 constexpr int CH = 64, NQ = SDUMC_NQ, WAVES = 4, MAXPAIR = 6;
 
 struct ExportArgs {
@@ -127,8 +125,4 @@ extern "C" int sdumc_net_export_attention(const sdumc_net_dims* d, const sdumc_n
   return SDUMC_OK;
 }
 
-__global__ void sdumc_preload_attn_export_kernel() {}
-extern "C" int sdumc_preload_attn_export_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_attn_export_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(attn_export)      // (common.h)

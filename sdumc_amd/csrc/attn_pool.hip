@@ -30,22 +30,8 @@ constexpr int D = SDUMC_D;       // one channel block = 256 channels = 64 lanes 
 constexpr int MAXQ = 8;
 constexpr int CH = 64;           // rows of one v handled by a 4-wave workgroup (16 per wave)
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// agent-scope (write-through / L2-bypassing) accesses for data that another workgroup of the SAME launch reads after a ticket
-// hand-shake (descriptor field `tickets`): the chunks of one sample may run on different XCDs, whose L2s are not coherent
-__device__ __forceinline__ void stf_dev(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ldf_dev(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st4_dev(float* p, f32x4 v) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) stf_dev(p + j, v[j]);
-}
-__device__ __forceinline__ f32x4 ld4_dev(const float* p) {
-  f32x4 v;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = ldf_dev(p + j);
-  return v;
-}
+// (descriptor field `tickets`: data that another workgroup of the SAME launch reads after a ticket hand-shake is written and read
+//  with the agent-scope accesses of prims.h -- the chunks of one sample may run on different XCDs)
 // true in exactly one workgroup per ticket: the last of `n` to arrive (which also re-arms the ticket).  Every thread calls it,
 // after the workgroup's agent-scope stores; ends with a barrier.
 __device__ __forceinline__ bool last_arrival(uint32_t* ticket, uint32_t n, int* s_flag) {
@@ -59,7 +45,6 @@ __device__ __forceinline__ bool last_arrival(uint32_t* ticket, uint32_t n, int* 
   __syncthreads();
   return *s_flag != 0;
 }
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 // Frame tensors (x, keys, dz, dxd) are fp32, or bf16 in the engine's bf16-storage mode (sdumc_attnpool.bf16): `base` is the
 // tensor's address as float*, `off` an ELEMENT offset; 4 consecutive channels either way (16 or 8 bytes).
 template <bool HF>
@@ -1289,8 +1274,6 @@ extern "C" int sdumc_attnpool_bwd_multi(const sdumc_attnpool_bwd_t* bs, int32_t 
 // ====================================================================================================================
 namespace sdumc_k3 {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
 constexpr int BM = 64, BN = 256, BK = 16, NST = 3, NW = 4;
 constexpr int A_BYTES = BM * BK * 4, B_BYTES = BN * BK * 4, BITS_LDS = 256;
 constexpr int A_CH = A_BYTES / 1024, B_CH = B_BYTES / 1024;
@@ -1303,7 +1286,6 @@ constexpr int LDS_BYTES = TOP_BYTES + Q_BYTES;
 static_assert(4 * MAXQ * D * 4 <= TOP_BYTES, "the pooling reduce overlays the key tile");
 
 __device__ __forceinline__ int swz16(int row) { return (row >> 2) & 3; }   // gemm_wide.hip swz<16>
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }   // = gemm_wide.hip
 
 // SPLIT: the key projection's fp32 products on the bf16 matrix pipe from exactly split operands (gemm_group.hip, "fp32 products
 // on the bf16 pipe", has the arithmetic; sdumc_hip.h: sdumc_set_split_).
@@ -1604,12 +1586,4 @@ extern "C" int sdumc_umca_fwd(const sdumc_umca* up, void* stream) {
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_attn_pool_kernel() {}
-extern "C" int sdumc_preload_attn_pool_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_attn_pool_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(attn_pool)      // (common.h)

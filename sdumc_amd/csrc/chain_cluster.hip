@@ -53,17 +53,6 @@ struct Cl {
   uint32_t mode;    // sdumc_chain_args.cl_mode
 };
 
-__device__ __forceinline__ void st4_dev(float* p, f32x4 v) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) __hip_atomic_store(p + j, v[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ f32x4 ld4_dev(const float* p) {
-  f32x4 v;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = __hip_atomic_load(p + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return v;
-}
-
 // rows [row0, row0 + ROWS) of a global [.., width] tensor (written by the cluster's members in this launch) -> LDS
 template <int ROWS>
 __device__ __forceinline__ void reload_rows(float* dst_lds, int ld_dst, const float* src, int64_t ld_src, int width, int row0, int nrows) {
@@ -1344,12 +1333,4 @@ extern "C" int sdumc_chain_cluster_trace_(int on, double* out) {
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_chain_cluster_kernel() {}
-extern "C" int sdumc_preload_chain_cluster_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_chain_cluster_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(chain_cluster)      // (common.h)

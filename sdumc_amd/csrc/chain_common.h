@@ -14,10 +14,6 @@ constexpr int D = SDUMC_D, H = SDUMC_H, NQ = SDUMC_NQ, RD = SDUMC_RNC_DIM;
 constexpr int NTHR = 512, NWV = 8;
 constexpr int PART_FLOATS = NWV * 7 * D;   // partial-sum area: 8 waves x up to 7 rows x 256 columns (or 2 rows x 896)
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
 __device__ __forceinline__ DropRT mkdrop_rt(const DropRT& base, uint32_t site, uint32_t rows, uint32_t width) {
   DropRT d = base;     // resolved once per kernel (seed / call counter come from device memory)
   d.site = site;

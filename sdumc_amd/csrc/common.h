@@ -9,8 +9,7 @@
     if (hipGetLastError() != hipSuccess) return SDUMC_ELAUNCH; \
   } while (0)
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "prims.h"   // f32x4 and the device primitives every kernel source shares
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
@@ -18,7 +17,6 @@ static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 // them).  sdumc_once_per_device runs `setup` (returns true on success) the first time the CURRENT device asks: under a lock, and the
 // device's bit is set only AFTER the setup has succeeded -- a second host thread on the same device either finds the attribute applied
 // or waits for it, and a failed setup is retried by the next call instead of being remembered as done.
-#ifdef __cplusplus
 #include <atomic>
 #include <mutex>
 struct sdumc_dev_once {
@@ -41,7 +39,73 @@ template <class K>
 static inline bool sdumc_set_dyn_lds(K kernel, size_t bytes) {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
-#endif
+// compute units of the current device (what a persistent launch sizes its grid by), cached per device; 256 where the query fails
+inline int sdumc_cu_count() {
+  static std::atomic<int> per_device[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  int n = per_device[dev].load(std::memory_order_relaxed);
+  if (!n) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    per_device[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
+// ---------------------------------------------------------------------------
+// Code-object preload.  One empty kernel per source file = per gfx950 code object: the file's hook asks for that kernel's attributes,
+// which makes the HIP runtime load the file's code object NOW (outside any timed or latency-sensitive region) instead of at the first
+// launch of one of its kernels -- with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms
+// gap in the middle of an epoch, at the first batch whose shape took a fallback path: profiles/README.md, round 6).
+// Every source of the Makefile's SRCS has ONE line `SDUMC_PRELOAD_HOOK(<file stem>)` and one entry in the list below; engine.hip
+// declares and calls the hooks from the list (preload_code_objects), and tests/test_source_lists_cpu.py holds the two to SRCS.
+// ---------------------------------------------------------------------------
+#define SDUMC_PRELOAD_SOURCES(X)                                                                                                  \
+  X(gemm_f32) X(gemm_wide) X(gemm_p3) X(frame_dx) X(frame_saliency) X(gemm_b1) X(gemm_group) X(gemm_rows) X(gemm_bf16) X(attn_pool) \
+  X(attn_export) X(elementwise) X(loss) X(adam) X(chain) X(chain_cluster) X(engine) X(transformer) X(resample) X(epoch_record)     \
+  X(tensor_norms) X(grad_guard)
+#define SDUMC_PRELOAD_HOOK_OF(stem)                                                                                                  \
+  extern "C" int sdumc_preload_##stem##_(void) {                                                                                     \
+    hipFuncAttributes a;                                                                                                             \
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_##stem##_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH; \
+  }
+#define SDUMC_PRELOAD_HOOK(stem)                  \
+  __global__ void sdumc_preload_##stem##_kernel() {} \
+  SDUMC_PRELOAD_HOOK_OF(stem)
+
+// ---------------------------------------------------------------------------
+// Profile variants (sdumc_profile_report; bench.py's roofline leg and tests/gemm_cases.py read the names): ONE list gives the
+// enumerator SDUMC_PV_<name> a launcher passes to sdumc_prof_begin_ and the name at that index of the report.  A new GEMM route
+// appends a line; the order is the report's order.
+// ---------------------------------------------------------------------------
+#define SDUMC_PROF_VARIANTS(X)                                                                                              \
+  X(gemm_nt_128x128) X(gemm_nt_64x64) X(gemm_nn_128x128) X(gemm_nn_64x64) X(gemm_tn_128x128) X(gemm_tn_64x64) /* gemm_f32.hip */ \
+  X(gemm_small_nt) X(gemm_small_nn) X(gemm_small_tn)                                                                        \
+  X(gemm_bf16_nt_128x128) X(gemm_bf16_nt_64x64) X(gemm_bf16_nn_128x128) X(gemm_bf16_nn_64x64) X(gemm_bf16_tn_128x128)      \
+  X(gemm_bf16_tn_64x64)                                                                                                     \
+  X(gemm_wide_nt) X(gemm_wide_tn)                                                                                           \
+  X(gemm_bf16s_nt) X(gemm_bf16s_tn)           /* gemm_bf16.hip (bf16 storage) */                                            \
+  X(gemm_group_tn) X(gemm_group_tn_bf16)      /* gemm_group.hip (the persistent kernel alone, without its reduce) */        \
+  X(gemm_rows256) X(gemm_rows256_bf16)        /* gemm_rows.hip */                                                           \
+  /* fp32 operands, products on the bf16 matrix pipe from exactly split operands (sdumc_set_split_) */                      \
+  X(gemm_wide_nt_bf16x3) X(gemm_group_tn_bf16x3) X(gemm_rows256_bf16x3)                                                     \
+  /* gemm_p3.hip: operands pre-split into bf16 planes (P3 tensors); the two instantiations rocprof lists too: plain (frame  \
+     projections), keep-bits on A (key projections) */                                                                      \
+  X(gemm_p3_nt_bf16x3) X(gemm_p3_nt_masked_bf16x3)                                                                          \
+  X(gemm_b1_nt_bf16)
+enum sdumc_prof_variant {
+#define SDUMC_PV_ENUM(name) SDUMC_PV_##name,
+  SDUMC_PROF_VARIANTS(SDUMC_PV_ENUM)
+#undef SDUMC_PV_ENUM
+  SDUMC_PV_COUNT
+};
+extern "C" {
+// gemm_f32.hip: bench.py's per-launch HIP events on the launch stream.  begin returns a token: -1 = profiling is off, -2 = the events
+// could not be created; end records the closing event (a negative token: nothing); drop takes the record back (a route that declined)
+int sdumc_prof_begin_(int variant, double flops, void* stream);
+void sdumc_prof_end_(int token, void* stream);
+void sdumc_prof_drop_(int token);
+}
 
 // ---------------------------------------------------------------------------
 // Internal entry points (not part of include/sdumc_hip.h): fused variants the engine's train step uses to take

@@ -13,10 +13,6 @@ constexpr int D = SDUMC_D;
 constexpr int H = SDUMC_H;
 constexpr int NQ = SDUMC_NQ;
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
 __global__ void relu_drop_bwd_kernel(const float* dy, const float* y, float scale, float* dz, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dz[i] = y[i] > 0.f ? dy[i] * scale : 0.f;
@@ -902,12 +898,4 @@ extern "C" int sdumc_dp_unpack(const float* records, int32_t W, int32_t B, int32
 
 extern "C" const char* sdumc_version(void) { return "sdumc_hip 0.1 (gfx950)"; }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_elementwise_kernel() {}
-extern "C" int sdumc_preload_elementwise_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_elementwise_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(elementwise)      // (common.h)

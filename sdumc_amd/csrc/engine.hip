@@ -521,49 +521,21 @@ LaneSet* default_lanes() {
 }
 void ensure_side_streams() { (void)default_lanes(); }
 }  // namespace
-extern "C" int sdumc_preload_gemm_f32_(void);
-extern "C" int sdumc_preload_gemm_wide_(void);
-extern "C" int sdumc_preload_gemm_p3_(void);
-extern "C" int sdumc_preload_gemm_b1_(void);
-extern "C" int sdumc_preload_gemm_group_(void);
-extern "C" int sdumc_preload_gemm_rows_(void);
-extern "C" int sdumc_preload_gemm_bf16_(void);
-extern "C" int sdumc_preload_attn_pool_(void);
-extern "C" int sdumc_preload_attn_export_(void);
-extern "C" int sdumc_preload_elementwise_(void);
-extern "C" int sdumc_preload_loss_(void);
-extern "C" int sdumc_preload_adam_(void);
-extern "C" int sdumc_preload_chain_(void);
-extern "C" int sdumc_preload_chain_cluster_(void);
-extern "C" int sdumc_preload_transformer_(void);
-extern "C" int sdumc_preload_frame_dx_(void);
-extern "C" int sdumc_preload_grad_guard_(void);
+namespace { __global__ void sdumc_preload_engine_kernel() {} }      // (this file's empty kernel keeps its unnamed namespace)
+SDUMC_PRELOAD_HOOK_OF(engine)
+#define SDUMC_DECLARE_HOOK(stem) extern "C" int sdumc_preload_##stem##_(void);
+SDUMC_PRELOAD_SOURCES(SDUMC_DECLARE_HOOK)
+#undef SDUMC_DECLARE_HOOK
 namespace {
-__global__ void sdumc_preload_engine_kernel() {}
-// every code object of the library loaded on the current device, once per device (see the note at the end of any kernel source);
+// every code object of the library loaded on the current device, once per device (common.h: SDUMC_PRELOAD_SOURCES);
 // called from the *_workspace_bytes queries every caller makes first -- never under stream capture, never inside a step
 void preload_code_objects() {
   static sdumc_dev_once once;
   (void)sdumc_once_per_device(once, [] {
-    hipFuncAttributes a;
-    bool ok = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_engine_kernel)) == hipSuccess;
-    ok = sdumc_preload_gemm_f32_() == SDUMC_OK && ok;
-    ok = sdumc_preload_gemm_wide_() == SDUMC_OK && ok;
-    ok = sdumc_preload_gemm_p3_() == SDUMC_OK && ok;
-    ok = sdumc_preload_gemm_b1_() == SDUMC_OK && ok;
-    ok = sdumc_preload_gemm_group_() == SDUMC_OK && ok;
-    ok = sdumc_preload_gemm_rows_() == SDUMC_OK && ok;
-    ok = sdumc_preload_gemm_bf16_() == SDUMC_OK && ok;
-    ok = sdumc_preload_attn_pool_() == SDUMC_OK && ok;
-    ok = sdumc_preload_attn_export_() == SDUMC_OK && ok;
-    ok = sdumc_preload_elementwise_() == SDUMC_OK && ok;
-    ok = sdumc_preload_loss_() == SDUMC_OK && ok;
-    ok = sdumc_preload_adam_() == SDUMC_OK && ok;
-    ok = sdumc_preload_chain_() == SDUMC_OK && ok;
-    ok = sdumc_preload_chain_cluster_() == SDUMC_OK && ok;
-    ok = sdumc_preload_transformer_() == SDUMC_OK && ok;
-    ok = sdumc_preload_frame_dx_() == SDUMC_OK && ok;
-    ok = sdumc_preload_grad_guard_() == SDUMC_OK && ok;
+    bool ok = true;
+#define SDUMC_CALL_HOOK(stem) ok = sdumc_preload_##stem##_() == SDUMC_OK && ok;
+    SDUMC_PRELOAD_SOURCES(SDUMC_CALL_HOOK)
+#undef SDUMC_CALL_HOOK
     return ok;
   });
 }

@@ -34,11 +34,6 @@ struct RecordArgs {
   float* log_row;
 };
 
-__device__ __forceinline__ void take(float x, double& acc, uint32_t& bad) {
-  acc = fma((double)x, (double)x, acc);
-  bad += (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;      // NaN or +-Inf
-}
-
 // columns 0..7 the loss vector as it stands, 8 grad_norm, 9 non-finite gradient elements, 10 B, 11 the learning rate
 __device__ __forceinline__ void write_log_row(const RecordArgs& a, float norm, float bad) {
   const int t = threadIdx.x;
@@ -77,11 +72,11 @@ __global__ __launch_bounds__(NT) void epoch_record_kernel(const RecordArgs a) {
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) take(v[u][j], acc, bad);
+      for (int j = 0; j < 4; ++j) sumsq_count_nonfinite(v[u][j], acc, bad);
   }
   if (bid == 0 && t == 0) {
-    for (int64_t k = 0; k < a.head; ++k) take(a.grads[k], acc, bad);
-    for (int64_t k = a.head + 4 * a.nquad; k < a.n; ++k) take(a.grads[k], acc, bad);
+    for (int64_t k = 0; k < a.head; ++k) sumsq_count_nonfinite(a.grads[k], acc, bad);
+    for (int64_t k = a.head + 4 * a.nquad; k < a.n; ++k) sumsq_count_nonfinite(a.grads[k], acc, bad);
   }
   s_sum[t] = acc;
   s_bad[t] = bad;
@@ -175,3 +170,5 @@ extern "C" int sdumc_epoch_record(const sdumc_epoch_rec* r, void* stream) {
   }
   return SDUMC_OK;
 }
+
+SDUMC_PRELOAD_HOOK(epoch_record)      // (common.h)

@@ -268,9 +268,4 @@ extern "C" int sdumc_frame_dx(const sdumc_frame_dx_t* p, void* stream) {
   return SDUMC_OK;
 }
 
-// (one empty kernel per source file: sdumc_preload_() makes the runtime load this code object outside any timed region; gemm_p3.hip)
-__global__ void sdumc_preload_frame_dx_kernel() {}
-extern "C" int sdumc_preload_frame_dx_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_frame_dx_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(frame_dx)      // (common.h)

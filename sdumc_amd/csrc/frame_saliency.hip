@@ -140,3 +140,5 @@ extern "C" int sdumc_frame_saliency(const sdumc_saliency_desc* descs, int32_t n,
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
 }
+
+SDUMC_PRELOAD_HOOK(frame_saliency)      // (common.h)

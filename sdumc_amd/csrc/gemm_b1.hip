@@ -23,20 +23,9 @@
 
 namespace sdumc_b1 {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
-__device__ __forceinline__ float bf2f(uint32_t h16) { return __uint_as_float(h16 << 16); }
-__device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {       // two fp32 -> one dword of two bf16 (round to nearest even)
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2s __attribute__((ext_vector_type(2)));
-  const f32x2s v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
 
 constexpr int BN = 256, BM = 64, NW = 4, NTHR = 256, TM = 2, TN = 2;
 constexpr int SK = 64, KS = 4;                 // k per stage, MFMA k-steps (16 k) per stage
@@ -230,7 +219,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_b1_nt_kernel(const Args a) {
           }
           if (g.c_bf16) {
             uint32_t* dst = reinterpret_cast<uint32_t*>(static_cast<unsigned short*>(g.C) + (size_t)row * g.ldc + col);
-            *reinterpret_cast<u32x4*>(dst) = u32x4{f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7])};
+            *reinterpret_cast<u32x4*>(dst) = u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
           } else {
             float* dst = static_cast<float*>(g.C) + (size_t)row * g.ldc + col;
             *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
@@ -280,7 +269,7 @@ __global__ __launch_bounds__(256) void b1_splitk_reduce_kernel(const sdumc_gemm_
   }
   if (g.c_bf16) {
     uint32_t* dst = reinterpret_cast<uint32_t*>(static_cast<unsigned short*>(g.C) + (size_t)row * g.ldc + col);
-    *reinterpret_cast<u32x4*>(dst) = u32x4{f2bf2(v[0], v[1]), f2bf2(v[2], v[3]), f2bf2(v[4], v[5]), f2bf2(v[6], v[7])};
+    *reinterpret_cast<u32x4*>(dst) = u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
   } else {
     float* dst = static_cast<float*>(g.C) + (size_t)row * g.ldc + col;
     *reinterpret_cast<f32x4*>(dst) = f32x4{v[0], v[1], v[2], v[3]};
@@ -306,7 +295,7 @@ __global__ __launch_bounds__(256) void b1_frag_multi_kernel(const float* __restr
     const f32x4 a0 = *reinterpret_cast<const f32x4*>(sp), a1 = *reinterpret_cast<const f32x4*>(sp + 4);
     const int rb = row >> 5, li = row & 31, kt = c >> 1, lh = c & 1;
     char* d = out + ((int64_t)rb * (cols >> 4) + kt) * FRAG_KT + (lh * 32 + li) * 16;
-    *reinterpret_cast<u32x4*>(d) = u32x4{f2bf2(a0[0], a0[1]), f2bf2(a0[2], a0[3]), f2bf2(a1[0], a1[1]), f2bf2(a1[2], a1[3])};
+    *reinterpret_cast<u32x4*>(d) = u32x4{pack_bf16x2(a0[0], a0[1]), pack_bf16x2(a0[2], a0[3]), pack_bf16x2(a1[0], a1[1]), pack_bf16x2(a1[2], a1[3])};
   }
 }
 
@@ -330,9 +319,6 @@ inline Plan plan(const sdumc_gemm_b1& g, size_t have) {
 }
 
 }  // namespace sdumc_b1
-
-extern "C" int sdumc_prof_begin_(int variant, double flops, void* stream);     // gemm_f32.hip: bench.py's per-launch HIP events
-extern "C" void sdumc_prof_end_(int token, void* stream);
 
 extern "C" size_t sdumc_gemm_b1_workspace_bytes(const sdumc_gemm_b1* g) {
   if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0 || (g->K % (2 * sdumc_b1::SK))) return 0;
@@ -365,7 +351,7 @@ extern "C" int sdumc_gemm_b1_nt(const sdumc_gemm_b1* gp, void* stream) {
       }) != SDUMC_OK)
     return SDUMC_ELAUNCH;
   hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(28, 2.0 * g.M * (double)g.N * g.K, stream);
+  const int tok = sdumc_prof_begin_(SDUMC_PV_gemm_b1_nt_bf16, 2.0 * g.M * (double)g.N * g.K, stream);
   Args a{g, p.nsplit, p.kchunk};
   const dim3 grid((unsigned)(((g.M + BM - 1) / BM) * (g.N / BN)), (unsigned)p.nsplit);
   if (mode == 0) hipLaunchKernelGGL(gemm_b1_nt_kernel<0>, grid, dim3(NTHR), LDS_BYTES, st, a);
@@ -399,12 +385,4 @@ extern "C" int sdumc_b1_frag_multi(const float* P, void* dst, const int64_t* src
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_b1_kernel() {}
-extern "C" int sdumc_preload_gemm_b1_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_b1_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_b1)      // (common.h)

@@ -28,19 +28,9 @@
 
 namespace sdumc_bf16 {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
-
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 h = (__bf16)f;      // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-  return *reinterpret_cast<unsigned short*>(&h);
-}
 
 template <int BM_, int BN_, int WGM_, int WGN_, int BK_, int NST_, bool KC_, int OCC_>
 struct HCfg {
@@ -409,9 +399,6 @@ int launch(const sdumc_gemm_bf16& g, const Plan& p, bool cs, hipStream_t st) {
 
 }  // namespace sdumc_bf16
 
-extern "C" int sdumc_prof_begin_(int variant, double flops, void* stream);     // gemm_f32.hip: bench.py's per-launch HIP events
-extern "C" void sdumc_prof_end_(int token, void* stream);
-
 extern "C" size_t sdumc_gemm_bf16_workspace_bytes(const sdumc_gemm_bf16* g) {
   if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0 || g->groups < 1) return 0;
   return sdumc_bf16::ws_bytes(*g, sdumc_bf16::plan(*g, (size_t)-1).nsplit);
@@ -445,7 +432,7 @@ extern "C" int sdumc_gemm_bf16_run(const sdumc_gemm_bf16* gp, void* stream) {
   const Plan p = plan(g, g.workspace ? g.workspace_bytes : 0);
   if (p.nsplit > 1 && (!g.workspace || g.workspace_bytes < ws_bytes(g, p.nsplit))) return SDUMC_ENOMEM;
   hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(nt ? 17 : 18, 2.0 * g.M * (double)g.N * g.K * g.groups, stream);
+  const int tok = sdumc_prof_begin_(nt ? SDUMC_PV_gemm_bf16s_nt : SDUMC_PV_gemm_bf16s_tn, 2.0 * g.M * (double)g.N * g.K * g.groups, stream);
   int rc;
   if (nt) rc = nt_small(g) ? launch<NT64>(g, p, false, st) : launch<NT128>(g, p, false, st);
   else {
@@ -465,12 +452,4 @@ extern "C" int sdumc_gemm_bf16_run(const sdumc_gemm_bf16* gp, void* stream) {
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_bf16_kernel() {}
-extern "C" int sdumc_preload_gemm_bf16_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_bf16_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_bf16)      // (common.h)

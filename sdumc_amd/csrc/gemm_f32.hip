@@ -32,28 +32,20 @@ namespace {
 // ---- optional per-launch timing with HIP events on the launch stream (bench.py roofline leg) -----
 struct ProfRec {
   hipEvent_t a, b;
-  int variant;  // layout * 2 + (tile == 64x64)
+  int variant;  // an sdumc_prof_variant; -1: dropped (its events are destroyed)
   double flops;
 };
 bool g_prof_on = false;
 std::vector<ProfRec> g_prof;
 std::mutex g_prof_mu;
-constexpr int kNumVariants = 29;
-const char* const kVariantName[kNumVariants] = {"gemm_nt_128x128", "gemm_nt_64x64",  "gemm_nn_128x128",
-                                                "gemm_nn_64x64",   "gemm_tn_128x128", "gemm_tn_64x64",
-                                                "gemm_small_nt",   "gemm_small_nn",   "gemm_small_tn",
-                                                "gemm_bf16_nt_128x128", "gemm_bf16_nt_64x64",
-                                                "gemm_bf16_nn_128x128", "gemm_bf16_nn_64x64",
-                                                "gemm_bf16_tn_128x128", "gemm_bf16_tn_64x64",
-                                                "gemm_wide_nt", "gemm_wide_tn",
-                                                "gemm_bf16s_nt", "gemm_bf16s_tn",    // gemm_bf16.hip (bf16 storage)
-                                                "gemm_group_tn", "gemm_group_tn_bf16",    // gemm_group.hip (the persistent kernel alone, without its reduce)
-                                                "gemm_rows256", "gemm_rows256_bf16",      // gemm_rows.hip
-                                                // fp32 operands, products on the bf16 matrix pipe from exactly split operands (sdumc_set_split_)
-                                                "gemm_wide_nt_bf16x3", "gemm_group_tn_bf16x3", "gemm_rows256_bf16x3",
-                                                "gemm_p3_nt_bf16x3", "gemm_p3_nt_masked_bf16x3",
-                                                "gemm_b1_nt_bf16"};     // gemm_p3.hip: operands pre-split into bf16 planes (P3 tensors); the two
-                                                // instantiations rocprof lists too: plain (frame projections), keep-bits on A (key projections)
+constexpr int kNumVariants = SDUMC_PV_COUNT;
+#define SDUMC_PV_NAME(name) #name,
+const char* const kVariantName[kNumVariants] = {SDUMC_PROF_VARIANTS(SDUMC_PV_NAME)};      // (common.h: the one list of variants)
+#undef SDUMC_PV_NAME
+// sdumc_gemm_f32 computes its variant from (bf16, layout, tile): each family's six entries lie in layout order, 128x128 before 64x64
+static_assert(kNumVariants == 29 && SDUMC_PV_gemm_tn_64x64 == SDUMC_PV_gemm_nt_128x128 + 2 * SDUMC_TN + 1 &&
+                  SDUMC_PV_gemm_small_tn == SDUMC_PV_gemm_small_nt + SDUMC_TN && SDUMC_PV_gemm_bf16_tn_64x64 == SDUMC_PV_gemm_bf16_nt_128x128 + 2 * SDUMC_TN + 1,
+              "profile variants of the generic kernels");
 
 constexpr int BK = 32;
 constexpr int LDK = BK + 4;
@@ -857,11 +849,11 @@ int launch(const sdumc_gemm& g, int nsplit, int kchunk, hipStream_t st) {
 
 }  // namespace
 
-// per-launch timing hooks for the other GEMM files (gemm_bf16.hip): begin returns a token (or -1 when profiling is off)
+// per-launch timing hooks of every GEMM file (common.h has the contract)
 extern "C" int sdumc_prof_begin_(int variant, double flops, void* stream) {
   if (!g_prof_on) return -1;
   ProfRec r;
-  if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) return -1;
+  if (hipEventCreate(&r.a) != hipSuccess || hipEventCreate(&r.b) != hipSuccess) return -2;
   r.variant = variant;
   r.flops = flops;
   (void)hipEventRecord(r.a, as_stream(stream));
@@ -873,6 +865,14 @@ extern "C" void sdumc_prof_end_(int token, void* stream) {
   if (token < 0) return;
   std::lock_guard<std::mutex> lock(g_prof_mu);
   if (token < (int)g_prof.size()) (void)hipEventRecord(g_prof[token].b, as_stream(stream));
+}
+extern "C" void sdumc_prof_drop_(int token) {
+  if (token < 0) return;
+  std::lock_guard<std::mutex> lock(g_prof_mu);
+  if (token >= (int)g_prof.size() || g_prof[token].variant < 0) return;
+  (void)hipEventDestroy(g_prof[token].a);
+  (void)hipEventDestroy(g_prof[token].b);
+  g_prof[token].variant = -1;      // (the slot stays: younger tokens are indices too)
 }
 
 extern "C" int sdumc_gemm_wide_(const sdumc_gemm* gp, int cfg, int nsplit, int kchunk, void* stream);   // gemm_wide.hip
@@ -905,7 +905,7 @@ extern "C" int sdumc_gemm_small_tn_multi_(const sdumc_gemm* gs, int n, void* str
     m.blk_end[i] = blocks;
     flops += 2.0 * g.M * (double)g.N * g.K;
   }
-  const int tok = sdumc_prof_begin_(8, flops, stream);      // (gemm_small_tn)
+  const int tok = sdumc_prof_begin_(SDUMC_PV_gemm_small_tn, flops, stream);
   hipLaunchKernelGGL(gemm_small_tn_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), m);
   SDUMC_CHECK_LAUNCH();
   sdumc_prof_end_(tok, stream);
@@ -943,22 +943,14 @@ extern "C" int sdumc_gemm_f32(const sdumc_gemm* gp, void* stream) {
   hipStream_t st = as_stream(stream);
   if (pl.tile >= 11) {
     if (pl.nsplit > 1 && (!g.workspace || g.workspace_bytes < plan_ws_bytes(g, pl.nsplit))) return SDUMC_ENOMEM;
-    ProfRec wrec;
-    const bool wprof = g_prof_on;
-    if (wprof) {
-      if (hipEventCreate(&wrec.a) != hipSuccess || hipEventCreate(&wrec.b) != hipSuccess) return SDUMC_ELAUNCH;
-      wrec.variant = g.layout == SDUMC_TN ? 16 : (sdumc_split_on_(SDUMC_SPLIT_WIDE) ? 23 : 15);
-      wrec.flops = 2.0 * g.M * (double)g.N * g.K * g.groups;
-      (void)hipEventRecord(wrec.a, st);
-    }
+    const int wvar = g.layout == SDUMC_TN ? SDUMC_PV_gemm_wide_tn : (sdumc_split_on_(SDUMC_SPLIT_WIDE) ? SDUMC_PV_gemm_wide_nt_bf16x3 : SDUMC_PV_gemm_wide_nt);
+    const int wtok = sdumc_prof_begin_(wvar, 2.0 * g.M * (double)g.N * g.K * g.groups, stream);
+    if (wtok == -2) return SDUMC_ELAUNCH;
     const int wrc = sdumc_gemm_wide_(&g, pl.tile - 10, pl.nsplit, pl.kchunk, stream);
+    if (wrc != SDUMC_OK) sdumc_prof_drop_(wtok);      // an error, or not a problem the wide kernels take: no record
     if (wrc < 0) return wrc;
     if (wrc == SDUMC_OK) {
-      if (wprof) {
-        (void)hipEventRecord(wrec.b, st);
-        std::lock_guard<std::mutex> lock(g_prof_mu);
-        g_prof.push_back(wrec);
-      }
+      sdumc_prof_end_(wtok, stream);      // (the main kernel alone, without its split-K reduce)
       if (pl.nsplit > 1) {
         const size_t mn = (size_t)g.M * g.N + (size_t)g.M;
         dim3 grid((unsigned)((mn + 255) / 256), g.groups);
@@ -967,7 +959,6 @@ extern "C" int sdumc_gemm_f32(const sdumc_gemm* gp, void* stream) {
       }
       return SDUMC_OK;
     }
-    if (wprof) { (void)hipEventDestroy(wrec.a); (void)hipEventDestroy(wrec.b); }
     sdumc_gemm g2 = g;           // not a problem the wide kernels take: the generic kernels
     g2.tile = 2;
     g2.splitk = 0;
@@ -976,17 +967,14 @@ extern "C" int sdumc_gemm_f32(const sdumc_gemm* gp, void* stream) {
   const int nsplit = pl.nsplit, kchunk = pl.kchunk, tile = pl.tile;
   const int small_nw = pl.waves;
   if (nsplit > 1 && (!g.workspace || g.workspace_bytes < plan_ws_bytes(g, nsplit))) return SDUMC_ENOMEM;
-  ProfRec rec;
-  const bool prof = g_prof_on;
-  if (prof) {
-    if (hipEventCreate(&rec.a) != hipSuccess || hipEventCreate(&rec.b) != hipSuccess) return SDUMC_ELAUNCH;
-    rec.variant = g.bf16 ? 9 + g.layout * 2 + (tile == 1 ? 0 : 1) : tile == 3 ? 6 + g.layout : g.layout * 2 + (tile == 1 ? 0 : 1);
-    rec.flops = 2.0 * g.M * (double)g.N * g.K * g.groups * (g.batch > 1 ? g.batch : 1);
-    (void)hipEventRecord(rec.a, st);
-  }
+  const int var = g.bf16 ? SDUMC_PV_gemm_bf16_nt_128x128 + g.layout * 2 + (tile == 1 ? 0 : 1)
+                  : tile == 3 ? SDUMC_PV_gemm_small_nt + g.layout : SDUMC_PV_gemm_nt_128x128 + g.layout * 2 + (tile == 1 ? 0 : 1);
+  const int tok = sdumc_prof_begin_(var, 2.0 * g.M * (double)g.N * g.K * g.groups * (g.batch > 1 ? g.batch : 1), stream);
+  if (tok == -2) return SDUMC_ELAUNCH;
   int rc = SDUMC_OK;
-  if (tile == 3) {
-    if (g.tile == 3 && (g.a_drop.enabled || g.b_drop.enabled || g.a_row_mod || g.b_row_mod)) return SDUMC_EINVAL;
+  if (tile == 3 && g.tile == 3 && (g.a_drop.enabled || g.b_drop.enabled || g.a_row_mod || g.b_row_mod)) {
+    rc = SDUMC_EINVAL;
+  } else if (tile == 3) {
     dim3 grid((g.N + 31) / 32, (g.M + 31) / 32, g.groups);
     if (small_nw == 8) {
       switch (g.layout) {
@@ -1005,13 +993,12 @@ extern "C" int sdumc_gemm_f32(const sdumc_gemm* gp, void* stream) {
     rc = tile == 1 ? launch<128, 128>(g, nsplit, kchunk, st)
          : tile == 4 ? launch<128, 64>(g, nsplit, kchunk, st) : launch<64, 64>(g, nsplit, kchunk, st);
   }
-  if (rc != SDUMC_OK) return rc;
-  SDUMC_CHECK_LAUNCH();
-  if (prof) {
-    (void)hipEventRecord(rec.b, st);
-    std::lock_guard<std::mutex> lock(g_prof_mu);
-    g_prof.push_back(rec);
+  if (rc != SDUMC_OK) {
+    sdumc_prof_drop_(tok);
+    return rc;
   }
+  sdumc_prof_end_(tok, stream);      // (the main kernel alone, without its split-K reduce)
+  SDUMC_CHECK_LAUNCH();
   if (nsplit > 1) {
     const size_t mn = (size_t)g.M * g.N + (size_t)g.M;   // + M tail threads for the fused column sums
     dim3 grid((unsigned)((mn + 255) / 256), g.groups);
@@ -1025,6 +1012,7 @@ extern "C" int sdumc_gemm_f32(const sdumc_gemm* gp, void* stream) {
 extern "C" int sdumc_profile_enable(int on) {
   std::lock_guard<std::mutex> lock(g_prof_mu);
   for (ProfRec& r : g_prof) {
+    if (r.variant < 0) continue;
     (void)hipEventDestroy(r.a);
     (void)hipEventDestroy(r.b);
   }
@@ -1043,6 +1031,7 @@ extern "C" int sdumc_profile_report(sdumc_prof_entry* out, int max_entries) {
     out[v].total_flops = 0.0;
   }
   for (ProfRec& r : g_prof) {
+    if (r.variant < 0) continue;
     if (hipEventSynchronize(r.b) != hipSuccess) return SDUMC_ELAUNCH;
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) return SDUMC_ELAUNCH;
@@ -1053,12 +1042,4 @@ extern "C" int sdumc_profile_report(sdumc_prof_entry* out, int max_entries) {
   return kNumVariants;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_f32_kernel() {}
-extern "C" int sdumc_preload_gemm_f32_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_f32_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_f32)      // (common.h)

@@ -27,20 +27,16 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
 
 #include "common.h"
 
 namespace sdumc_gg {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(4))) int32_t const_i32_t;      // (a load through it with a wave-uniform index is a scalar load)
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) i32x4 const_i32x4_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
 
 constexpr int BM = 256, BN = 128, BK = 16;
 constexpr int NW = 8, NTHR = 64 * NW, WGN = 2;       // 4 x 2 waves, each 64 x 64
@@ -1068,36 +1064,12 @@ __global__ __launch_bounds__(NTHR) void gg_reduce_kernel(const Launch L, const i
   }
 }
 
-int cu_count() {
-  static std::mutex mu;
-  static int per_device[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!per_device[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    per_device[dev] = n;
-  }
-  return per_device[dev];
-}
-
 bool set_lds_attr() {   // the dynamic-LDS limit is a per-device function attribute
-  static std::mutex mu;
-  static bool done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!done[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_tn_kernel<5, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * STAGE_BYTES) != hipSuccess)
-      return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_tn_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, hf::HNST * hf::HSTAGE) != hipSuccess)
-      return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gg_tn_split2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, s2::LDS2) != hipSuccess)
-      return false;
-    done[dev] = true;
-  }
-  return true;
+  static sdumc_dev_once attr_set;
+  return sdumc_once_per_device(attr_set, [] {
+           return sdumc_set_dyn_lds(&gg_tn_kernel<5, 2>, 5 * STAGE_BYTES) && sdumc_set_dyn_lds(&gg_tn_bf16_kernel, hf::HNST * hf::HSTAGE) &&
+                  sdumc_set_dyn_lds(&gg_tn_split2_kernel, s2::LDS2);
+         }) == SDUMC_OK;
 }
 
 bool valid(const sdumc_gg_problem& p) {
@@ -1188,17 +1160,14 @@ bool valid_bf16(const sdumc_gg_problem& p) {
 extern "C" size_t sdumc_gg_slab_bytes_(int tiles) {
   (void)set_lds_attr();
   // (`tiles` counts 256 x 128 tiles; the 256 x 256 form has at most as many, of twice the size)
-  return (size_t)(cu_count() + tiles) * s2::SLOT2_FLOATS * sizeof(float);
+  return (size_t)(sdumc_cu_count() + tiles) * s2::SLOT2_FLOATS * sizeof(float);
 }
-
-extern "C" int sdumc_prof_begin_(int variant, double flops, void* stream);     // gemm_f32.hip: bench.py's per-launch HIP events
-extern "C" void sdumc_prof_end_(int token, void* stream);
 
 namespace {
 bool split_products() { return sdumc_split_on_(SDUMC_SPLIT_GROUP) != 0; }
 size_t gg_workspace_bytes(const sdumc_gg_problem* probs, int32_t n, bool hf) {
   if (!probs || n <= 0) return 0;
-  const int nwg = cu_count();
+  const int nwg = sdumc_cu_count();
   size_t need = 0;
   for (int first = 0; first < n; first += MAXP) {
     const int cnt = std::min(MAXP, n - first);
@@ -1220,7 +1189,7 @@ int gg_run(const sdumc_gg_problem* probs, int32_t n, void* workspace, size_t wor
     if (!(hf ? valid_bf16(probs[i]) : valid(probs[i]))) return SDUMC_EINVAL;
   if (workspace_bytes < gg_workspace_bytes(probs, n, hf)) return SDUMC_ENOMEM;
   if (!set_lds_attr()) return SDUMC_ELAUNCH;
-  const int nwg = cu_count();      // one workgroup per CU (two on a 3-stage ring spilled registers and ran at 2/3 of the rate)
+  const int nwg = sdumc_cu_count();      // one workgroup per CU (two on a 3-stage ring spilled registers and ran at 2/3 of the rate)
   hipStream_t st = as_stream(stream);
   for (int first = 0; first < n; first += MAXP) {
     const int cnt = std::min(MAXP, n - first);
@@ -1235,7 +1204,7 @@ int gg_run(const sdumc_gg_problem* probs, int32_t n, void* workspace, size_t wor
     L.slab = static_cast<float*>(workspace);
     double flops = 0.0;
     for (int i = 0; i < cnt; ++i) flops += 2.0 * probs[first + i].M * (double)probs[first + i].N * ((double)probs[first + i].K[0] + probs[first + i].K[1]);
-    const int tok = sdumc_prof_begin_(hf ? 20 : (split_products() ? 24 : 19), flops, stream);
+    const int tok = sdumc_prof_begin_(hf ? SDUMC_PV_gemm_group_tn_bf16 : (split_products() ? SDUMC_PV_gemm_group_tn_bf16x3 : SDUMC_PV_gemm_group_tn), flops, stream);
     if (hf) hipLaunchKernelGGL(gg_tn_bf16_kernel, dim3(L.nwg), dim3(NTHR), hf::HNST * hf::HSTAGE, st, L);
     else if (wide) {
       // (round 6: a form that converts k-tile t + 1 while it multiplies k-tile t -- double-buffered planes, 8-k raw halves, the two
@@ -1290,12 +1259,4 @@ extern "C" int sdumc_split_scope_(int mask) {      // returns the previous scope
   return prev;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_group_kernel() {}
-extern "C" int sdumc_preload_gemm_group_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_group_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_group)      // (common.h)

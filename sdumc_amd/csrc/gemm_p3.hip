@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void p3_splitk_reduce_kernel(const sdumc_gemm_
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     float x = v[c] + (g.bias ? g.bias[col + c] : 0.f);
-    if (g.act == SDUMC_ACT_TANH) x = sdumc_p3::fast_tanh(x);
+    if (g.act == SDUMC_ACT_TANH) x = fast_tanh(x);
     else if (g.act == SDUMC_ACT_RELU) x = fmaxf(x, 0.f);
     v[c] = x;
   }
@@ -345,9 +345,6 @@ int launch(const sdumc_gemm_p3& g, const Plan& p, hipStream_t st) {
 
 }  // namespace sdumc_p3
 
-extern "C" int sdumc_prof_begin_(int variant, double flops, void* stream);     // gemm_f32.hip: bench.py's per-launch HIP events
-extern "C" void sdumc_prof_end_(int token, void* stream);
-
 extern "C" size_t sdumc_gemm_p3_workspace_bytes(const sdumc_gemm_p3* g) {
   if (!g || g->M <= 0 || g->N <= 0 || g->K <= 0 || (g->K % (4 * sdumc_p3::BK))) return 0;
   const sdumc_p3::Plan p = sdumc_p3::plan(*g, (size_t)-1);
@@ -378,7 +375,7 @@ extern "C" int sdumc_gemm_p3_nt(const sdumc_gemm_p3* gp, void* stream) {
   const Plan p = plan(g, g.workspace ? g.workspace_bytes : 0);
   if (p.nsplit > 1 && (!g.workspace || (reinterpret_cast<uintptr_t>(g.workspace) & 15))) return SDUMC_ENOMEM;
   hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(mask ? 27 : 26, 2.0 * g.M * (double)g.N * g.K, stream);
+  const int tok = sdumc_prof_begin_(mask ? SDUMC_PV_gemm_p3_nt_masked_bf16x3 : SDUMC_PV_gemm_p3_nt_bf16x3, 2.0 * g.M * (double)g.N * g.K, stream);
   int rc;
   // tile_m = 0: 64-row tiles on 256-thread workgroups, two per CU -- slower alone than the tall 512-thread forms on a shape that fills
   // the chip in one round (audio frame projection: 76 against 62 us at 96 rows), faster inside the step, where three lanes' kernels
@@ -451,12 +448,4 @@ extern "C" int sdumc_p3_join(const void* src, int64_t ld_bytes, float* dst, int6
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_p3_kernel() {}
-extern "C" int sdumc_preload_gemm_p3_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_p3_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_p3)      // (common.h)

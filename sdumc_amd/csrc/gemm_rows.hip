@@ -34,18 +34,11 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
 
 #include "common.h"
 
 namespace sdumc_gr {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-// (vmcnt is a 6-bit counter: a count beyond 63 is waited for as 63 -- stricter, so still correct)
-constexpr int waitcnt_vm(int n) { return ((n > 63 ? 63 : n) & 0xF) | (((n > 63 ? 63 : n) >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }   // = gemm_wide.hip
 
 constexpr int BM = 64, DK = 256, DN = 256, BK = 32;
 constexpr int NS = DK / BK;                      // stages per tile = ring slots
@@ -753,11 +746,6 @@ constexpr int younger(int s) {
   return n;
 }
 static_assert(younger<false, 1>(0) == 4 + HP_OPS && younger<false, 2>(2) == 4 + 2 * HP_OPS && younger<true, 2>(2) == 4 + 2 * HP_OPS + 32, "bf16 fold");
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 h = (__bf16)f;      // v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN
-  return *reinterpret_cast<unsigned short*>(&h);
-}
 }  // namespace hf
 
 // (stage 0..7 of a pair: plain 4 x 8; accumulating 36 36 68 36 36 36 68 36 -- 68 = both C prefetches were issued behind the A piece)
@@ -1045,47 +1033,18 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
 #endif
 }
 
-int cu_count() {
-  static std::mutex mu;
-  static int per_device[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!per_device[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    per_device[dev] = n;
-  }
-  return per_device[dev];
-}
-
 bool set_lds_attr() {   // the dynamic-LDS limit is a per-device function attribute
-  static std::mutex mu;
-  static bool done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!done[dev]) {
-    const void* ks[3] = {reinterpret_cast<const void*>(&gr_kernel<false, false>), reinterpret_cast<const void*>(&gr_kernel<true, false>),
-                         reinterpret_cast<const void*>(&gr_kernel<false, true>)};
-    for (const void* k : ks)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) return false;
-    const void* ks2[4] = {reinterpret_cast<const void*>(&gr_split_kernel<false, false>), reinterpret_cast<const void*>(&gr_split_kernel<true, false>),
-                          reinterpret_cast<const void*>(&gr_split_kernel<false, true>), reinterpret_cast<const void*>(&gr_split_kernel<false, false, true>)};
-    for (const void* k : ks2)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, sp::LDS_BYTES2) != hipSuccess) return false;
-    const void* ks3[2] = {reinterpret_cast<const void*>(&gr_split_kernel<false, false, true, true>), reinterpret_cast<const void*>(&gr_split_kernel<false, true, true, true>)};
-    for (const void* k : ks3)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, sp::LDS_FOLD) != hipSuccess) return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gr_bf16_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, RING) != hipSuccess) return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gr_bf16_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, RING) != hipSuccess) return false;
-    const void* kf[4] = {reinterpret_cast<const void*>(&gr_bf16_kernel<false, 1>), reinterpret_cast<const void*>(&gr_bf16_kernel<true, 1>),
-                         reinterpret_cast<const void*>(&gr_bf16_kernel<false, 2>), reinterpret_cast<const void*>(&gr_bf16_kernel<true, 2>)};
-    for (const void* k : kf)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, RING + 2 * hf::HP_BUF) != hipSuccess) return false;
-    done[dev] = true;
-  }
-  return true;
+  static sdumc_dev_once attr_set;
+  return sdumc_once_per_device(attr_set, [] {
+           return sdumc_set_dyn_lds(&gr_kernel<false, false>, LDS_BYTES) && sdumc_set_dyn_lds(&gr_kernel<true, false>, LDS_BYTES) &&
+                  sdumc_set_dyn_lds(&gr_kernel<false, true>, LDS_BYTES) &&
+                  sdumc_set_dyn_lds(&gr_split_kernel<false, false>, sp::LDS_BYTES2) && sdumc_set_dyn_lds(&gr_split_kernel<true, false>, sp::LDS_BYTES2) &&
+                  sdumc_set_dyn_lds(&gr_split_kernel<false, true>, sp::LDS_BYTES2) && sdumc_set_dyn_lds(&gr_split_kernel<false, false, true>, sp::LDS_BYTES2) &&
+                  sdumc_set_dyn_lds(&gr_split_kernel<false, false, true, true>, sp::LDS_FOLD) && sdumc_set_dyn_lds(&gr_split_kernel<false, true, true, true>, sp::LDS_FOLD) &&
+                  sdumc_set_dyn_lds(&gr_bf16_kernel<false>, RING) && sdumc_set_dyn_lds(&gr_bf16_kernel<true>, RING) &&
+                  sdumc_set_dyn_lds(&gr_bf16_kernel<false, 1>, RING + 2 * hf::HP_BUF) && sdumc_set_dyn_lds(&gr_bf16_kernel<true, 1>, RING + 2 * hf::HP_BUF) &&
+                  sdumc_set_dyn_lds(&gr_bf16_kernel<false, 2>, RING + 2 * hf::HP_BUF) && sdumc_set_dyn_lds(&gr_bf16_kernel<true, 2>, RING + 2 * hf::HP_BUF);
+         }) == SDUMC_OK;
 }
 
 bool valid(const sdumc_rows_problem& p) {
@@ -1102,9 +1061,6 @@ bool valid(const sdumc_rows_problem& p) {
 
 }  // namespace sdumc_gr
 using namespace sdumc_gr;
-
-extern "C" int sdumc_prof_begin_(int variant, double flops, void* stream);     // gemm_f32.hip: bench.py's per-launch HIP events
-extern "C" void sdumc_prof_end_(int token, void* stream);
 
 extern "C" int sdumc_gemm_rows_prepare_(void) { return set_lds_attr() ? SDUMC_OK : SDUMC_ELAUNCH; }
 
@@ -1143,12 +1099,12 @@ extern "C" int sdumc_gemm_rows256_capped_(const sdumc_rows_problem* probs, int32
   }
   L.unit0[n] = units;
   L.n = n;
-  L.nwg = std::min(cu_count(), units);
+  L.nwg = std::min(sdumc_cu_count(), units);
   if (max_wg > 0) L.nwg = std::min(L.nwg, (int)max_wg);
   if ((long long)units * (L.nwg + 1) >= (1LL << 31)) return SDUMC_EINVAL;
   if (!set_lds_attr()) return SDUMC_ELAUNCH;
   hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(sdumc_split_on_(SDUMC_SPLIT_ROWS) ? 25 : 21, flops, stream);
+  const int tok = sdumc_prof_begin_(sdumc_split_on_(SDUMC_SPLIT_ROWS) ? SDUMC_PV_gemm_rows256_bf16x3 : SDUMC_PV_gemm_rows256, flops, stream);
   if (sdumc_split_on_(SDUMC_SPLIT_ROWS)) {
     if (fold && accum) hipLaunchKernelGGL((gr_split_kernel<false, true, true, true>), dim3(L.nwg), dim3(NTHR), sp::LDS_FOLD, st, L);
     else if (fold) hipLaunchKernelGGL((gr_split_kernel<false, false, true, true>), dim3(L.nwg), dim3(NTHR), sp::LDS_FOLD, st, L);
@@ -1200,12 +1156,12 @@ extern "C" int sdumc_gemm_rows256_bf16_capped_(const sdumc_rows_problem* probs, 
   }
   L.unit0[n] = units;
   L.n = n;
-  L.nwg = std::min(cu_count(), units);      // (a workgroup works through pairs of tiles; with fewer tiles than CUs a pair is one tile and nothing)
+  L.nwg = std::min(sdumc_cu_count(), units);      // (a workgroup works through pairs of tiles; with fewer tiles than CUs a pair is one tile and nothing)
   if (max_wg > 0) L.nwg = std::min(L.nwg, (int)max_wg);
   if ((long long)units * (L.nwg + 1) >= (1LL << 31)) return SDUMC_EINVAL;
   if (!set_lds_attr()) return SDUMC_ELAUNCH;
   hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(22, flops, stream);
+  const int tok = sdumc_prof_begin_(SDUMC_PV_gemm_rows256_bf16, flops, stream);
   const size_t lds_fold = RING + 2 * hf::HP_BUF;
   if (fold == 2 && accum) hipLaunchKernelGGL((gr_bf16_kernel<true, 2>), dim3(L.nwg), dim3(NTHR), lds_fold, st, L);
   else if (fold == 2) hipLaunchKernelGGL((gr_bf16_kernel<false, 2>), dim3(L.nwg), dim3(NTHR), lds_fold, st, L);
@@ -1218,12 +1174,4 @@ extern "C" int sdumc_gemm_rows256_bf16_capped_(const sdumc_rows_problem* probs, 
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_rows_kernel() {}
-extern "C" int sdumc_preload_gemm_rows_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_rows_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_rows)      // (common.h)

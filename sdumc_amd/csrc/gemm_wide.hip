@@ -28,15 +28,6 @@
 // (a named namespace: hipFuncSetAttribute takes the kernels' addresses, which needs external linkage on the host side)
 namespace sdumc_wide {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
-
-__device__ __forceinline__ float fast_tanh(float x) {
-  // 1 - 2 / (1 + e^{2x}): v_exp_f32 + v_rcp_f32, absolute error ~1e-7 (saturates correctly at +-1, NaN propagates)
-  return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x));
-}
-
 template <int BM_, int BN_, int WGM_, int WGN_, int BK_, int NST_, bool A_KC_, bool B_KC_, int OCC_>
 struct WideCfg {
   static constexpr int OCC = OCC_;          // waves per SIMD the register allocation must leave room for
@@ -547,12 +538,4 @@ extern "C" int sdumc_gemm_wide_(const sdumc_gemm* gp, int cfg, int nsplit, int k
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_gemm_wide_kernel() {}
-extern "C" int sdumc_preload_gemm_wide_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_gemm_wide_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(gemm_wide)      // (common.h)

@@ -1016,8 +1016,7 @@ static int rnc_impl(const float* feats, const float* labels, int label_mod, int3
     const size_t lds = ((((size_t)dim + 3) & ~(size_t)3) + 8 * (size_t)n + 8) * sizeof(float);
     if (lds > 160 * 1024) return SDUMC_EINVAL;
     if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(rnc_row_sorted_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
+        !sdumc_set_dyn_lds(rnc_row_sorted_kernel, lds))      // (the size follows n and dim: set per call, not once per device)
       return SDUMC_ELAUNCH;
     hipLaunchKernelGGL(rnc_row_sorted_kernel, dim3(n), dim3(256), lds, st, feats, labels, label_mod, n, dim, inv_t, w, perm,
                        rank, want_grad);
@@ -1399,12 +1398,4 @@ extern "C" int sdumc_supcon_fwd_bwd(const float* feats, const float* labels, con
   return SDUMC_OK;
 }
 
-// One empty kernel per source file = per gfx950 code object: sdumc_preload_() asks for its attributes, which makes the HIP runtime load
-// this file's code object NOW (outside any timed or latency-sensitive region) instead of at the first launch of one of its kernels --
-// with deferred loading that first launch stalls the host for tens of milliseconds (seen as a 36-59 ms gap in the middle of an epoch,
-// at the first batch whose shape took a fallback path: profiles/README.md, round 6).
-__global__ void sdumc_preload_loss_kernel() {}
-extern "C" int sdumc_preload_loss_(void) {
-  hipFuncAttributes a;
-  return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&sdumc_preload_loss_kernel)) == hipSuccess ? SDUMC_OK : SDUMC_ELAUNCH;
-}
+SDUMC_PRELOAD_HOOK(loss)      // (common.h)

@@ -7,34 +7,23 @@
 
 namespace sdumc_p3 {
 
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
 typedef const __attribute__((address_space(4))) int32_t const_i32_t;      // loads through it with a wave-uniform index are scalar loads
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2s __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int waitcnt_vm(int n) { return (n & 0xF) | ((n >> 4) << 14) | (0x7 << 4) | (0xF << 8); }
-
-__device__ __forceinline__ float fast_tanh(float x) { return 1.f - 2.f * __frcp_rn(1.f + __expf(2.f * x)); }
-
-__device__ __forceinline__ uint32_t pk(float x, float y) {       // v_cvt_pk_bf16_f32 (round to nearest even), low half = x
-  const f32x2s v = {x, y};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
 // eight fp32 values -> their three bf16 planes (4 dwords each)
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&pl)[3]) {
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
     const float x = v[2 * d], y = v[2 * d + 1];
-    const uint32_t p0 = pk(x, y);
+    const uint32_t p0 = pack_bf16x2(x, y);
     const float x1 = x - __uint_as_float(p0 << 16), y1 = y - __uint_as_float(p0 & 0xFFFF0000u);       // exact
-    const uint32_t p1 = pk(x1, y1);
+    const uint32_t p1 = pack_bf16x2(x1, y1);
     const float x2 = x1 - __uint_as_float(p1 << 16), y2 = y1 - __uint_as_float(p1 & 0xFFFF0000u);     // exact
     pl[0][d] = p0;
     pl[1][d] = p1;
-    pl[2][d] = pk(x2, y2);
+    pl[2][d] = pack_bf16x2(x2, y2);
   }
 }
 

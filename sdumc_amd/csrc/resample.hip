@@ -110,3 +110,5 @@ extern "C" int sdumc_pool_frames(const sdumc_pool_desc* p, int32_t max_workgroup
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
 }
+
+SDUMC_PRELOAD_HOOK(resample)      // (common.h)

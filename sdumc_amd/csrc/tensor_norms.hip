@@ -41,11 +41,9 @@ __host__ __device__ inline int64_t chunk_floats(int64_t count, int64_t nch) { re
 
 template <bool Y>
 __device__ __forceinline__ void take(float x, float y, double& acc, double& dacc, uint32_t& bad) {
-  const double xd = (double)x;
-  acc = fma(xd, xd, acc);
-  bad += (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;      // NaN or +-Inf
+  sumsq_count_nonfinite(x, acc, bad);
   if (Y) {
-    const double d = xd - (double)y;      // (exact in fp64)
+    const double d = (double)x - (double)y;      // (exact in fp64)
     dacc = fma(d, d, dacc);
   }
 }
@@ -234,3 +232,5 @@ extern "C" int sdumc_tensor_norms(const sdumc_norm_seg* segs, int32_t n, float* 
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
 }
+
+SDUMC_PRELOAD_HOOK(tensor_norms)      // (common.h)
