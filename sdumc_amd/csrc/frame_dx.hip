@@ -110,16 +110,15 @@ __global__ __launch_bounds__(NTHR, 1) void frame_dx_kernel(const Args a) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int p = 0; p < 3; ++p) pa[i][p] = *reinterpret_cast<const u32x4*>(lds + kt * KT_BYTES + i * 32 * ROWB + lane_off + p * 16);
-        // smallest terms first, as in p3_loop.h: (a2 b0), (a0 b2), (a1 b1), (a1 b0), (a0 b1) into `lo`, (a0 b0) into `acc`
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};
+        // smallest terms first, as in p3_loop.h (prims.h: BF16X3_TA / _TB): the first five into `lo`, (a0 b0) into `acc`
 #pragma unroll
         for (int t = 0; t < 5; ++t)
 #pragma unroll
           for (int i = 0; i < TM; ++i)
-            lo[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][TA[t]]), op(pb[j][TB[t]]), lo[i], 0, 0, 0);
+            lo[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][BF16X3_TA[t]]), op(pb[j][BF16X3_TB[t]]), lo[i], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][TA[5]]), op(pb[j][TB[5]]), acc[i], 0, 0, 0);
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][BF16X3_TA[5]]), op(pb[j][BF16X3_TB[5]]), acc[i], 0, 0, 0);
       }
     }
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5)

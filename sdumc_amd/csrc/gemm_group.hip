@@ -330,6 +330,7 @@ __device__ __forceinline__ void gg_tn_body(const Launch& L, char* lds) {
       // commits on every one of its K steps.  Six 32-cycle MFMAs replace eight 64-cycle ones per 32 x 32 x 16 block (2.67x the
       // matrix rate); the split costs 5.5 VALU operations per fragment value (and, sub, and, sub + three half v_perm_b32 that
       // pack two values' top halves into one operand dword), which run beside the MFMAs of the previous k-tile.
+      // (prims.h holds the one definition of each: split_bf16x3, the term order BF16X3_TA / _TB, mfma_bf16x3)
       // A lane's eight k of one operand are k = 4 lh + s and 8 + 4 lh + s (s < 4) -- the two fp32 fragments of the k-tile side
       // by side; A and B use the same assignment, which is all a contraction needs.
       // (the in-fragment form of this kernel -- every wave splitting the fragments it multiplies, 136-147 TF -- was superseded by
@@ -461,23 +462,6 @@ __global__ __launch_bounds__(NTHR, 2) void gg_tn_split2_kernel(const Launch L) {
   const int x_end = range_begin(wg + 1, LL, L.nwg);
   constexpr int PER = 5;      // 2 A rows, 2 B rows, 1 keep-bits piece per wave and stage
 
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2s __attribute__((ext_vector_type(2)));
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  auto pk = [](float a, float b) -> uint32_t {       // v_cvt_pk_bf16_f32 (round to nearest even), low half = a
-    const f32x2s v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-  };
-  auto split2 = [&](float a, float b, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-    p0 = pk(a, b);
-    const float a1 = a - __uint_as_float(p0 << 16), b1 = b - __uint_as_float(p0 & 0xFFFF0000u);       // exact
-    p1 = pk(a1, b1);
-    const float a2 = a1 - __uint_as_float(p1 << 16), b2 = b1 - __uint_as_float(p1 & 0xFFFF0000u);     // exact
-    p2 = pk(a2, b2);
-  };
-  auto op = [](const u32x4& v) { return __builtin_bit_cast(bf16x8, v); };
-
   // conversion roles: row ar of A and column ar of B, k 8 ag .. + 7 of both
   const int ar = tid & (BM - 1), ag = tid >> 8;
   const uint32_t a_rd = (uint32_t)((8 * ag) * BM + ar) * 4u;                                  // + s * BM * 4
@@ -607,11 +591,11 @@ __global__ __launch_bounds__(NTHR, 2) void gg_tn_split2_kernel(const Launch L) {
         csum += ((av[0] + av[1]) + (av[2] + av[3])) + ((av[4] + av[5]) + (av[6] + av[7]));
         uint32_t q[3][4];
 #pragma unroll
-        for (int d = 0; d < 4; ++d) split2(av[2 * d], av[2 * d + 1], q[0][d], q[1][d], q[2][d]);
+        for (int d = 0; d < 4; ++d) split_bf16x3(av[2 * d], av[2 * d + 1], q[0][d], q[1][d], q[2][d]);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(planes + pl * PA_BYTES + a_wr) = u32x4{q[pl][0], q[pl][1], q[pl][2], q[pl][3]};
 #pragma unroll
-        for (int d = 0; d < 4; ++d) split2(bv[2 * d], bv[2 * d + 1], q[0][d], q[1][d], q[2][d]);
+        for (int d = 0; d < 4; ++d) split_bf16x3(bv[2 * d], bv[2 * d + 1], q[0][d], q[1][d], q[2][d]);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(planes + pl * PB_BYTES + b_wr) = u32x4{q[pl][0], q[pl][1], q[pl][2], q[pl][3]};
       };
@@ -630,16 +614,8 @@ __global__ __launch_bounds__(NTHR, 2) void gg_tn_split2_kernel(const Launch L) {
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) pa[(i + 1) & 1][pl] = *reinterpret_cast<const u32x4*>(planes + pl * PA_BYTES + a_op[i + 1]);
           }
-          const u32x4* A_ = pa[i & 1];
 #pragma unroll
-          for (int j = 0; j < TN2; ++j) {   // smallest terms first
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(A_[2]), op(pb[j][0]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(A_[0]), op(pb[j][2]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(A_[1]), op(pb[j][1]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(A_[1]), op(pb[j][0]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(A_[0]), op(pb[j][1]), acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(A_[0]), op(pb[j][0]), acc[i][j], 0, 0, 0);
-          }
+          for (int j = 0; j < TN2; ++j) mfma_bf16x3(acc[i][j], pa[i & 1], pb[j]);
           __builtin_amdgcn_sched_barrier(0);
         }
       };

@@ -60,23 +60,43 @@ struct Launch {
 };
 
 // ---- the vector-memory bookkeeping of one wave --------------------------------------------------------------------------
-// Issue point of stage t (steady state): [the two keep-bits pieces of the next tile, t == 2] the A piece of stage t + PF [32
-// loads of the C tile, t == 5].  The wait in stage s is for the A piece of stage s + 1, issued at stage s + 1 - PF.
-constexpr int T_BITS = 2, T_C = 5;
-template <bool MASK, bool ACC>
-constexpr int ops_at(int t) { return 1 + ((MASK && t == T_BITS) ? 2 : 0) + ((ACC && t == T_C) ? 32 : 0); }
-template <bool MASK, bool ACC>
-constexpr int younger(int s) {
-  const int t0 = ((s + 1 - PF) % NS + NS) % NS;
-  int n = (ACC && t0 == T_C) ? 32 : 0;                 // what followed the A piece at its own issue point
-  for (int t = 1; t < PF - 1; ++t) n += ops_at<MASK, ACC>((t0 + t) % NS);
+// The ledger of a kernel: every issue point t of the 8-point cycle issues one A piece (the stage `pf` ahead), and some carry
+// further PIECES -- `ops` vector-memory instructions before or after that A piece.  Each kernel states its pieces once; its stage
+// code asks carries() of the same entry whether to issue, and younger() counts from it: the two cannot disagree about where.
+// A load added to an issue point = one entry here plus the issuing code, `ops` being the constant that code loops over or asserts.
+struct Piece {
+  int ops;
+  unsigned points;         // bit t: carried at issue point t (0: the variant does not have the piece)
+  bool before_a = false;
+};
+struct Ledger {
+  int pf, ahead;           // the A piece of stage s + pf is issued at point s; the wait in stage s is for the A piece of stage s + ahead
+  Piece pc[4];
+};
+constexpr unsigned at(bool on, int t) { return on ? 1u << t : 0u; }
+constexpr bool carries(Piece p, int t) { return (p.points >> t) & 1u; }
+// the operations issued after the A piece that stage s waits for (issued at point s + ahead - pf): what followed it at its own
+// issue point, plus every operation of the issue points between
+constexpr int younger(const Ledger& g, int s) {
+  const int t0 = ((s + g.ahead - g.pf) % NS + NS) % NS, between = g.pf - g.ahead - 1;
+  int n = between;                                     // (their A pieces)
+  for (const Piece& p : g.pc) {
+    if (carries(p, t0) && !p.before_a) n += p.ops;
+    for (int t = 1; t <= between; ++t) n += carries(p, (t0 + t) % NS) ? p.ops : 0;
+  }
   return n;
 }
+constexpr int BITS_OPS = 2, CPRE_OPS = 32;      // the keep-bits of a tile: two pieces; a C tile into registers: one load per accumulator element
 
-// (the tables these formulas produce, stage 0..7: plain 4 x 8; masked 4 4 4 6 6 6 6 4; accumulating 36 36 36 4 4 4 36 36)
-static_assert(younger<false, false>(0) == 4 && younger<false, false>(5) == 4, "plain");
-static_assert(younger<true, false>(2) == 4 && younger<true, false>(3) == 6 && younger<true, false>(6) == 6 && younger<true, false>(7) == 4, "masked");
-static_assert(younger<false, true>(2) == 36 && younger<false, true>(3) == 4 && younger<false, true>(5) == 4 && younger<false, true>(6) == 36, "accumulating");
+// gr_kernel: the two keep-bits pieces of the next tile ahead of the A piece of point 2, the C tile behind that of point 5
+enum { G_BITS, G_C };
+template <bool MASK, bool ACC>
+constexpr Ledger plain = {PF, 1, {{BITS_OPS, at(MASK, 2), true}, {CPRE_OPS, at(ACC, 5)}}};
+
+// (the tables this produces, stage 0..7: plain 4 x 8; masked 4 4 4 6 6 6 6 4; accumulating 36 36 36 4 4 4 36 36)
+static_assert(younger(plain<false, false>, 0) == 4 && younger(plain<false, false>, 5) == 4, "plain");
+static_assert(younger(plain<true, false>, 2) == 4 && younger(plain<true, false>, 3) == 6 && younger(plain<true, false>, 6) == 6 && younger(plain<true, false>, 7) == 4, "masked");
+static_assert(younger(plain<false, true>, 2) == 36 && younger(plain<false, true>, 3) == 4 && younger(plain<false, true>, 5) == 4 && younger(plain<false, true>, 6) == 36, "accumulating");
 
 template <bool MASK, bool ACC>
 __global__ __launch_bounds__(NTHR, 2) void gr_kernel(const Launch L) {
@@ -143,6 +163,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_kernel(const Launch L) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void_t*)(lds + chunk * A_STAGE + wave * 1024), 16, off, chunk * (BK * 4), 0, 0);
     };
     auto issue_bits = [&](uint32_t off, int par) {
+      static_assert(BITS_OPS == 2, "the two instructions below");
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rbits, (lds_void_t*)(bits_lds + par * BITS_TILE + wave * 512), 4, off, 0, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rbits, (lds_void_t*)(bits_lds + par * BITS_TILE + wave * 512 + 256), 4, off, 256, 0, 0);
     };
@@ -212,18 +233,22 @@ __global__ __launch_bounds__(NTHR, 2) void gr_kernel(const Launch L) {
       float cpre[ACC ? 32 : 1];
       auto stage = [&](auto sc) {
         constexpr int s = decltype(sc)::value;
+        constexpr const Ledger& G = plain<MASK, ACC>;
         read_frag(s, 1, par, fb);
         __builtin_amdgcn_sched_barrier(0);
         mma(fa, 0, s);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(waitcnt_vm(younger<MASK, ACC>(s)));
+        __builtin_amdgcn_s_waitcnt(waitcnt_vm(younger(G, s)));
         __builtin_amdgcn_s_barrier();
+        // (the outer conditions keep what a variant lacks out of this generic lambda's captures: with `cpre` or `issue_bits` captured
+        //  and unused, the register allocation of the whole kernel came out differently)
         if constexpr (MASK) {
-          if constexpr (s == T_BITS) issue_bits(b_nxt, par ^ 1);
+          if constexpr (carries(G.pc[G_BITS], s)) issue_bits(b_nxt, par ^ 1);
         }
         issue_a(s + PF < NS ? o_cur : o_nxt, (s + PF) % NS);
         if constexpr (ACC) {
-          if constexpr (s == T_C) {
+          if constexpr (carries(G.pc[G_C], s)) {
+            static_assert(CPRE_OPS == 2 * 16, "one load per accumulator element");
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -291,7 +316,6 @@ __global__ __launch_bounds__(NTHR, 2) void gr_kernel(const Launch L) {
 // ------------------------------------------------------------------------------------------------------------------------
 namespace sp {
 constexpr int PF2 = 7;
-constexpr int T_BITS2 = 0, T_C2 = 1;
 constexpr int PL_STAGE = 3 * BM * BK * 2;            // three planes of one stage: 12 KB
 constexpr int C_TILE = BM * DN * 4;                  // `accumulate`: the C tile waits in LDS (64 KB; MASK and ACC exclude each other,
                                                      // so it starts where the keep-bits would lie) -- 32 registers a wave does not have
@@ -300,33 +324,25 @@ constexpr int C_OPS = BM / NW;                       // LDS-DMA instructions per
 // POOL (sdumc_rows_problem.pool_w / pool_g): the operands of the tile's extra k-tile -- its 64 rows of attention weights (<= 2 KB)
 // and the masked dout rows of the <= 2 samples it spans (2 x 8 x 1 KB) -- ride in by LDS-DMA at issue point 1 of the tile itself
 // (three instructions per wave) and are multiplied behind stage 7: the wait of stage 7 is for a piece issued after them.
-constexpr int T_P2 = 1, P_OPS = 3;
+constexpr int P_OPS = 3;
 constexpr int POOL_W = BM * 8 * 4, POOL_G = 2 * 8 * DN * 4;      // LDS bytes (where the keep-bits / the C tile lie in the other variants)
 // FOLD (sdumc_rows_problem.fold): `fold` row blocks of A add up, each under its own keep-bits, into ONE C tile -- the mask-sum of the
 // frame-level input dropouts (dx = sum over sites and streams of keep . dxd) folded into the launch that produces dxd.  The partial
 // tile waits in LDS where the C tile of `accumulate` lies (and is that tile when both are on); the keep-bits of the tile's rows (4 KB)
 // ride with the attention weights at issue point 1 (three instructions per wave again), the masked dout rows come straight into
 // eight registers at issue point 5 (no LDS left for them: ring 64 + planes 24 + tile 64 + weights 2 + bits 4 + a dummy row 1 = 159 KB).
-constexpr int T_G2 = 5, G_OPS = 7;      // (fold: at most 7 queries -- k = 7 of a slot is a zero)
+constexpr int G_OPS = 7;      // (fold: at most 7 queries -- k = 7 of a slot is a zero)
 constexpr int LDS_FOLD = RING + 2 * PL_STAGE + C_TILE + POOL_W + BITS_TILE + DN * 4;
 static_assert(LDS_FOLD <= 160 * 1024, "LDS of the folding variant");
+// the ledger: the keep-bits ahead of the A piece of point 0; the pool operands and the C tile behind that of point 1, the masked dout
+// rows behind that of point 5; the wait in stage s is for the A piece of stage s + 2
+enum { S_BITS, S_POOL, S_G, S_C };
 template <bool MASK, bool ACC, bool POOL = false, bool FOLD = false>
-constexpr int ops_at(int t) {
-  return 1 + ((MASK && t == T_BITS2) ? 2 : 0) + ((ACC && t == T_C2) ? C_OPS : 0) + ((POOL && t == T_P2) ? P_OPS : 0) + ((FOLD && t == T_G2) ? G_OPS : 0);
-}
-// the wait in stage s is for the A piece of stage s + 2, issued at issue point s + 2 - PF2: what was issued after it
-template <bool MASK, bool ACC, bool POOL = false, bool FOLD = false>
-constexpr int younger(int s) {
-  const int t0 = ((s + 2 - PF2) % NS + NS) % NS;
-  // what followed the A piece at its own issue point (the bits of MASK precede it)
-  int n = ((ACC && t0 == T_C2) ? C_OPS : 0) + ((POOL && t0 == T_P2) ? P_OPS : 0) + ((FOLD && t0 == T_G2) ? G_OPS : 0);
-  for (int t = 1; t < PF2 - 2; ++t) n += ops_at<MASK, ACC, POOL, FOLD>((t0 + t) % NS);
-  return n;
-}
-static_assert(younger<false, true, true, true>(7) == 11 && younger<false, true, true, true>(6) == 22 && younger<false, false, true, true>(2) == 14,
+constexpr Ledger split = {PF2, 2, {{BITS_OPS, at(MASK, 0), true}, {P_OPS, at(POOL, 1)}, {G_OPS, at(FOLD, 5)}, {C_OPS, at(ACC, 1)}}};
+static_assert(younger(split<false, true, true, true>, 7) == 11 && younger(split<false, true, true, true>, 6) == 22 && younger(split<false, false, true, true>, 2) == 14,
               "fold: 3 + 8 (+ 8) loads behind the piece of issue point 1, 8 behind the piece of issue point 5");
-static_assert(younger<false, false>(0) == 4 && younger<false, false>(7) == 4, "plain: four issue points of one piece");
-static_assert(younger<false, false, true>(7) == 4 && younger<false, false, true>(6) == 7 && younger<false, false, true>(2) == 7 && younger<false, false, true>(1) == 4,
+static_assert(younger(split<false, false>, 0) == 4 && younger(split<false, false>, 7) == 4, "plain: four issue points of one piece");
+static_assert(younger(split<false, false, true>, 7) == 4 && younger(split<false, false, true>, 6) == 7 && younger(split<false, false, true>, 2) == 7 && younger(split<false, false, true>, 1) == 4,
               "pool: the three loads are behind the piece of issue point 1 (waited for in stage 6) and ahead of every later piece");
 static_assert(POOL_W + POOL_G <= (C_TILE > 2 * BITS_TILE ? C_TILE : 2 * BITS_TILE), "the pool operands fit where the C tile would lie");
 }  // namespace sp
@@ -345,24 +361,8 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
   int u = (int)(((uint32_t)blockIdx.x * (uint32_t)U) / (uint32_t)L.nwg);
   const int u_end = (int)((((uint32_t)blockIdx.x + 1u) * (uint32_t)U) / (uint32_t)L.nwg);
 
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2s __attribute__((ext_vector_type(2)));
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  auto pk = [](float x, float y) -> uint32_t {       // v_cvt_pk_bf16_f32 (round to nearest even), low half = x
-    const f32x2s v = {x, y};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-  };
-  // two values -> their three parts, one dword per plane
-  auto split2 = [&](float x, float y, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
-    p0 = pk(x, y);
-    const float x1 = x - __uint_as_float(p0 << 16), y1 = y - __uint_as_float(p0 & 0xFFFF0000u);       // exact
-    p1 = pk(x1, y1);
-    const float x2 = x1 - __uint_as_float(p1 << 16), y2 = y1 - __uint_as_float(p1 & 0xFFFF0000u);     // exact
-    p2 = pk(x2, y2);
-  };
 
   // conversion: this lane's chunk of a raw stage = row cr, k 4 cg .. 4 cg + 3
   const int cq = (wave << 6) + lane, cr = cq >> 3, cg = cq & 7;
@@ -441,12 +441,14 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_void_t*)(lds + chunk * A_STAGE + wave * 1024), 16, off, chunk * (BK * 4), 0, 0);
     };
     auto issue_bits = [&](uint32_t off, int par) {
+      static_assert(BITS_OPS == 2, "the two instructions below");
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rbits, (lds_void_t*)(bits_lds + par * BITS_TILE + wave * 512), 4, off, 0, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rbits, (lds_void_t*)(bits_lds + par * BITS_TILE + wave * 512 + 256), 4, off, 256, 0, 0);
     };
     // POOL: wave w brings 256 bytes of the tile's attention weights (rows r0 .. r0 + 63, pnq floats each: contiguous) and row w of
     // both samples' masked dout ([slot][8][256] in LDS; rows >= pnq and samples past the last one: outside the descriptor, zeros)
     auto issue_pool = [&](int w) {
+      static_assert(P_OPS == 3, "the weights, then two keep-bits pieces (FOLD) or the two samples' dout rows");
       const uint32_t r0 = vrow0(w), v0 = r0 / (uint32_t)pT;
       const uint32_t wb = 256u * (uint32_t)wave + 4u * (uint32_t)lane;
       const uint32_t woff = wb < (uint32_t)(BM * pnq * 4) ? r0 * (uint32_t)pnq * 4u + wb : SDUMC_GR_NULL_OFF;
@@ -473,8 +475,8 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
         for (int e = 0; e < 4; ++e) v[e] = __uint_as_float(__float_as_uint(v[e]) & (uint32_t)__builtin_amdgcn_sbfe((int)b, e, 1u));
       }
       uint32_t q[3][2];
-      split2(v[0], v[1], q[0][0], q[1][0], q[2][0]);
-      split2(v[2], v[3], q[0][1], q[1][1], q[2][1]);
+      split_bf16x3(v[0], v[1], q[0][0], q[1][0], q[2][0]);
+      split_bf16x3(v[2], v[3], q[0][1], q[1][1], q[2][1]);
       char* dst = planes + pb * PL_STAGE + pl_woff;
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) {
@@ -482,7 +484,6 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
         *reinterpret_cast<u32x2*>(dst + pl * (BM * BK * 2)) = w;
       }
     };
-    auto op = [](const u32x4& v) { return __builtin_bit_cast(bf16x8, v); };
     // the three parts of the 8 B values of half h of stage s (registers 16 s + 8 h .. + 7)
     struct Parts {
       u32x4 p[3];
@@ -495,7 +496,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
         //  tile loop and spill: an empty asm makes the two values opaque here)
         float x = breg[16 * s + 8 * h + 2 * d], y = breg[16 * s + 8 * h + 2 * d + 1];
         asm volatile("" : "+v"(x), "+v"(y));
-        split2(x, y, bq[0][d], bq[1][d], bq[2][d]);
+        split_bf16x3(x, y, bq[0][d], bq[1][d], bq[2][d]);
       }
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) o.p[pl] = u32x4{bq[pl][0], bq[pl][1], bq[pl][2], bq[pl][3]};
@@ -505,14 +506,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) o.p[pl] = *reinterpret_cast<const u32x4*>(base + pl * (BM * BK * 2));
     };
-    auto mma6 = [&](int i, const Parts& a, const Parts& bb) {     // smallest terms first
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a.p[2]), op(bb.p[0]), acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a.p[0]), op(bb.p[2]), acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a.p[1]), op(bb.p[1]), acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a.p[1]), op(bb.p[0]), acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a.p[0]), op(bb.p[1]), acc[i], 0, 0, 0);
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(a.p[0]), op(bb.p[0]), acc[i], 0, 0, 0);
-    };
+    auto mma6 = [&](int i, const Parts& a, const Parts& bb) { mfma_bf16x3(acc[i], a.p, bb.p); };
 
     // ---- prologue: the ring belongs to this problem from here (the previous one drained it) ----
 #pragma unroll
@@ -548,6 +542,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
       float gq[8];      // FOLD: this lane's masked dout values G[v0 + lh][j][n0 + li] (issue point 5)
       auto stage = [&](auto sc) {
         constexpr int s = decltype(sc)::value;
+        constexpr const Ledger& G = split<MASK, ACC, POOL, FOLD>;
         // raw stage s + 1 (published by the previous barrier) -> the other planes buffer; stage 8 = the next tile's first
         convert((s + 1) % NS, s + 1 == NS ? par ^ 1 : par, (s + 1) & 1);
         // four blocks of six MFMAs: (h, i) = (0, 0), (0, 1), (1, 0), (1, 1).  The A parts of the next block are read and the B
@@ -569,17 +564,17 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
         __builtin_amdgcn_sched_barrier(0);
         mma6(1, a1, bh1);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(waitcnt_vm(sp::younger<MASK, ACC, POOL, FOLD>(s)));
+        __builtin_amdgcn_s_waitcnt(waitcnt_vm(younger(G, s)));
         __builtin_amdgcn_s_barrier();
-        if constexpr (MASK) {
-          if constexpr (s == T_BITS2) issue_bits(b_nxt, par ^ 1);
+        if constexpr (MASK) {      // (the outer conditions keep what a variant lacks out of the lambda's captures)
+          if constexpr (carries(G.pc[S_BITS], s)) issue_bits(b_nxt, par ^ 1);
         }
         issue_a(s + PF2 < NS ? o_cur : o_nxt, (s + PF2) % NS);
         if constexpr (POOL) {
-          if constexpr (s == T_P2) issue_pool(w);
+          if constexpr (carries(G.pc[S_POOL], s)) issue_pool(w);
         }
         if constexpr (FOLD) {
-          if constexpr (s == T_G2) {
+          if constexpr (carries(G.pc[S_G], s)) {
             const uint32_t v0 = vrow0(w) / (uint32_t)pT;
             const uint32_t gv = (uint32_t)lh * (uint32_t)pnq * (DN * 4u) + (uint32_t)(n0 + li) * 4u;
 #pragma unroll
@@ -589,7 +584,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
           }
         }
         if constexpr (ACC) {
-          if constexpr (s == T_C2) {   // this wave's rows 8 wave .. + 7 of the C tile (rows past M: outside the descriptor, zeros)
+          if constexpr (carries(G.pc[S_C], s)) {   // this wave's rows 8 wave .. + 7 of the C tile (rows past M: outside the descriptor, zeros)
             // (FOLD: only the unit that opens the tile fetches it; the others send their eight loads, from nowhere, to a dummy row --
             //  the queue of every unit holds the same operations)
             const bool real = !FOLD || first;
@@ -622,7 +617,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
             uint32_t q0, q1, q2;
-            split2(g[2 * d], g[2 * d + 1], q0, q1, q2);
+            split_bf16x3(g[2 * d], g[2 * d + 1], q0, q1, q2);
             pb_.p[0][d] = q0; pb_.p[1][d] = q1; pb_.p[2][d] = q2;
           }
         }
@@ -636,7 +631,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
             uint32_t q0, q1, q2;
-            split2(w[2 * d], w[2 * d + 1], q0, q1, q2);
+            split_bf16x3(w[2 * d], w[2 * d + 1], q0, q1, q2);
             pa_.p[0][d] = q0; pa_.p[1][d] = q1; pa_.p[2][d] = q2;
           }
           mma6(i, pa_, pb_);
@@ -723,9 +718,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_split_kernel(const Launch L) {
 // buys here is 48 KB per CU in flight all the time instead of one short k-loop per workgroup.
 // ------------------------------------------------------------------------------------------------------------------------
 namespace hf {
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define SDUMC_GR_HNS 4                            /* stages per tile (64 k each) */
-constexpr int T_C0 = 1, T_C1 = 5;               // issue points (of the pair's 8) that carry the C prefetch of tile 0 / tile 1
 // FOLD (1 or 2 = sdumc_rows_problem.fold, one value per launch): the pooling term as one more k-tile (split arithmetic: its operands are
 // fp32) and the mask-sum of the input dropouts, as in gr_split_kernel.  A unit's operands -- 64 rows of attention weights (2 KB), the
 // masked dout rows of its <= 2 samples (16 KB), its keep-bits (4 KB) -- ride in by LDS-DMA six stages before the unit's last one:
@@ -734,23 +727,17 @@ constexpr int T_C0 = 1, T_C1 = 5;               // issue points (of the pair's 8
 // prefetch registers; with `accumulate` they start from C), its second closes and stores it: no C prefetch at issue point 5.
 constexpr int HP_OPS = 5;
 constexpr int HP_W = BM * 8 * 4, HP_G = 2 * 8 * DN * 4, HP_BUF = HP_W + HP_G + BITS_TILE;
+// the ledger, over the pair's 8 issue points: the C prefetch of tile 0 behind the A piece of point 1, of tile 1 behind that of point 5;
+// the pool operands behind both
+enum { H_C, H_POOL };
 template <bool ACC, int FOLD = 0>
-constexpr int ops_at(int t) {
-  return 1 + ((ACC && (t == T_C0 || (t == T_C1 && FOLD != 2))) ? 32 : 0) + ((FOLD && (t == T_C0 || t == T_C1)) ? HP_OPS : 0);
-}
-template <bool ACC, int FOLD = 0>
-constexpr int younger(int s) {
-  const int t0 = ((s + 1 - PF) % NS + NS) % NS;
-  int n = ops_at<ACC, FOLD>(t0) - 1;            // what followed the A piece at its own issue point
-  for (int t = 1; t < PF - 1; ++t) n += ops_at<ACC, FOLD>((t0 + t) % NS);
-  return n;
-}
-static_assert(younger<false, 1>(0) == 4 + HP_OPS && younger<false, 2>(2) == 4 + 2 * HP_OPS && younger<true, 2>(2) == 4 + 2 * HP_OPS + 32, "bf16 fold");
+constexpr Ledger pair = {PF, 1, {{CPRE_OPS, at(ACC, 1) | at(ACC && FOLD != 2, 5)}, {HP_OPS, at(FOLD != 0, 1) | at(FOLD != 0, 5)}}};
+static_assert(younger(pair<false, 1>, 0) == 4 + HP_OPS && younger(pair<false, 2>, 2) == 4 + 2 * HP_OPS && younger(pair<true, 2>, 2) == 4 + 2 * HP_OPS + 32, "bf16 fold");
 }  // namespace hf
 
 // (stage 0..7 of a pair: plain 4 x 8; accumulating 36 36 68 36 36 36 68 36 -- 68 = both C prefetches were issued behind the A piece)
-static_assert(hf::younger<false>(0) == 4 && hf::younger<true>(0) == 36 && hf::younger<true>(1) == 36 && hf::younger<true>(2) == 68 &&
-              hf::younger<true>(3) == 36 && hf::younger<true>(6) == 68 && hf::younger<true>(7) == 36, "bf16 pair: C prefetch at stages 1 and 5");
+static_assert(younger(hf::pair<false>, 0) == 4 && younger(hf::pair<true>, 0) == 36 && younger(hf::pair<true>, 1) == 36 && younger(hf::pair<true>, 2) == 68 &&
+              younger(hf::pair<true>, 3) == 36 && younger(hf::pair<true>, 6) == 68 && younger(hf::pair<true>, 7) == 36, "bf16 pair: C prefetch at stages 1 and 5");
 
 template <bool ACC, int FOLD = 0>
 __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
@@ -801,7 +788,6 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
       const uint32_t bo = (uint32_t)(n0 + li) * ldb2 + 16u * (uint32_t)lh;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rb, bo, 32 * j, 0);
         breg[j] = *reinterpret_cast<const bf16x8*>(&v);
       }
@@ -830,6 +816,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
     // FOLD: the operands of unit t's extra k-tile and its keep-bits -> LDS buffer `buf` (past the run's end: from nowhere, zeros)
     char* const pool_lds = lds + RING;
     auto issue_pool = [&](int t, int buf) {
+      static_assert(HP_OPS == 1 + 2 + 2, "the weights, the two samples' dout rows, two keep-bits pieces");
       char* base = pool_lds + buf * HP_BUF;
       const bool live = t < t_end;
       const uint32_t r0 = live ? vrow0(t) : 0u, v0 = r0 / (uint32_t)pT;
@@ -891,25 +878,14 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
       // then keep . (...) * scale into the running sum / out to C
       auto fold_tail = [&](auto uc) {
         constexpr int U = decltype(uc)::value;
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        typedef float f32x2s __attribute__((ext_vector_type(2)));
-        auto pk = [](float x, float y) -> uint32_t {
-          const f32x2s v = {x, y};
-          return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-        };
         auto split8 = [&](const float (&x)[8], u32x4 (&pp)[3]) {
 #pragma unroll
           for (int d = 0; d < 4; ++d) {
-            const float a = x[2 * d], b = x[2 * d + 1];
-            const uint32_t p0 = pk(a, b);
-            const float a1 = a - __uint_as_float(p0 << 16), b1 = b - __uint_as_float(p0 & 0xFFFF0000u);
-            const uint32_t p1 = pk(a1, b1);
-            const float a2 = a1 - __uint_as_float(p1 << 16), b2 = b1 - __uint_as_float(p1 & 0xFFFF0000u);
-            pp[0][d] = p0; pp[1][d] = p1; pp[2][d] = pk(a2, b2);
+            uint32_t p0, p1, p2;
+            split_bf16x3(x[2 * d], x[2 * d + 1], p0, p1, p2);
+            pp[0][d] = p0; pp[1][d] = p1; pp[2][d] = p2;
           }
         };
-        auto opb = [](const u32x4& v) { return __builtin_bit_cast(bf16x8, v); };
         const char* base = pool_lds + U * HP_BUF;
         const uint32_t r0 = vrow0(w + U), v0 = r0 / (uint32_t)pT;
         const int rb = (int)((v0 + 1u) * (uint32_t)pT - r0);                 // first row of the unit that belongs to sample v0 + 1
@@ -930,12 +906,7 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) x[j] = (mine && j < pnq) ? wl[row * pnq + j] : 0.f;
           split8(x, pa_);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(opb(pa_[2]), opb(pb_[0]), acc[i], 0, 0, 0);      // smallest terms first
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(opb(pa_[0]), opb(pb_[2]), acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(opb(pa_[1]), opb(pb_[1]), acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(opb(pa_[1]), opb(pb_[0]), acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(opb(pa_[0]), opb(pb_[1]), acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(opb(pa_[0]), opb(pb_[0]), acc[i], 0, 0, 0);
+          mfma_bf16x3(acc[i], pa_, pb_);
         }
         const uint8_t* cb = reinterpret_cast<const uint8_t*>(base + HP_W + HP_G) + 8 * wave + (li >> 2) + 4 * lh * QW;
         const uint32_t sh = (uint32_t)(li & 3);
@@ -981,16 +952,18 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
       };
       auto stage = [&](auto sc) {
         constexpr int s = decltype(sc)::value;        // stage of the pair: tile s / 4, its stage s % 4; ring slot s
+        constexpr const Ledger& G = pair<ACC, FOLD>;
         read_frag(s, 1, fb);
         __builtin_amdgcn_sched_barrier(0);
         mma(fa, 0, s % SDUMC_GR_HNS);
         __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(waitcnt_vm(hf::younger<ACC, FOLD>(s)));
+        __builtin_amdgcn_s_waitcnt(waitcnt_vm(younger(G, s)));
         __builtin_amdgcn_s_barrier();
         issue_a(o[(s + PF) / SDUMC_GR_HNS], (s + PF) % SDUMC_GR_HNS, (s + PF) % NS);
-        if constexpr (ACC) {
-          if constexpr (s == T_C0 || (s == T_C1 && FOLD != 2)) {
-            const uint32_t c_off = co[s == T_C0 ? 0 : 1];
+        if constexpr (ACC) {      // (the outer conditions keep what a variant lacks out of the lambda's captures)
+          if constexpr (carries(G.pc[H_C], s)) {      // (of the tile this point lies in)
+            static_assert(CPRE_OPS == 2 * 16, "one load per accumulator element");
+            const uint32_t c_off = co[s / SDUMC_GR_HNS];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -998,9 +971,8 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
                 cpre[i * 16 + e] = bf2f(__builtin_amdgcn_raw_buffer_load_b16(rc, c_off, (32 * i + (e & 3) + 8 * (e >> 2)) * ldc2, 0));
           }
         }
-        if constexpr (FOLD != 0) {      // (behind the C prefetch; issue point 1: this pair's second unit, 5: the next pair's first)
-          if constexpr (s == T_C0) issue_pool(w + 1, 1);
-          if constexpr (s == T_C1) issue_pool(w + 2, 0);
+        if constexpr (FOLD != 0) {      // (behind the C prefetch; issue point 1: this pair's second unit into buffer 1, 5: the next pair's first into buffer 0)
+          if constexpr (carries(G.pc[H_POOL], s)) issue_pool(w + 1 + s / SDUMC_GR_HNS, 1 - s / SDUMC_GR_HNS);
         }
         __builtin_amdgcn_sched_barrier(0);
         read_frag((s + 1) % NS, 0, fa);
@@ -1033,30 +1005,109 @@ __global__ __launch_bounds__(NTHR, 2) void gr_bf16_kernel(const Launch L) {
 #endif
 }
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
+// Every instantiation, once: set_lds_attr() walks both tables and a launcher looks its variant up in one, so none is launchable
+// without its attribute; a combination without a row is refused.  `fold`: the bf16 kernels are compiled per fold count; the split
+// kernel reads the count from each problem, its key is fold > 0.
+struct Variant {
+  bool split, mask, acc, pool;
+  int fold;
+  void (*kernel)(const Launch);
+  size_t lds;
+};
+constexpr size_t LDS_HF_FOLD = RING + 2 * hf::HP_BUF;
+constexpr Variant F32_VARIANTS[] = {
+    {false, false, false, false, 0, &gr_kernel<false, false>, LDS_BYTES},
+    {false, true, false, false, 0, &gr_kernel<true, false>, LDS_BYTES},
+    {false, false, true, false, 0, &gr_kernel<false, true>, LDS_BYTES},
+    {true, false, false, false, 0, &gr_split_kernel<false, false>, sp::LDS_BYTES2},
+    {true, true, false, false, 0, &gr_split_kernel<true, false>, sp::LDS_BYTES2},
+    {true, false, true, false, 0, &gr_split_kernel<false, true>, sp::LDS_BYTES2},
+    {true, false, false, true, 0, &gr_split_kernel<false, false, true>, sp::LDS_BYTES2},      // (the pooling k-tile: split arithmetic only)
+    {true, false, false, true, 1, &gr_split_kernel<false, false, true, true>, sp::LDS_FOLD},
+    {true, false, true, true, 1, &gr_split_kernel<false, true, true, true>, sp::LDS_FOLD},
+};
+constexpr Variant BF16_VARIANTS[] = {      // (no fused dropout -- the engine materialises the masked frames -- and no pooling term without the fold)
+    {false, false, false, false, 0, &gr_bf16_kernel<false>, RING},
+    {false, false, true, false, 0, &gr_bf16_kernel<true>, RING},
+    {false, false, false, true, 1, &gr_bf16_kernel<false, 1>, LDS_HF_FOLD},
+    {false, false, true, true, 1, &gr_bf16_kernel<true, 1>, LDS_HF_FOLD},
+    {false, false, false, true, 2, &gr_bf16_kernel<false, 2>, LDS_HF_FOLD},
+    {false, false, true, true, 2, &gr_bf16_kernel<true, 2>, LDS_HF_FOLD},
+};
+template <size_t N>
+const Variant* find(const Variant (&table)[N], bool split, const sdumc_rows_problem& p, int fold) {
+  for (const Variant& v : table)
+    if (v.split == split && v.mask == (p.a_bits != nullptr) && v.acc == (p.accumulate != 0) && v.pool == (p.pool_w != nullptr) && v.fold == fold) return &v;
+  return nullptr;
+}
+
 bool set_lds_attr() {   // the dynamic-LDS limit is a per-device function attribute
   static sdumc_dev_once attr_set;
   return sdumc_once_per_device(attr_set, [] {
-           return sdumc_set_dyn_lds(&gr_kernel<false, false>, LDS_BYTES) && sdumc_set_dyn_lds(&gr_kernel<true, false>, LDS_BYTES) &&
-                  sdumc_set_dyn_lds(&gr_kernel<false, true>, LDS_BYTES) &&
-                  sdumc_set_dyn_lds(&gr_split_kernel<false, false>, sp::LDS_BYTES2) && sdumc_set_dyn_lds(&gr_split_kernel<true, false>, sp::LDS_BYTES2) &&
-                  sdumc_set_dyn_lds(&gr_split_kernel<false, true>, sp::LDS_BYTES2) && sdumc_set_dyn_lds(&gr_split_kernel<false, false, true>, sp::LDS_BYTES2) &&
-                  sdumc_set_dyn_lds(&gr_split_kernel<false, false, true, true>, sp::LDS_FOLD) && sdumc_set_dyn_lds(&gr_split_kernel<false, true, true, true>, sp::LDS_FOLD) &&
-                  sdumc_set_dyn_lds(&gr_bf16_kernel<false>, RING) && sdumc_set_dyn_lds(&gr_bf16_kernel<true>, RING) &&
-                  sdumc_set_dyn_lds(&gr_bf16_kernel<false, 1>, RING + 2 * hf::HP_BUF) && sdumc_set_dyn_lds(&gr_bf16_kernel<true, 1>, RING + 2 * hf::HP_BUF) &&
-                  sdumc_set_dyn_lds(&gr_bf16_kernel<false, 2>, RING + 2 * hf::HP_BUF) && sdumc_set_dyn_lds(&gr_bf16_kernel<true, 2>, RING + 2 * hf::HP_BUF);
+           for (const Variant& v : F32_VARIANTS)
+             if (!sdumc_set_dyn_lds(v.kernel, v.lds)) return false;
+           for (const Variant& v : BF16_VARIANTS)
+             if (!sdumc_set_dyn_lds(v.kernel, v.lds)) return false;
+           return true;
          }) == SDUMC_OK;
 }
 
-bool valid(const sdumc_rows_problem& p) {
-  if (!p.A || !p.B || !p.C || p.M <= 0 || p.lda < DK || p.ldb < DN || p.ldc < DN || (p.lda & 3) || p.a_row_mod < 0) return false;
-  if (reinterpret_cast<uintptr_t>(p.A) & 15) return false;
-  if ((reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C)) & 3) return false;
-  if (p.a_bits && (reinterpret_cast<uintptr_t>(p.a_bits) & 3)) return false;
+// What differs between the problems of the two entry points; the rest of valid() is shared.
+struct Form {
+  int esz;                    // bytes per element of A, B and C
+  int lda_mask, ldb_mask;     // fp32: lda a multiple of 4; bf16: lda and ldb multiples of 8 (16-byte rows)
+  int b_align, c_align;       // bytes (A: 16 in both)
+  int margin;                 // rows past M that are still addressed: two tiles, four for the bf16 kernel's pairs
+  bool fold_exact;            // bf16: one fold count per launch; fp32: problems of fold 1 and 2 may share a launch
+};
+constexpr Form FORM_F32 = {4, 3, 0, 4, 4, 2 * BM, false}, FORM_BF16 = {2, 7, 7, 16, 2, 4 * BM, true};
+
+bool valid(const sdumc_rows_problem& p, const Form& f, const Variant& v) {
+  auto off = [](const void* q, uintptr_t align) { return (reinterpret_cast<uintptr_t>(q) & (align - 1)) != 0; };
+  if (!p.A || !p.B || !p.C || p.M <= 0 || p.lda < DK || p.ldb < DN || p.ldc < DN || (p.lda & f.lda_mask) || (p.ldb & f.ldb_mask) || p.a_row_mod < 0) return false;
+  if (off(p.A, 16) || off(p.B, f.b_align) || off(p.C, f.c_align) || off(p.a_bits, 4)) return false;
   if (p.act != SDUMC_ACT_NONE && p.act != SDUMC_ACT_TANH) return false;
   // 32-bit byte offsets, descriptor ranges below 2 GiB (a tile past the last row is still addressed)
-  const size_t rows = (size_t)p.M + 2 * BM;
-  if (rows * p.lda * 4 >= 0x7FFFFFF0u || rows * p.ldc * 4 >= 0x7FFFFFF0u) return false;
+  const size_t rows = (size_t)p.M + f.margin;
+  if (rows * p.lda * f.esz >= 0x7FFFFFF0u || rows * p.ldc * f.esz >= 0x7FFFFFF0u) return false;
+  // one kernel variant per launch
+  if ((p.a_bits != nullptr) != v.mask || (p.accumulate != 0) != v.acc || (p.pool_w != nullptr) != v.pool) return false;
+  if ((f.fold_exact ? p.fold : (int)(p.fold > 0)) != v.fold) return false;
+  if (v.pool) {      // (fold: at most 7 queries -- k = 7 of a slot is a zero)
+    if (!p.pool_g || p.pool_nq < 1 || p.pool_nq > (v.fold ? 7 : 8) || !(p.pool_T >= 63 || p.pool_T == 32) || (p.M % p.pool_T) || p.a_row_mod || p.bias || p.act != SDUMC_ACT_NONE) return false;
+    if (off(p.pool_w, 4) || off(p.pool_g, 16)) return false;
+  }
+  if (v.fold && (p.fold > 2 || (p.M % p.fold) || ((p.M / p.fold) % p.pool_T) || off(p.c_bits, 4))) return false;
   return true;
+}
+
+// max_wg > 0: at most that many (persistent) workgroups -- a launch that should leave part of the chip to a neighbour
+int launch(const sdumc_rows_problem* probs, int32_t n, int32_t max_wg, void* stream, const Form& f, const Variant* v, int prof_variant) {
+  if (!v) return SDUMC_EINVAL;
+  Launch L;
+  memset(&L, 0, sizeof(L));
+  int units = 0;
+  double flops = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const sdumc_rows_problem& p = probs[i];
+    if (!valid(p, f, *v)) return SDUMC_EINVAL;
+    L.p[i] = p;
+    L.unit0[i] = units;
+    units += ((v->fold ? p.M / p.fold : p.M) + BM - 1) / BM;      // (fold: a unit of the launch = an OUTPUT tile)
+    flops += 2.0 * p.M * (double)DK * DN;
+  }
+  L.unit0[n] = units;
+  L.n = n;
+  L.nwg = std::min(sdumc_cu_count(), units);      // (bf16: a workgroup works through pairs of tiles; with fewer tiles than CUs a pair is one tile and nothing)
+  if (max_wg > 0) L.nwg = std::min(L.nwg, (int)max_wg);
+  if ((long long)units * (L.nwg + 1) >= (1LL << 31)) return SDUMC_EINVAL;
+  if (!set_lds_attr()) return SDUMC_ELAUNCH;
+  const int tok = sdumc_prof_begin_(prof_variant, flops, stream);
+  hipLaunchKernelGGL(v->kernel, dim3(L.nwg), dim3(NTHR), v->lds, as_stream(stream), L);
+  sdumc_prof_end_(tok, stream);
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
 }
 
 }  // namespace sdumc_gr
@@ -1067,111 +1118,21 @@ extern "C" int sdumc_gemm_rows_prepare_(void) { return set_lds_attr() ? SDUMC_OK
 extern "C" int sdumc_gemm_rows256(const sdumc_rows_problem* probs, int32_t n, void* stream) {
   return sdumc_gemm_rows256_capped_(probs, n, 0, stream);
 }
-// max_wg > 0: at most that many (persistent) workgroups -- a launch that should leave part of the chip to a neighbour
 extern "C" int sdumc_gemm_rows256_capped_(const sdumc_rows_problem* probs, int32_t n, int32_t max_wg, void* stream) {
   if (!probs || n <= 0 || n > MAXP) return SDUMC_EINVAL;
-  const bool mask = probs[0].a_bits != nullptr, accum = probs[0].accumulate != 0, pool = probs[0].pool_w != nullptr;
-  if (mask && accum) return SDUMC_EINVAL;
-  const bool fold = probs[0].fold > 0;
-  if (pool && (mask || (accum && !fold) || !sdumc_split_on_(SDUMC_SPLIT_ROWS))) return SDUMC_EINVAL;      // (the pooling k-tile: split arithmetic only)
-  if (fold && !pool) return SDUMC_EINVAL;
-  Launch L;
-  memset(&L, 0, sizeof(L));
-  int units = 0;
-  double flops = 0.0;
-  for (int i = 0; i < n; ++i) {
-    if (!valid(probs[i])) return SDUMC_EINVAL;
-    if ((probs[i].a_bits != nullptr) != mask || (probs[i].accumulate != 0) != accum || (probs[i].pool_w != nullptr) != pool) return SDUMC_EINVAL;   // one kernel variant per launch
-    if (pool) {
-      const sdumc_rows_problem& q = probs[i];
-      if (!q.pool_g || q.pool_nq < 1 || q.pool_nq > 8 || !(q.pool_T >= 63 || q.pool_T == 32) || (q.M % q.pool_T) || q.a_row_mod || q.bias || q.act != SDUMC_ACT_NONE) return SDUMC_EINVAL;
-      if ((reinterpret_cast<uintptr_t>(q.pool_w) & 3) || (reinterpret_cast<uintptr_t>(q.pool_g) & 15)) return SDUMC_EINVAL;
-    }
-    if ((probs[i].fold > 0) != fold) return SDUMC_EINVAL;
-    if (fold) {
-      const sdumc_rows_problem& q = probs[i];
-      if (q.fold > 2 || q.pool_nq > 7 || (q.M % q.fold) || ((q.M / q.fold) % q.pool_T) || (reinterpret_cast<uintptr_t>(q.c_bits) & 3)) return SDUMC_EINVAL;
-    }
-    L.p[i] = probs[i];
-    L.unit0[i] = units;
-    units += ((fold ? probs[i].M / probs[i].fold : probs[i].M) + BM - 1) / BM;      // (fold: a unit of the launch = an OUTPUT tile)
-    flops += 2.0 * probs[i].M * (double)DK * DN;
-  }
-  L.unit0[n] = units;
-  L.n = n;
-  L.nwg = std::min(sdumc_cu_count(), units);
-  if (max_wg > 0) L.nwg = std::min(L.nwg, (int)max_wg);
-  if ((long long)units * (L.nwg + 1) >= (1LL << 31)) return SDUMC_EINVAL;
-  if (!set_lds_attr()) return SDUMC_ELAUNCH;
-  hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(sdumc_split_on_(SDUMC_SPLIT_ROWS) ? SDUMC_PV_gemm_rows256_bf16x3 : SDUMC_PV_gemm_rows256, flops, stream);
-  if (sdumc_split_on_(SDUMC_SPLIT_ROWS)) {
-    if (fold && accum) hipLaunchKernelGGL((gr_split_kernel<false, true, true, true>), dim3(L.nwg), dim3(NTHR), sp::LDS_FOLD, st, L);
-    else if (fold) hipLaunchKernelGGL((gr_split_kernel<false, false, true, true>), dim3(L.nwg), dim3(NTHR), sp::LDS_FOLD, st, L);
-    else if (pool) hipLaunchKernelGGL((gr_split_kernel<false, false, true>), dim3(L.nwg), dim3(NTHR), sp::LDS_BYTES2, st, L);
-    else if (mask) hipLaunchKernelGGL((gr_split_kernel<true, false>), dim3(L.nwg), dim3(NTHR), sp::LDS_BYTES2, st, L);
-    else if (accum) hipLaunchKernelGGL((gr_split_kernel<false, true>), dim3(L.nwg), dim3(NTHR), sp::LDS_BYTES2, st, L);
-    else hipLaunchKernelGGL((gr_split_kernel<false, false>), dim3(L.nwg), dim3(NTHR), sp::LDS_BYTES2, st, L);
-  } else if (mask) hipLaunchKernelGGL((gr_kernel<true, false>), dim3(L.nwg), dim3(NTHR), LDS_BYTES, st, L);
-  else if (accum) hipLaunchKernelGGL((gr_kernel<false, true>), dim3(L.nwg), dim3(NTHR), LDS_BYTES, st, L);
-  else hipLaunchKernelGGL((gr_kernel<false, false>), dim3(L.nwg), dim3(NTHR), LDS_BYTES, st, L);
-  sdumc_prof_end_(tok, stream);
-  SDUMC_CHECK_LAUNCH();
-  return SDUMC_OK;
+  const bool split = sdumc_split_on_(SDUMC_SPLIT_ROWS);
+  return launch(probs, n, max_wg, stream, FORM_F32, find(F32_VARIANTS, split, probs[0], probs[0].fold > 0),
+                split ? SDUMC_PV_gemm_rows256_bf16x3 : SDUMC_PV_gemm_rows256);
 }
 
 // A ([M][256]), B ([256 n][256 k], row stride ldb: C = A B^T) and C are bf16 tensors (lda / ldb / ldc in elements, lda a multiple
-// of 8, A 16-byte aligned); bias fp32; no fused dropout (a_bits must be NULL: the engine materialises the masked frames)
+// of 8, A 16-byte aligned); bias fp32; fp32 pool_w / pool_g with the fold
 extern "C" int sdumc_gemm_rows256_bf16(const sdumc_rows_problem* probs, int32_t n, void* stream) {
   return sdumc_gemm_rows256_bf16_capped_(probs, n, 0, stream);
 }
 extern "C" int sdumc_gemm_rows256_bf16_capped_(const sdumc_rows_problem* probs, int32_t n, int32_t max_wg, void* stream) {
   if (!probs || n <= 0 || n > MAXP) return SDUMC_EINVAL;
-  const bool accum = probs[0].accumulate != 0;
-  const int fold = probs[0].fold;
-  Launch L;
-  memset(&L, 0, sizeof(L));
-  int units = 0;
-  double flops = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const sdumc_rows_problem& p = probs[i];
-    if (!p.A || !p.B || !p.C || p.a_bits || p.M <= 0 || p.lda < DK || p.ldb < DK || p.ldc < DN || (p.lda & 7) || (p.ldb & 7) || p.a_row_mod < 0)
-      return SDUMC_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B)) & 15) return SDUMC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(p.C) & 1) return SDUMC_EINVAL;
-    if (p.act != SDUMC_ACT_NONE && p.act != SDUMC_ACT_TANH) return SDUMC_EINVAL;
-    const size_t rows = (size_t)p.M + 4 * BM;
-    if (rows * p.lda * 2 >= 0x7FFFFFF0u || rows * p.ldc * 2 >= 0x7FFFFFF0u) return SDUMC_EINVAL;
-    if ((p.accumulate != 0) != accum || p.fold != fold) return SDUMC_EINVAL;
-    if (fold) {      // the pooling term and the mask-sum folded in (sdumc_rows_problem.fold; fp32 pool_w / pool_g, bf16 A / B / C)
-      if (fold > 2 || !p.pool_w || !p.pool_g || p.pool_nq < 1 || p.pool_nq > 7 || !(p.pool_T >= 63 || p.pool_T == 32) || (p.M % fold) ||
-          ((p.M / fold) % p.pool_T) || p.a_row_mod || p.bias || p.act != SDUMC_ACT_NONE)
-        return SDUMC_EINVAL;
-      if ((reinterpret_cast<uintptr_t>(p.pool_w) & 3) || (reinterpret_cast<uintptr_t>(p.pool_g) & 15) || (reinterpret_cast<uintptr_t>(p.c_bits) & 3)) return SDUMC_EINVAL;
-    } else if (p.pool_w) return SDUMC_EINVAL;      // (the pooling term alone: fp32 launches only)
-    L.p[i] = p;
-    L.unit0[i] = units;
-    units += ((fold ? p.M / fold : p.M) + BM - 1) / BM;      // (fold: a unit of the launch = an OUTPUT tile)
-    flops += 2.0 * p.M * (double)DK * DN;
-  }
-  L.unit0[n] = units;
-  L.n = n;
-  L.nwg = std::min(sdumc_cu_count(), units);      // (a workgroup works through pairs of tiles; with fewer tiles than CUs a pair is one tile and nothing)
-  if (max_wg > 0) L.nwg = std::min(L.nwg, (int)max_wg);
-  if ((long long)units * (L.nwg + 1) >= (1LL << 31)) return SDUMC_EINVAL;
-  if (!set_lds_attr()) return SDUMC_ELAUNCH;
-  hipStream_t st = as_stream(stream);
-  const int tok = sdumc_prof_begin_(SDUMC_PV_gemm_rows256_bf16, flops, stream);
-  const size_t lds_fold = RING + 2 * hf::HP_BUF;
-  if (fold == 2 && accum) hipLaunchKernelGGL((gr_bf16_kernel<true, 2>), dim3(L.nwg), dim3(NTHR), lds_fold, st, L);
-  else if (fold == 2) hipLaunchKernelGGL((gr_bf16_kernel<false, 2>), dim3(L.nwg), dim3(NTHR), lds_fold, st, L);
-  else if (fold == 1 && accum) hipLaunchKernelGGL((gr_bf16_kernel<true, 1>), dim3(L.nwg), dim3(NTHR), lds_fold, st, L);
-  else if (fold == 1) hipLaunchKernelGGL((gr_bf16_kernel<false, 1>), dim3(L.nwg), dim3(NTHR), lds_fold, st, L);
-  else if (accum) hipLaunchKernelGGL((gr_bf16_kernel<true>), dim3(L.nwg), dim3(NTHR), RING, st, L);
-  else hipLaunchKernelGGL((gr_bf16_kernel<false>), dim3(L.nwg), dim3(NTHR), RING, st, L);
-  sdumc_prof_end_(tok, stream);
-  SDUMC_CHECK_LAUNCH();
-  return SDUMC_OK;
+  return launch(probs, n, max_wg, stream, FORM_BF16, find(BF16_VARIANTS, false, probs[0], probs[0].fold), SDUMC_PV_gemm_rows256_bf16);
 }
 
 SDUMC_PRELOAD_HOOK(gemm_rows)      // (common.h)

@@ -301,25 +301,15 @@ __device__ __forceinline__ void gemm_wide_body(const sdumc_gemm& g, const int ns
 
   // the k-tile (16 k) as ONE bf16 MFMA depth: a lane's eight k of an operand are its two fp32 fragments side by side
   // (k = 4 lh + s and 8 + 4 lh + s), the same assignment for A and B
-  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2s __attribute__((ext_vector_type(2)));
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  auto pk = [](float x, float y) -> uint32_t {       // v_cvt_pk_bf16_f32 (round to nearest even), low half = x
-    const f32x2s v = {x, y};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-  };
   auto split8 = [&](const f32x4 lo, const f32x4 hi, u32x4* pl) {
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       const float x = d < 2 ? lo[2 * d] : hi[2 * d - 4], y = d < 2 ? lo[2 * d + 1] : hi[2 * d - 3];
-      const uint32_t p0 = pk(x, y);
-      const float x1 = x - __uint_as_float(p0 << 16), y1 = y - __uint_as_float(p0 & 0xFFFF0000u);       // exact
-      const uint32_t p1 = pk(x1, y1);
-      const float x2 = x1 - __uint_as_float(p1 << 16), y2 = y1 - __uint_as_float(p1 & 0xFFFF0000u);     // exact
+      uint32_t p0, p1, p2;
+      split_bf16x3(x, y, p0, p1, p2);
       pl[0][d] = p0;
       pl[1][d] = p1;
-      pl[2][d] = pk(x2, y2);
+      pl[2][d] = p2;
     }
   };
   auto compute_split = [&](const char* base) {
@@ -329,21 +319,13 @@ __device__ __forceinline__ void gemm_wide_body(const sdumc_gemm& g, const int ns
     read_b(base, 0, bf[0]);
     read_b(base, 1, bf[1]);
     u32x4 pa[TM][3], pb[TN][3];
-    auto op = [](const u32x4& v) { return __builtin_bit_cast(bf16x8, v); };
 #pragma unroll
     for (int j = 0; j < TN; ++j) split8(bf[0][j], bf[1][j], pb[j]);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       split8(af[0][i], af[1][i], pa[i]);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {   // smallest terms first
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][2]), op(pb[j][0]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][0]), op(pb[j][2]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][1]), op(pb[j][1]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][1]), op(pb[j][0]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][0]), op(pb[j][1]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[i][0]), op(pb[j][0]), acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < TN; ++j) mfma_bf16x3(acc[i][j], pa[i], pb[j]);
     }
   };
 

@@ -16,14 +16,11 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&pl)[3]) {
 #pragma unroll
   for (int d = 0; d < 4; ++d) {
-    const float x = v[2 * d], y = v[2 * d + 1];
-    const uint32_t p0 = pack_bf16x2(x, y);
-    const float x1 = x - __uint_as_float(p0 << 16), y1 = y - __uint_as_float(p0 & 0xFFFF0000u);       // exact
-    const uint32_t p1 = pack_bf16x2(x1, y1);
-    const float x2 = x1 - __uint_as_float(p1 << 16), y2 = y1 - __uint_as_float(p1 & 0xFFFF0000u);     // exact
+    uint32_t p0, p1, p2;
+    split_bf16x3(v[2 * d], v[2 * d + 1], p0, p1, p2);
     pl[0][d] = p0;
     pl[1][d] = p1;
-    pl[2][d] = pack_bf16x2(x2, y2);
+    pl[2][d] = p2;
   }
 }
 
@@ -197,17 +194,16 @@ __device__ __forceinline__ void p3_mainloop(char* lds, const __amdgpu_buffer_rsr
         }
       }
     }
-    // smallest terms first: (a2 b0), (a0 b2), (a1 b1), (a1 b0), (a0 b1), (a0 b0); term-major over the TM accumulator tiles, so
-    // consecutive MFMAs never depend on each other
-    constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};
+    // smallest terms first (prims.h: BF16X3_TA / _TB); term-major over the TM accumulator tiles, so consecutive MFMAs never
+    // depend on each other
 #pragma unroll
     for (int t = 0; t < 6; ++t)
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if (SDUMC_P3_DBG & 4) acc[i][j][t] += __uint_as_float(pa[P][i][TA[t]][0] ^ pb[S][j][TB[t]][1]);
-          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[P][i][TA[t]]), op(pb[S][j][TB[t]]), acc[i][j], 0, 0, 0);
+          if (SDUMC_P3_DBG & 4) acc[i][j][t] += __uint_as_float(pa[P][i][BF16X3_TA[t]][0] ^ pb[S][j][BF16X3_TB[t]][1]);
+          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(op(pa[P][i][BF16X3_TA[t]]), op(pb[S][j][BF16X3_TB[t]]), acc[i][j], 0, 0, 0);
         }
   };
   auto interleave = [&]() {      // one memory instruction in the shadow of every MFMA as long as there are any

@@ -40,6 +40,27 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
+// ---- fp32 products on the bf16 matrix pipe (gemm_group.hip derives the arithmetic) ----
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+// two fp32 values -> their three bf16 parts, one dword per plane (low half = x): x == p0.x + p1.x + p2.x exactly.
+// tests/test_split_arithmetic.py restates this on the CPU.
+__device__ __forceinline__ void split_bf16x3(float x, float y, uint32_t& p0, uint32_t& p1, uint32_t& p2) {
+  p0 = pack_bf16x2(x, y);
+  const float x1 = x - __uint_as_float(p0 << 16), y1 = y - __uint_as_float(p0 & 0xFFFF0000u);       // exact
+  p1 = pack_bf16x2(x1, y1);
+  const float x2 = x1 - __uint_as_float(p1 << 16), y2 = y1 - __uint_as_float(p1 & 0xFFFF0000u);     // exact
+  p2 = pack_bf16x2(x2, y2);
+}
+// the six largest of the nine part products, smallest terms first: (a2 b0), (a0 b2), (a1 b1), (a1 b0), (a0 b1), (a0 b0)
+constexpr int BF16X3_TA[6] = {2, 0, 1, 1, 0, 0}, BF16X3_TB[6] = {0, 2, 1, 0, 1, 0};
+// one accumulator tile += a b, a and b as three planes of eight k each
+__device__ __forceinline__ void mfma_bf16x3(f32x16& acc, const u32x4 (&a)[3], const u32x4 (&b)[3]) {
+#pragma unroll
+  for (int t = 0; t < 6; ++t)
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[BF16X3_TA[t]]), __builtin_bit_cast(bf16x8, b[BF16X3_TB[t]]), acc, 0, 0, 0);
+}
+
 // ---- 16-byte accesses ----
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }

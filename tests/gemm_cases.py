@@ -223,6 +223,7 @@ for _v, _split, _hf in (("gemm_rows256_bf16x3", 1, False), ("gemm_rows256", 0, F
         run("rows", _v, "fold1_bits", (64, 256), P(195, 256, 256, pool=(65, 7), fold=1, cbits=True, **_kw), **_o)
         run("rows", _v, "fold2_bits_acc", (64, 256), P(2 * 130, 256, 256, pool=(65, 1), fold=2, cbits=True, acc=True, **_kw), **_o)
         run("rows", _v, "fold2_nobits", (64, 256), P(2 * 96, 256, 256, pool=(32, 7), fold=2, **_kw), **_o)
+        run("rows", _v, "fold1_acc_nobits", (64, 256), P(130, 256, 256, pool=(65, 7), fold=1, acc=True, **_kw), **_o)
 
 # sdumc_frame_dx: C = dz [M, 256] . W [256, N], N % 256.  The split route has no profile hook: the launcher's dispatch names it
 # (frame_dx.hip: bit 1 on -> frame_dx_kernel, nothing recorded; off -> the NN form of sdumc_gemm_f32, which IS recorded)

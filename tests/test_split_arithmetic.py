@@ -7,7 +7,7 @@ import torch
 
 
 def split3(a):
-    """a (fp32) -> a0, a1, a2 (bf16 values held in fp32), exactly as split2() in the kernels"""
+    """a (fp32) -> a0, a1, a2 (bf16 values held in fp32), exactly as split_bf16x3() of sdumc_amd/csrc/prims.h, the kernels' one split"""
     a0 = a.to(torch.bfloat16).to(torch.float32)
     r1 = a - a0                                   # exact in fp32 (asserted below)
     a1 = r1.to(torch.bfloat16).to(torch.float32)
