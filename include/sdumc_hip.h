@@ -705,6 +705,32 @@ int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, f
                      float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                      void* stream);
 
+/* Per-tensor learning rates, decay and frozen tensors over the ONE flat bucket: torch.optim.Adam with one parameter group per tensor
+ * and one shared step count.  A segment names elements [offset, offset + n) of param / grad / exp_avg / exp_avg_sq; its elements
+ * are updated with step size hyper[2] * lr_scale and coupled L2 weight_decay * wd_scale (two fp32 products; everything else is the
+ * expression of sdumc_adam_step, so a table of ones gives that call's bits).  lr_scale == 0 is torch's lr = 0 group: the parameter
+ * stays, the moments advance.  frozen != 0 is requires_grad = False: parameter and both moments are neither read nor written, the
+ * gradient is not read (the scales of a frozen segment are checked like any and then not used).  Elements of the bucket that
+ * belong to no segment (alignment padding) get the update of sdumc_adam_step.  Segments need only their natural 4-byte alignment:
+ * any offset, any length >= 1. */
+#define SDUMC_RATES_MAX_SEGS 96    /* the table travels in the kernel arguments, like sdumc_adam_table */
+typedef struct sdumc_rate_seg {
+  int64_t offset, n;       /* elements [offset, offset + n) of the bucket */
+  float lr_scale, wd_scale;
+  int32_t frozen;
+} sdumc_rate_seg;
+/* sdumc_adam_step with the table (HOST memory, read during the call): hyper advances once, then ONE launch over the bucket.
+ * SDUMC_EINVAL before anything is launched: what sdumc_adam_step refuses (null pointers, n <= 0, a buffer that is not 16-byte
+ * aligned), segs NULL, nseg outside 1 .. SDUMC_RATES_MAX_SEGS, a segment with n < 1 or outside [0, n), segments that are not
+ * ascending or that overlap, a scale that is negative, NaN or Inf. */
+int sdumc_adam_step_rates(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper, float beta1,
+                          float beta2, float eps, float weight_decay, float grad_scale, const sdumc_rate_seg* segs, int32_t nseg,
+                          void* stream);
+/* Writes +0.0f over the segments of buf[0 .. n) with frozen != 0 and nothing else (one launch; none when no segment is frozen):
+ * what a frozen tensor's gradient reads as to everyone behind the backward.  buf 16-byte aligned; the table as above, refused
+ * alike. */
+int sdumc_zero_segments(float* buf, int64_t n, const sdumc_rate_seg* segs, int32_t nseg, void* stream);
+
 /* Batch assembly from a device-resident packed feature store = the collater's padding
  * (toolkit/utils/read_data.py:139-151, :223-248; toolkit/data/feat_data.py:232-253) on the GPU:
  * out[b, t, :] = packed[start[b] + t, :] for t < len[b], zero beyond, out is [B, Tmax, d].
@@ -1381,6 +1407,16 @@ typedef struct sdumc_saliency_desc {
 } sdumc_saliency_desc;
 int sdumc_frame_saliency(const sdumc_saliency_desc* descs, int32_t n, const int64_t* idx, void* stream);
 
+/* sdumc_step_cfg.rates: the fused step's per-tensor learning-rate scale, decay scale and frozen flag, indexed by LIVE tensor in
+ * sdumc_param_table order (entry i = the i-th line with live == 1).  The step turns it into sdumc_adam_step_rates' segment table
+ * with the layout's own offsets. */
+typedef struct sdumc_tensor_rates {
+  int32_t n;                                /* the live tensor count of the step's dims */
+  float lr_scale[SDUMC_RATES_MAX_SEGS];     /* finite, >= 0 */
+  float wd_scale[SDUMC_RATES_MAX_SEGS];     /* finite, >= 0 */
+  uint8_t frozen[SDUMC_RATES_MAX_SEGS];     /* != 0: torch's requires_grad = False */
+} sdumc_tensor_rates;
+
 /* Two-stream self-distillation step (main :119-150). */
 typedef struct sdumc_step_cfg {
   float weights[6];      /* full_mse, missing_mse, text_feat, text_query_feat, features, rnc (main :234-239) */
@@ -1408,6 +1444,16 @@ typedef struct sdumc_step_cfg {
   const float* ssd_global;        /* device float[3]: all-reduced sums of squared differences (text, query, fused) */
   const float* rnc_feats_global;  /* [2*B_global, 64] = cat(r_stream0 of all ranks, r_stream1 of all ranks) */
   const float* rnc_labels_global; /* [2*B_global] */
+  /* Per-tensor learning rates, decay and frozen tensors (sdumc_adam_step_rates, which see); NULL = the step without them, launch
+   * for launch.  A HOST pointer, read during the call.  Tensor i is updated with hyper[2] * lr_scale[i] and weight_decay *
+   * wd_scale[i] by ONE launch in Adam's place, which carries Adam's holds (cluster failure, a skipped step) and its scalar tail.  A
+   * frozen tensor keeps parameter and moments bit for bit, and its segment of the gradient bucket is +0.0f to everyone behind the
+   * backward (sdumc_zero_segments, in front of sdumc_grad_guard): the guard's norm and whoever reads the bucket after the step.
+   * frame_dim_reshape_m with weight AND bias frozen: modality m's frame dW is not computed at all; every other frozen tensor's
+   * gradient is computed and then zeroed.  SDUMC_EINVAL before the forward is enqueued: n other than the live tensor count of the
+   * dims, a scale that is negative, NaN or Inf.  (In the middle like the guard fields, which tests pin between `losses` and
+   * `B_global`: behind the data-parallel pointers.) */
+  const sdumc_tensor_rates* rates;
   int32_t rnc_row0[2];   /* rows of this rank's stream-0 / stream-1 features in the gathered matrix */
   /* The contrastive criterion over the [2B, 64] rnc rows (losses[6], weights[5]): SDUMC_CONTRAST_RNC (0 = a zeroed
    * struct) RnCLoss with `temperature`; SDUMC_CONTRAST_SUPCON SupConLoss (loss.py:143-240) with the two streams as the

@@ -169,13 +169,37 @@ GUARD_ABI = _guard_abi()
 _GUARD_FIELDS = [("clip_norm", C.c_float), ("skip_nonfinite", C.c_int32), ("guard", C.c_void_p), ("guard_scratch", C.c_void_p)]
 
 
+RATES_MAX_SEGS = 96
+
+
+class RateSeg(C.Structure):         # sdumc_rate_seg: elements [offset, offset + n) of the bucket, their scales, frozen or not
+    _fields_ = [("offset", C.c_int64), ("n", C.c_int64), ("lr_scale", C.c_float), ("wd_scale", C.c_float), ("frozen", C.c_int32)]
+
+
+class TensorRates(C.Structure):     # sdumc_tensor_rates: sdumc_step_cfg.rates, indexed by live tensor in sdumc_param_table order
+    _fields_ = [("n", C.c_int32), ("lr_scale", C.c_float * RATES_MAX_SEGS), ("wd_scale", C.c_float * RATES_MAX_SEGS),
+                ("frozen", C.c_uint8 * RATES_MAX_SEGS)]
+
+
+def _rates_abi():
+    """False only for an A/B against an older build (SDUMC_LIB, tools/rates_bench.py) from before sdumc_adam_step_rates: that library
+    reads sdumc_step_cfg WITHOUT the rates pointer, which sits in the struct's middle, so StepCfg leaves it out for it."""
+    if not os.environ.get("SDUMC_LIB") or not os.path.exists(LIB_PATH):
+        return True
+    return hasattr(C.CDLL(LIB_PATH), "sdumc_adam_step_rates")
+
+
+RATES_ABI = _rates_abi()
+_RATES_FIELDS = [("rates", C.POINTER(TensorRates))]
+
+
 class StepCfg(C.Structure):
     _fields_ = [("weights", C.c_float * 6), ("temperature", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
                 ("losses", C.c_void_p)] + (_GUARD_FIELDS if GUARD_ABI else []) + [
                 ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
-                ("rnc_labels_global", C.c_void_p), ("rnc_row0", C.c_int32 * 2),
+                ("rnc_labels_global", C.c_void_p)] + (_RATES_FIELDS if RATES_ABI else []) + [("rnc_row0", C.c_int32 * 2),
                 ("contrast", C.c_int32), ("supcon_label_mode", C.c_int32), ("supcon_temperature", C.c_float),
                 ("supcon_base_temperature", C.c_float), ("distill", C.c_int32)]
 
@@ -434,6 +458,10 @@ _SIGS = {
     "sdumc_rnc_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "sdumc_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "sdumc_adam_step_rates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(RateSeg), C.c_int32,
+                                        C.c_void_p]),
+    "sdumc_zero_segments": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(RateSeg), C.c_int32, C.c_void_p]),
     "sdumc_adam_multi": (C.c_int, [C.POINTER(AdamSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sdumc_copy2d": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

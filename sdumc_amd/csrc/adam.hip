@@ -11,6 +11,7 @@
 // The bias corrections are derived on the device (in double, like torch's Python-side doubles) so a
 // captured hipGraph replays with the right step count.
 #include "common.h"
+#include <string.h>
 
 namespace {
 
@@ -26,9 +27,12 @@ __global__ void adam_hyper_kernel(float* hyper, double beta1, double beta2) {
 __device__ __forceinline__ void adam_update(float& p, const float g, float& m, float& v, const float step_size,
                                             const float bc2_sqrt, const float beta1, const float beta2, const float eps,
                                             const float wd, const float gscale) {
-  const float ge = g * gscale + wd * p;
+  // (the two sums of two products name the product that is fused: which one the compiler contracts is otherwise its choice per
+  //  kernel -- a wd held in a vector register made it the other one -- and the kernels of this file promise each other's bits.
+  //  Written so that adam_kernel and adam_multi_kernel keep the instruction streams they had with `g * gscale + wd * p`.)
+  const float ge = __builtin_fmaf(gscale, g, wd * p);
   m = m + (ge - m) * (1.f - beta1);
-  v = v * beta2 + (1.f - beta2) * ge * ge;
+  v = __builtin_fmaf(v, beta2, (1.f - beta2) * ge * ge);
   p = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
 }
 
@@ -128,6 +132,157 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sdumc_adam_table 
   }
 }
 
+// Per-tensor learning rates, decay and frozen tensors (sdumc_adam_step_rates): adam_kernel's launch over the flat bucket, with each
+// element's tensor found through a segment table that travels in the kernel arguments.  The table is a kernel argument, so a lookup
+// with a wave-uniform index is a scalar load.
+struct rates_table {
+  sdumc_rate_seg seg[SDUMC_RATES_MAX_SEGS];
+  int32_t nseg;
+};
+__device__ __forceinline__ int64_t seg_end(const rates_table& tb, int s) { return tb.seg[s].offset + tb.seg[s].n; }
+// the first segment that ends behind element e (nseg: none does): e lies in it, or in the padding in front of it
+__device__ __forceinline__ int first_seg_behind(const rates_table& tb, int64_t e) {
+  int lo = 0, hi = tb.nseg;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (seg_end(tb, mid) > e) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// 16 bytes of ONE tensor (or of padding): adam_kernel's vector path
+__device__ __forceinline__ void adam_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, const int64_t e0, const float step_size, const float bc2_sqrt,
+                                             const float beta1, const float beta2, const float eps, const float wd,
+                                             const float gscale) {
+  f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
+  const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
+  f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
+  f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float pe = pp[e], me = mm[e], ve = vv[e];
+    adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    pp[e] = pe; mm[e] = me; vv[e] = ve;
+  }
+  *reinterpret_cast<f32x4*>(p + e0) = pp;
+  *reinterpret_cast<f32x4*>(m + e0) = mm;
+  *reinterpret_cast<f32x4*>(v + e0) = vv;
+}
+// ONE element, on the per-element path.  s: the first segment that ends behind some element at or in front of t; moved on to t's.
+// An element of no segment (alignment padding) gets the default update; one of a frozen segment is neither read nor written.
+__device__ __forceinline__ void adam_rates_one(const rates_table& tb, int& s, const int64_t t, float* __restrict__ p,
+                                               const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                               const float step_size, const float bc2_sqrt, const float beta1, const float beta2,
+                                               const float eps, const float wd, const float gscale) {
+  while (s < tb.nseg && seg_end(tb, s) <= t) ++s;
+  float ss = step_size, w = wd;
+  if (s < tb.nseg && tb.seg[s].offset <= t) {
+    if (tb.seg[s].frozen) return;
+    ss = step_size * tb.seg[s].lr_scale;
+    w = wd * tb.seg[s].wd_scale;
+  }
+  adam_update(p[t], g[t], m[t], v[t], ss, bc2_sqrt, beta1, beta2, eps, w, gscale);
+}
+
+// Thread i owns the 16-byte group [4 i, 4 i + 4) of the bucket, as in adam_kernel.  A wave whose 256 elements lie inside one segment
+// (all but a handful: the tensors are thousands of elements long) finds it with a scalar binary search and takes its scales from
+// scalar registers; a frozen segment's waves leave without touching memory.  In a wave that meets a boundary every lane walks on from
+// the wave's segment to its own: a group inside one segment (or inside padding) still moves 16 bytes, a group that straddles a boundary
+// -- segments start at any residue mod 4 -- goes element by element.  Holds and scalar tail are adam_kernel's.
+__global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, int64_t n4, int64_t n,
+                                                         const float* hyper, float beta1, float beta2, float eps, float wd,
+                                                         float gscale, uint32_t* rng, uint32_t rng_inc, const sdumc_total_loss tl,
+                                                         const rates_table tb) {
+  const float step_size = hyper[2], bc2_sqrt = hyper[3];
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool poisoned = tl.chain_err != nullptr && *tl.chain_err != 0;                   // (see adam_kernel)
+  const bool hold = poisoned || (tl.guard != nullptr && tl.guard[3] != 0.f);
+  // the wave's first element and the first segment that ends behind it: scalar registers, scalar loads
+  const int64_t w0 = 4 * ((int64_t)blockIdx.x * blockDim.x + __builtin_amdgcn_readfirstlane((int)threadIdx.x));
+  const int s0 = first_seg_behind(tb, w0);
+  if (i < n4 && !hold) {
+    const int64_t e0 = 4 * i;
+    if (s0 < tb.nseg && tb.seg[s0].offset <= w0 && w0 + 256 <= seg_end(tb, s0)) {        // (wave-uniform)
+      if (!tb.seg[s0].frozen)
+        adam_update4(p, g, m, v, e0, step_size * tb.seg[s0].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s0].wd_scale, gscale);
+    } else {
+      int s = s0;
+      while (s < tb.nseg && seg_end(tb, s) <= e0) ++s;
+      const bool padding = s == tb.nseg || tb.seg[s].offset >= e0 + 4;                   // the group meets no segment
+      if (padding) {
+        adam_update4(p, g, m, v, e0, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      } else if (tb.seg[s].offset <= e0 && e0 + 4 <= seg_end(tb, s)) {                   // ... lies inside one
+        if (!tb.seg[s].frozen)
+          adam_update4(p, g, m, v, e0, step_size * tb.seg[s].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s].wd_scale, gscale);
+      } else {                                                                           // ... straddles a boundary
+        for (int e = 0; e < 4; ++e) adam_rates_one(tb, s, e0 + e, p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      }
+    }
+  }
+  // scalar tail, as adam_kernel's
+  if (i == 0) {
+    if (rng) rng[2] += rng_inc;
+    if (tl.losses) {
+      float* L = tl.losses;
+      L[0] = tl.w[0] * L[1] + tl.w[1] * L[2] + tl.w[2] * L[3] + tl.w[3] * L[4] + tl.w[4] * L[5] + tl.w[5] * L[6];
+      L[7] = 0.f;
+      if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
+    }
+    if (!hold && n4 * 4 < n) {
+      int s = first_seg_behind(tb, n4 * 4);
+      for (int64_t t = n4 * 4; t < n; ++t) adam_rates_one(tb, s, t, p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    }
+  }
+}
+
+// +0.0f over the frozen segments of a bucket (sdumc_zero_segments).  The launch's table holds the frozen segments only; workgroup b
+// finds its (segment, chunk) in the running workgroup counts, as adam_multi_kernel does.  A segment's whole 16-byte groups are split
+// into chunks of ZERO_CHUNK elements, 16 bytes per store; its first workgroup also writes the up to three elements in front of the
+// first whole group and behind the last, one float per lane.
+constexpr int ZERO_CHUNK = 4096;
+struct zero_table {
+  int64_t offset[SDUMC_RATES_MAX_SEGS], n[SDUMC_RATES_MAX_SEGS];
+  uint32_t block_end[SDUMC_RATES_MAX_SEGS];
+  int32_t nseg;
+};
+__host__ __device__ inline int64_t zero_groups_begin(int64_t first) { return (first + 3) & ~(int64_t)3; }
+__global__ __launch_bounds__(256) void zero_segments_kernel(float* __restrict__ buf, const zero_table tb) {
+  const uint32_t b = blockIdx.x;
+  int lo = 0, hi = tb.nseg - 1;
+  while (lo < hi) {                                         // first segment with block_end > b
+    const int mid = (lo + hi) >> 1;
+    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  const int64_t k = b - (lo > 0 ? tb.block_end[lo - 1] : 0u);
+  const int64_t first = tb.offset[lo], last = first + tb.n[lo];
+  const int64_t a = zero_groups_begin(first), z = last & ~(int64_t)3;      // the whole groups: [a, z), none when a >= z
+  const int tid = threadIdx.x;
+  const int64_t c1 = a + (k + 1) * ZERO_CHUNK < z ? a + (k + 1) * ZERO_CHUNK : z;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t e = a + k * ZERO_CHUNK + 4 * tid; e < c1; e += 4 * 256) *reinterpret_cast<f32x4*>(buf + e) = zero;
+  if (k == 0) {
+    const int64_t head_end = a < last ? a : last;           // [first, head_end): in front of the first whole group
+    if (first + tid < head_end) buf[first + tid] = 0.f;
+    const int64_t tail = z > head_end ? z : head_end;       // [tail, last): behind the last one
+    if (tail + tid < last) buf[tail + tid] = 0.f;
+  }
+}
+
+// what both entries ask of a table: 1 .. SDUMC_RATES_MAX_SEGS segments, ascending, disjoint, inside [0, n), scales finite and >= 0
+int rates_table_check(const sdumc_rate_seg* segs, int32_t nseg, int64_t n) {
+  if (!segs || nseg < 1 || nseg > SDUMC_RATES_MAX_SEGS || n <= 0) return SDUMC_EINVAL;
+  int64_t end = 0;
+  for (int32_t i = 0; i < nseg; ++i) {
+    const sdumc_rate_seg& s = segs[i];
+    if (s.n < 1 || s.n > n || s.offset < end || s.offset > n - s.n) return SDUMC_EINVAL;
+    if (!(s.lr_scale >= 0.f) || !(s.wd_scale >= 0.f) || s.lr_scale > 3.402823466e38f || s.wd_scale > 3.402823466e38f)
+      return SDUMC_EINVAL;
+    end = s.offset + s.n;
+  }
+  return SDUMC_OK;
+}
+
 }  // namespace
 
 extern "C" int sdumc_adam_hyper_(float* hyper, float beta1, float beta2, void* stream) {
@@ -169,6 +324,79 @@ extern "C" int sdumc_adam_step(float* param, const float* grad, float* exp_avg, 
   if (rc) return rc;
   return sdumc_adam_apply_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
                            0u, nullptr, stream);
+}
+
+extern "C" int sdumc_adam_rates_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
+                                       const sdumc_rate_seg* segs, int32_t nseg) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return SDUMC_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+    return SDUMC_EINVAL;
+  return rates_table_check(segs, nseg, n);
+}
+
+extern "C" int sdumc_adam_apply_rates_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                       const float* hyper, float beta1, float beta2, float eps, float weight_decay,
+                                       float grad_scale, uint32_t* rng_state, uint32_t rng_inc, const sdumc_total_loss* total,
+                                       const sdumc_rate_seg* segs, int32_t nseg, void* stream) {
+  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 128 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!hyper) return SDUMC_EINVAL;
+  const int rc = sdumc_adam_rates_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg);
+  if (rc) return rc;
+  sdumc_total_loss tl;
+  tl.losses = nullptr;
+  tl.chain_err = nullptr;
+  tl.guard = nullptr;
+  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
+  if (total) tl = *total;
+  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();      // (as sdumc_adam_apply_)
+  rates_table tb;
+  memset(&tb, 0, sizeof(tb));
+  tb.nseg = nseg;
+  for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
+  const int64_t n4 = n / 4;
+  const int64_t threads = n4 > 0 ? n4 : 1;
+  hipLaunchKernelGGL(adam_rates_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
+                     exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb);
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
+}
+
+extern "C" int sdumc_adam_step_rates(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper,
+                                     float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                     const sdumc_rate_seg* segs, int32_t nseg, void* stream) {
+  if (!hyper) return SDUMC_EINVAL;
+  int rc = sdumc_adam_rates_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg);      // (before the step count advances)
+  if (rc) return rc;
+  rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
+  if (rc) return rc;
+  return sdumc_adam_apply_rates_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
+                                 0u, nullptr, segs, nseg, stream);
+}
+
+extern "C" int sdumc_zero_segments(float* buf, int64_t n, const sdumc_rate_seg* segs, int32_t nseg, void* stream) {
+  static_assert(sizeof(zero_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!buf || (reinterpret_cast<uintptr_t>(buf) & 15)) return SDUMC_EINVAL;
+  const int rc = rates_table_check(segs, nseg, n);
+  if (rc) return rc;
+  zero_table tb;
+  memset(&tb, 0, sizeof(tb));
+  uint64_t blocks = 0;
+  for (int32_t i = 0; i < nseg; ++i) {
+    if (!segs[i].frozen) continue;
+    const int64_t a = zero_groups_begin(segs[i].offset), z = (segs[i].offset + segs[i].n) & ~(int64_t)3;
+    const int64_t chunks = z > a ? (z - a + ZERO_CHUNK - 1) / ZERO_CHUNK : 0;
+    blocks += (uint64_t)(chunks > 0 ? chunks : 1);
+    if (blocks > 0x7fffffffull) return SDUMC_EINVAL;      // (one launch's grid)
+    tb.offset[tb.nseg] = segs[i].offset;
+    tb.n[tb.nseg] = segs[i].n;
+    tb.block_end[tb.nseg++] = (uint32_t)blocks;
+  }
+  if (tb.nseg == 0) return SDUMC_OK;
+  for (int32_t i = tb.nseg; i < SDUMC_RATES_MAX_SEGS; ++i) tb.block_end[i] = (uint32_t)blocks;
+  hipLaunchKernelGGL(zero_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), buf, tb);
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
 }
 
 extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,

@@ -2250,6 +2250,7 @@ struct BwdSchedule : UttPath {     // chain: 12'-9' and 7'-3' as one launch each
     bool dw_on_lane3 = false;      // per-layer key-projection dW: on lane 3, off the modality's dz -> dX -> mask-sum -> frame dW chain
     bool dx_sum = false;           // the rows launches add keep . dxd straight into dx: no mask-sum launch
     bool frame_dw_grouped = false; // frame_dim_reshape dW: a problem of the grouped launch behind the join (else per stream)
+    bool frame_dw_skip = false;    // ... or not computed at all: weight and bias are frozen (sdumc_step_cfg.rates; the fused step only)
     int k1 = 2;                    // the sites [0, k1) are left for the frame-level pass
   } mod[3];
   // the input-feature gradients (sdumc_net_grads.d_audio / d_text / d_video): set by plan_feature_grads for sdumc_net_backward and
@@ -2261,7 +2262,8 @@ struct BwdSchedule : UttPath {     // chain: 12'-9' and 7'-3' as one launch each
 };
 // launches nothing, records no event, touches no stream: a function of dims, io, the context's options, the process-wide switches
 // (environment, setters) and whether the caller's stream is under capture (c.capturing, asked once by init_lanes)
-BwdSchedule plan_backward(const Ctx& c, const UttPath& utt, int phases) {
+// frozen_frame_dw: bit m = frame_dim_reshape_m's weight and bias are both frozen -- set by sdumc_train_step alone
+BwdSchedule plan_backward(const Ctx& c, const UttPath& utt, int phases, unsigned frozen_frame_dw = 0) {
   BwdSchedule s;
   static_cast<UttPath&>(s) = utt;
   s.utterance = (phases & 1) != 0;
@@ -2315,6 +2317,7 @@ BwdSchedule plan_backward(const Ctx& c, const UttPath& utt, int phases) {
     M.frame_dw_grouped = s.dw_grouped && (c.h() || ((m == 0 ? c.d.da : (m == 1 ? c.d.dt : c.d.dv)) & 3) == 0);
     for (int st = 0; st < (m == 1 ? c.pl.S : 1); ++st)
       if (reinterpret_cast<uintptr_t>(feat_in(c, m, st)) & 15) M.frame_dw_grouped = false;
+    M.frame_dw_skip = ((frozen_frame_dw >> m) & 1u) != 0;
     if (!M.frame_dw_grouped && c.io.row_map[0]) s.rc = SDUMC_EINVAL;      // (only the grouped launch fetches its rows through a map
                                                                           //  -- in fp32 storage its split-arithmetic kernel: below)
     any_early = any_early || M.early;
@@ -2737,12 +2740,12 @@ int bwd_frame(const Ctx& c, const BwdSchedule& sch, const hipEvent_t* early_done
         RET(sdumc_dropsum_bwd(&ds, c.st));
       }
       if (s == 0) mark(c.st, 15 + 5 * m);
-      if (!M.frame_dw_grouped) RET(frame_dw_per_layer(c, m, s));
+      if (!M.frame_dw_grouped && !M.frame_dw_skip) RET(frame_dw_per_layer(c, m, s));
     }
     // (measured and dropped, round 5: the text slot's frame dW -- its dx is final long before audio's -- as a launch of its own on
     //  text's lane, beside the other modalities' dX launches: 1.425-1.431 against 1.390-1.395 ms; a persistent launch in the middle
     //  of the backward holds the CUs the dX chain is waiting for)
-    if (M.frame_dw_grouped) (c.h() ? c.ggh : c.gg).push_back(frame_dw_problem(c, m));
+    if (M.frame_dw_grouped && !M.frame_dw_skip) (c.h() ? c.ggh : c.gg).push_back(frame_dw_problem(c, m));
     RET(feature_grads(c, sch, m));      // (dx of this modality is final on its lane; beside the grouped dW of lane 3)
   }
   c.use(0);
@@ -3107,8 +3110,34 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;   // before anything is launched
   if (!contrast_ok(cfg) || (cfg->contrast == SDUMC_CONTRAST_SUPCON && 2 * d->B > 2048)) return SDUMC_EINVAL;
   const StepLayout sl = step_layout(*d);
-  if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   char* base = static_cast<char*>(io->workspace);
+  // per-tensor rates (adam.hip): the segment table from the layout's own offsets; what the rates launch would refuse comes back here,
+  // like the other options' refusals before the workspace is looked at
+  sdumc_rate_seg rate_segs[SDUMC_RATES_MAX_SEGS];
+  int32_t n_rate_segs = 0;
+  bool any_frozen = false;
+  unsigned frozen_frame_dw = 0;
+  if (cfg->rates) {
+    const ParamMap& pm = build_params(d->da, d->dt, d->dv);
+    const sdumc_tensor_rates& r = *cfg->rates;
+    for (const PEntry& e : pm.table) {
+      if (!e.live) continue;
+      if (n_rate_segs >= r.n || n_rate_segs >= SDUMC_RATES_MAX_SEGS) return SDUMC_EINVAL;
+      const int i = n_rate_segs++;
+      rate_segs[i] = sdumc_rate_seg{e.off, (int64_t)e.rows * (e.cols ? e.cols : 1), r.lr_scale[i], r.wd_scale[i], r.frozen[i] ? 1 : 0};
+      any_frozen = any_frozen || r.frozen[i];
+    }
+    if (n_rate_segs != r.n) return SDUMC_EINVAL;
+    RET(sdumc_adam_rates_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, rate_segs, n_rate_segs));
+    auto frozen_at = [&](int64_t off) {
+      for (int i = 0; i < n_rate_segs; ++i)
+        if (rate_segs[i].offset == off) return rate_segs[i].frozen != 0;
+      return false;
+    };
+    for (int m = 0; m < 3; ++m)      // weight AND bias frozen: this modality's frame dW is not computed (plan_backward)
+      if (frozen_at(pm.frame[m].w) && frozen_at(pm.frame[m].b)) frozen_frame_dw |= 1u << m;
+  }
+  if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   // clipping and the non-finite guard (grad_guard.hip) are asked for through `guard`: options without it, and whatever
   // sdumc_grad_guard itself would refuse, come back before the forward is enqueued
   if (!cfg->guard && (cfg->clip_norm != 0.f || cfg->skip_nonfinite != 0 || cfg->guard_scratch)) return SDUMC_EINVAL;
@@ -3135,7 +3164,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   RET(ctx_init(c));
   c.G = g.grads;
   const FwdSchedule fs = plan_forward(c);
-  const BwdSchedule sch = plan_backward(c, fs, 3);
+  const BwdSchedule sch = plan_backward(c, fs, 3, frozen_frame_dw);
   RET(fs.rc);
   RET(sch.rc);
   mark(static_cast<hipStream_t>(stream), 0);
@@ -3151,14 +3180,22 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   tl.chain_err = sdumc_chain_cluster_err_ptr_();
   tl.guard = cfg->guard;
   for (int i = 0; i < 6; ++i) tl.w[i] = cfg->weights[i];
-  // behind the backward's final join, on the caller's stream: norm, coefficient and non-finite count of the bucket, the bucket
-  // scaled in place, and for a skipped step the step count taken back (the loss stage advanced it before a gradient existed)
+  // behind the backward's final join, on the caller's stream: a frozen tensor's gradient is +0.0f to everyone from here on -- the
+  // guard's norm, whoever reads the bucket after the step (the segments of a skipped frame dW hold whatever an earlier step left)
+  if (any_frozen) RET(sdumc_zero_segments(g.grads, (int64_t)sl.live, rate_segs, n_rate_segs, stream));
+  // ... then norm, coefficient and non-finite count of the bucket, the bucket scaled in place, and for a skipped step the step count
+  // taken back (the loss stage advanced it before a gradient existed)
   if (cfg->guard)
     RET(sdumc_grad_guard(g.grads, (int64_t)sl.live, cfg->clip_norm, cfg->skip_nonfinite, cfg->hyper, cfg->guard_scratch, cfg->guard,
                          stream));
-  RET(sdumc_adam_apply_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
-                        cfg->eps, cfg->weight_decay, 1.0f, d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr, 2u,
-                        total_pending || cfg->guard ? &tl : nullptr, stream));
+  uint32_t* rng = d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr;
+  const sdumc_total_loss* total = total_pending || cfg->guard ? &tl : nullptr;
+  if (cfg->rates)
+    RET(sdumc_adam_apply_rates_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
+                                cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, rate_segs, n_rate_segs, stream));
+  else
+    RET(sdumc_adam_apply_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
+                          cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, stream));
   mark(static_cast<hipStream_t>(stream), 10);
   return SDUMC_OK;      // (the backward's last act joined lane 3: the next batch's assembly, too, is ordered before whatever follows)
 }

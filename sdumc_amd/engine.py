@@ -63,6 +63,84 @@ class ParamLayout:
         return [n for n in self.order if self.entries[n][2]]
 
 
+class TensorRates:
+    """Per-tensor learning-rate scale, decay scale and frozen flag of the fused step (TrainStep / FusedTrainer: lr_scale=, decay_scale=,
+    freeze=), resolved ONCE on the host: torch.optim.Adam with one parameter group per tensor and one shared step count.
+    lr_scale / decay_scale: dicts {fnmatch pattern over ParamLayout's names: a finite Python number >= 0}, applied in order -- a later
+    match overrides an earlier one; freeze: patterns of the tensors that are torch's requires_grad = False.  A pattern that matches no
+    name of the layout raises; one that matches only parameters that never get a gradient is accepted and changes nothing; an entry
+    whose pattern reaches frozen tensors ONLY raises (frozen and scaled contradict each other), while a wider one ('*.bias') scales the
+    others and leaves the frozen ones among its matches frozen, their scales at 1.
+    .names / .lr_scale / .decay_scale / .frozen: one entry per live tensor, in sdumc_param_table order (layout.live_names());
+    .c: the same as the sdumc_tensor_rates every step's cfg.rates points at."""
+
+    def __init__(self, layout, lr_scale=None, decay_scale=None, freeze=None):
+        import fnmatch
+        import math
+        import numpy as np
+        self.layout = layout
+        self.names = layout.live_names()
+        n = len(self.names)
+        if n > _lib.RATES_MAX_SEGS:
+            raise _lib.SdumcError(f"TensorRates: {n} live tensors, the table holds {_lib.RATES_MAX_SEGS}")
+        index = {name: i for i, name in enumerate(self.names)}
+
+        def matches(pattern, what):
+            if not isinstance(pattern, str):
+                raise _lib.SdumcError(f"{what}: patterns are strings, not {pattern!r}")
+            hit = [name for name in layout.order if fnmatch.fnmatchcase(name, pattern)]
+            if not hit:
+                raise _lib.SdumcError(f"{what}: pattern {pattern!r} matches no parameter of the layout")
+            return [index[name] for name in hit if name in index]      # (dead parameters: accepted, nothing to scale)
+
+        self.frozen = np.zeros(n, dtype=bool)
+        if freeze is not None:
+            if isinstance(freeze, str) or not isinstance(freeze, (tuple, list)):
+                raise _lib.SdumcError(f"freeze must be a tuple or list of patterns or None, not {freeze!r}")
+            for pattern in freeze:
+                self.frozen[matches(pattern, "freeze")] = True
+
+        def scales(table, what):
+            out = np.ones(n, dtype=np.float32)
+            if table is None:
+                return out
+            if not isinstance(table, dict):
+                raise _lib.SdumcError(f"{what} must be a dict {{pattern: scale}} or None, not {table!r}")
+            for pattern, s in table.items():
+                hit = matches(pattern, what)
+                if isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or s < 0 \
+                        or not math.isfinite(C.c_float(s).value):
+                    raise _lib.SdumcError(f"{what}[{pattern!r}] must be a finite number >= 0, not {s!r}")
+                free = [i for i in hit if not self.frozen[i]]
+                if hit and not free:
+                    raise _lib.SdumcError(f"{what}[{pattern!r}] names frozen tensors only: {[self.names[i] for i in hit]} are frozen "
+                                          "AND given a scale")
+                out[free] = s
+            return out
+
+        self.lr_scale = scales(lr_scale, "lr_scale")
+        self.decay_scale = scales(decay_scale, "decay_scale")
+        self.c = _lib.TensorRates()
+        self.c.n = n
+        for i in range(n):
+            self.c.lr_scale[i], self.c.wd_scale[i], self.c.frozen[i] = float(self.lr_scale[i]), float(self.decay_scale[i]), int(self.frozen[i])
+
+    @staticmethod
+    def wanted(lr_scale, decay_scale, freeze):
+        return lr_scale is not None or decay_scale is not None or freeze is not None
+
+    def segments(self):
+        """(offset, n, lr_scale, decay_scale, frozen) per live tensor: the table ops.adam_step_rates / ops.zero_segments take"""
+        out = []
+        for i, name in enumerate(self.names):
+            off, shape, _ = self.layout.entries[name]
+            n = 1
+            for s in shape:
+                n *= s
+            out.append((off, n, float(self.lr_scale[i]), float(self.decay_scale[i]), bool(self.frozen[i])))
+        return out
+
+
 def _require_cuda(*tensors, dtypes=(torch.float32,)):
     for t in tensors:
         if t is None:
@@ -412,8 +490,17 @@ class TrainStep(_OptStateMixin):
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
                  bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
-                 skip_nonfinite=False):
-        """clip_norm (None or a positive number) / skip_nonfinite: gradient-norm clipping and the non-finite guard, on the device
+                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None):
+        """freeze / lr_scale / decay_scale (all None = today's step, launch for launch): per-tensor learning rates, decay and frozen
+        tensors -- TensorRates has the patterns and their resolution.  Tensor i is updated with lr * lr_scale_i and coupled L2
+        weight_decay * decay_scale_i (set_lr multiplies every tensor alike; lr_scale_i == 0: the parameter stays, the moments
+        advance) by ONE launch in Adam's place.  A frozen tensor is torch's requires_grad = False: parameter and both moments stay bit
+        for bit, and its segment of .grads is +0.0 to everyone who reads the bucket after the backward -- the guard's norm, the epoch
+        record.  frame_dim_reshape_m with weight and bias frozen: that modality's frame dW (at C2 the step's largest GEMM) is not
+        computed; every other frozen tensor's gradient is computed and then zeroed.  rates: a TensorRates built before (FusedTrainer
+        hands its one to every step) instead of the three.  .rates is the resolved object (None with all off).  A step with rates is
+        not captured (capture() raises).
+        clip_norm (None or a positive number) / skip_nonfinite: gradient-norm clipping and the non-finite guard, on the device
         between the backward and Adam (sdumc_grad_guard: three launches, no synchronisation).  With either on, .guard is the device
         float[4] the step writes -- the bucket's L2 norm before clipping, the coefficient min(1, clip_norm / (norm + 1e-6)) the
         bucket was scaled by in place (1 without clip_norm), its number of NaN / Inf elements, and 1 when skip_nonfinite skipped the
@@ -443,6 +530,15 @@ class TrainStep(_OptStateMixin):
         _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)      # (rejected before any device work)
         self.contrast, self.contrast_temperature, self.contrast_classes = contrast, contrast_temperature, contrast_classes
         self.layout = ParamLayout.get(dims[0], dims[1], dims[2])
+        if rates is not None and TensorRates.wanted(lr_scale, decay_scale, freeze):
+            raise _lib.SdumcError("rates= is the resolved form of freeze / lr_scale / decay_scale: give one or the other")
+        if rates is None and TensorRates.wanted(lr_scale, decay_scale, freeze):
+            rates = TensorRates(self.layout, lr_scale, decay_scale, freeze)
+        if rates is not None and (not isinstance(rates, TensorRates) or rates.layout is not self.layout):
+            raise _lib.SdumcError("rates: a TensorRates over this step's ParamLayout")
+        if rates is not None and not _lib.RATES_ABI:
+            raise _lib.SdumcError("freeze / lr_scale / decay_scale: the library named by SDUMC_LIB is from before sdumc_adam_step_rates")
+        self.rates = rates
         dev = flat_params.device
         _require_cuda(flat_params)
         self.params = flat_params
@@ -532,6 +628,8 @@ class TrainStep(_OptStateMixin):
                 self.guard, self.guard_scratch = _guard_buffers(self.layout.live, dev)
             cfg.clip_norm, cfg.skip_nonfinite = clip, skip
             cfg.guard, cfg.guard_scratch = ptr(self.guard), ptr(self.guard_scratch)
+        if rates is not None:
+            cfg.rates = C.pointer(rates.c)      # (host memory, read during every call: self.rates keeps it alive)
         self.graph = None
         goff = lib.sdumc_step_grads_offset(C.byref(self.dims))      # the same for every shape: the bucket leads the workspace
         self.grads = self.workspace[goff:goff + 4 * self.layout.live].view(torch.float32)
@@ -673,6 +771,8 @@ class TrainStep(_OptStateMixin):
         measured slower than the eager four-lane launches, which are the production path."""
         if self.guard is not None:
             raise _lib.SdumcError("capture: a step with clip_norm / skip_nonfinite is not captured (not built)")
+        if self.rates is not None:
+            raise _lib.SdumcError("capture: a step with freeze / lr_scale / decay_scale is not captured (not built)")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
@@ -810,8 +910,10 @@ class FusedTrainer:
 
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
                  inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
-                 skip_nonfinite=False, **step_kwargs):
+                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, **step_kwargs):
         """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        freeze / lr_scale / decay_scale: per-tensor learning rates, decay and frozen tensors of every step (TrainStep, TensorRates):
+        resolved once, here; .rates is the ONE TensorRates every step of the run reads (None with all three off).
         clip_norm / skip_nonfinite: gradient-norm clipping and the non-finite guard of every step (TrainStep); .guard is the run's
         ONE device float[4] {norm, coefficient, non-finite count, skipped}, rewritten by every step whatever its shape (None with
         both off); train_epoch keeps a copy per step.
@@ -833,6 +935,10 @@ class FusedTrainer:
         self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill, contrast=contrast, contrast_temperature=contrast_temperature,
                        contrast_classes=contrast_classes, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
+        self.rates = TensorRates(lay, lr_scale, decay_scale, freeze) if TensorRates.wanted(lr_scale, decay_scale, freeze) else None
+        if self.rates is not None and not _lib.RATES_ABI:
+            raise _lib.SdumcError("freeze / lr_scale / decay_scale: the library named by SDUMC_LIB is from before sdumc_adam_step_rates")
+        self.kw["rates"] = self.rates
         self.state = _RunState(flat_params, lay.live, lr, seed)     # (params, rng, adam_m, adam_v, hyper, losses)
         self.guard = None
         if clip or skip:

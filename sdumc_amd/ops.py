@@ -636,6 +636,27 @@ def adam_step(param, grad, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight
                               weight_decay, grad_scale, _st()), "sdumc_adam_step")
 
 
+def rate_segments(segments):
+    """The ctypes table of adam_step_rates / zero_segments from (offset, n, lr_scale, decay_scale, frozen) tuples.  Nothing is
+    checked here: the library refuses a bad table (and the tests hand it some)."""
+    segs = (_lib.RateSeg * max(1, len(segments)))()
+    for s, (off, n, lr_scale, wd_scale, frozen) in zip(segs, segments):
+        s.offset, s.n, s.lr_scale, s.wd_scale, s.frozen = off, n, lr_scale, wd_scale, int(bool(frozen))
+    return segs
+
+
+def adam_step_rates(param, grad, m, v, hyper, segments, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-5, grad_scale=1.0):
+    """adam_step with per-segment learning-rate scale, decay scale and frozen flag: segments = (offset, n, lr_scale, decay_scale,
+    frozen) tuples over the flat buffers, ascending and disjoint (1 .. 96 of them); elements of no segment get adam_step's update."""
+    check(lib.sdumc_adam_step_rates(ptr(param), ptr(grad), ptr(m), ptr(v), param.numel(), ptr(hyper), beta1, beta2, eps,
+                                    weight_decay, grad_scale, rate_segments(segments), len(segments), _st()), "sdumc_adam_step_rates")
+
+
+def zero_segments(buf, segments):
+    """+0.0 over the frozen segments of `buf` (the same tuples); nothing else is written."""
+    check(lib.sdumc_zero_segments(ptr(buf), buf.numel(), rate_segments(segments), len(segments), _st()), "sdumc_zero_segments")
+
+
 def adam_segments(params, grads, state_offsets):
     """The ctypes segment table of adam_multi (kept by a caller that steps the same tensors again and again)."""
     segs = (_lib.AdamSeg * max(1, len(params)))()

@@ -213,10 +213,13 @@ class DataParallelStep:
 
     def __init__(self, flat_params, B, T, dims, weights=(0.5, 0.5, 0.1, 0.7, 0.1, 0.8), lr=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=1e-5, seed=0, exact=True, backend_factory=None, bf16=False,
-                 force_collectives=False, planes=False, distill='rmse', contrast='rnc', clip_norm=None, skip_nonfinite=False):
+                 force_collectives=False, planes=False, distill='rmse', contrast='rnc', clip_norm=None, skip_nonfinite=False,
+                 freeze=None, lr_scale=None, decay_scale=None):
         import collections
         import inspect
         from ._lib import SdumcError, contrast_code
+        if freeze is not None or lr_scale is not None or decay_scale is not None:      # the fused single-GPU step's (engine.TensorRates)
+            raise SdumcError("DataParallelStep: freeze / lr_scale / decay_scale are not built under data parallelism (single-GPU steps only)")
         if clip_norm is not None or skip_nonfinite:      # the guard belongs behind the all-reduce, on the reduced bucket: not built
             raise SdumcError("DataParallelStep: clip_norm / skip_nonfinite are not built under data parallelism (single-GPU steps only)")
         contrast_code(contrast)
