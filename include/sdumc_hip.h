@@ -731,6 +731,38 @@ int sdumc_adam_step_rates(float* param, const float* grad, float* exp_avg, float
  * alike. */
 int sdumc_zero_segments(float* buf, int64_t n, const sdumc_rate_seg* segs, int32_t nseg, void* stream);
 
+/* Averaged weights: an exponential moving average (EMA) of the parameters, kept by the launch that updates them.
+ * sdumc_adam_step (segs NULL and nseg 0) or sdumc_adam_step_rates (a table) plus the average `ema` [n]: param, both moments and hyper
+ * get those calls' bits, and per element, with a = the average and p = the parameter AFTER this step's update (taken from its
+ * register, not re-read), torch.lerp(a, p, w)'s own rule in fp32:
+ *     w <  0.5:  a' = a + w * (p - a)              w >= 0.5:  a' = p - (p - a) * (1 - w)
+ * (the product fused into the sum; with w = 0.25, 0.5 or 1 it is exact and a' is torch.lerp's, bit for bit).
+ * w = (float)(1 - d_eff), computed on the device in double and rounded once; d_eff = ema_decay, or with ema_warmup != 0
+ * min(ema_decay, (1 + t) / (10 + t)) with t = hyper[1] after this step's increment (the timm / torch-ema warm-up).  ema_decay == 0:
+ * the average holds the parameters' bits.  There is no bias correction: start the average as a copy of the parameters.
+ * The average follows the parameter on every path: 16-byte groups where the parameter moves in them, the scalar tail (n % 4), the
+ * per-element path at segment boundaries.  Wherever the parameter is not written the average is neither read nor written: a step
+ * that is held (the clustered kernels' error word is set), frozen segments.  An lr_scale == 0 segment is updated by the rule.  No
+ * atomics, one fixed order: the same bits on every run.
+ * SDUMC_EINVAL before anything is launched and before the step count advances: what those two calls refuse (segs NULL with
+ * nseg != 0 and the reverse included), ema NULL, not 16-byte aligned or overlapping param[0 .. n), ema_decay outside [0, 1] or NaN. */
+int sdumc_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper, float beta1,
+                        float beta2, float eps, float weight_decay, float grad_scale, const sdumc_rate_seg* segs, int32_t nseg,
+                        float* ema, float ema_decay, int32_t ema_warmup, void* stream);
+/* The same rule over PER-PARAMETER tensors, for the loop that keeps its module (torch.optim.swa_utils.AveragedModel's multi_avg_fn;
+ * sdumc_amd/optim.py): segment i is ema[0 .. n) <- lerp(ema, param, weight) with the weight given (1 - decay).  The table travels in
+ * the kernel arguments as sdumc_adam_multi's does: SDUMC_ADAM_MAX_SEGS segments per launch, a longer list takes further launches,
+ * chunks of SDUMC_ADAM_CHUNK elements per workgroup; a segment whose two addresses are 16-byte aligned moves 16 bytes per lane, any
+ * other one float per lane, the same bits either way.  Segments must not overlap.  Nothing synchronises.
+ * SDUMC_EINVAL before anything is launched: segs NULL, nseg <= 0, a NULL or misaligned (4 bytes) pointer, n <= 0, weight outside
+ * [0, 1] or NaN. */
+typedef struct sdumc_ema_seg {
+  float* ema;
+  const float* param;
+  int64_t n;               /* elements */
+} sdumc_ema_seg;
+int sdumc_ema_multi(const sdumc_ema_seg* segs, int32_t nseg, float weight, void* stream);
+
 /* Batch assembly from a device-resident packed feature store = the collater's padding
  * (toolkit/utils/read_data.py:139-151, :223-248; toolkit/data/feat_data.py:232-253) on the GPU:
  * out[b, t, :] = packed[start[b] + t, :] for t < len[b], zero beyond, out is [B, Tmax, d].
@@ -1454,7 +1486,17 @@ typedef struct sdumc_step_cfg {
    * dims, a scale that is negative, NaN or Inf.  (In the middle like the guard fields, which tests pin between `losses` and
    * `B_global`: behind the data-parallel pointers.) */
   const sdumc_tensor_rates* rates;
-  int32_t rnc_row0[2];   /* rows of this rank's stream-0 / stream-1 features in the gathered matrix */
+  /* Averaged weights (sdumc_adam_step_ema, which has the rule); ema NULL = the step without them, launch for launch, and ema_decay /
+   * ema_warmup must then be zero.  ema: device float[live count], 16-byte aligned, not the parameters.  The EMA form of the step's
+   * last launch (Adam's, or the rates launch with `rates`) runs in its place: no further launch, nothing on the host per step.  It
+   * takes that launch's hold -- a step the guard skipped or the clustered kernels poisoned leaves the average bit for bit alone --
+   * and with ema_warmup the weight follows the step count the guard left.  A frozen tensor's average is neither read nor written.
+   * SDUMC_EINVAL before the forward is enqueued: a misaligned or aliasing ema, ema_decay outside [0, 1] or NaN, options without
+   * ema.  (Directly behind `rates`, in front of the tail other tests pin.) */
+  float* ema;
+  float ema_decay;
+  int32_t ema_warmup;
+  int32_t rnc_row0[2];  /* rows of this rank's stream-0 / stream-1 features in the gathered matrix */
   /* The contrastive criterion over the [2B, 64] rnc rows (losses[6], weights[5]): SDUMC_CONTRAST_RNC (0 = a zeroed
    * struct) RnCLoss with `temperature`; SDUMC_CONTRAST_SUPCON SupConLoss (loss.py:143-240) with the two streams as the
    * two views of a sample, contrast_mode 'all', positives from `labels` (supcon_label_mode 0: equal labels, 1: equal

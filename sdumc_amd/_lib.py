@@ -193,13 +193,42 @@ RATES_ABI = _rates_abi()
 _RATES_FIELDS = [("rates", C.POINTER(TensorRates))]
 
 
+def _ema_abi():
+    """False only for an A/B against an older build (SDUMC_LIB, tools/ema_bench.py) from before sdumc_adam_step_ema: that library
+    reads sdumc_step_cfg WITHOUT the three EMA fields, which sit behind `rates` in the struct's middle, so StepCfg leaves them out for
+    it."""
+    if not os.environ.get("SDUMC_LIB") or not os.path.exists(LIB_PATH):
+        return True
+    return hasattr(C.CDLL(LIB_PATH), "sdumc_adam_step_ema")
+
+
+EMA_ABI = _ema_abi()
+_EMA_FIELDS = [("ema", C.c_void_p), ("ema_decay", C.c_float), ("ema_warmup", C.c_int32)]
+
+
+def ema_args(ema_decay, ema_warmup):
+    """TrainStep / FusedTrainer (ema_decay=, ema_warmup=) -> (on, sdumc_step_cfg.ema_decay, .ema_warmup); (False, 0.0, 0) = the step
+    without averaged weights.  ema_decay: None or a Python number in [0, 1] (no bool, no string, no tensor, no NaN); ema_warmup: a
+    bool, and only beside ema_decay."""
+    if not isinstance(ema_warmup, bool):
+        raise SdumcError(f"ema_warmup must be True or False, not {ema_warmup!r}")
+    if ema_decay is None:
+        if ema_warmup:
+            raise SdumcError("ema_warmup=True needs ema_decay")
+        return False, 0.0, 0
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay <= 1.0:      # (NaN fails both)
+        raise SdumcError(f"ema_decay must be a number in [0, 1] or None, not {ema_decay!r}")
+    return True, float(ema_decay), int(ema_warmup)
+
+
 class StepCfg(C.Structure):
     _fields_ = [("weights", C.c_float * 6), ("temperature", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
                 ("losses", C.c_void_p)] + (_GUARD_FIELDS if GUARD_ABI else []) + [
                 ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
-                ("rnc_labels_global", C.c_void_p)] + (_RATES_FIELDS if RATES_ABI else []) + [("rnc_row0", C.c_int32 * 2),
+                ("rnc_labels_global", C.c_void_p)] + (_RATES_FIELDS if RATES_ABI else []) + (
+                _EMA_FIELDS if EMA_ABI else []) + [("rnc_row0", C.c_int32 * 2),
                 ("contrast", C.c_int32), ("supcon_label_mode", C.c_int32), ("supcon_temperature", C.c_float),
                 ("supcon_base_temperature", C.c_float), ("distill", C.c_int32)]
 
@@ -370,6 +399,10 @@ class AdamSeg(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state_offset", C.c_int64), ("n", C.c_int64)]
 
 
+class EmaSeg(C.Structure):         # sdumc_ema_seg: ema[0 .. n) <- lerp(ema, param, weight)
+    _fields_ = [("ema", C.c_void_p), ("param", C.c_void_p), ("n", C.c_int64)]
+
+
 class AdamTable(C.Structure):      # one launch's kernel argument (filled by sdumc_adam_multi; mirrored for the size checks)
     _fields_ = [("seg", AdamSeg * ADAM_MAX_SEGS), ("block_end", C.c_uint32 * ADAM_MAX_SEGS), ("nseg", C.c_int32),
                 ("reserved", C.c_int32)]
@@ -462,6 +495,10 @@ _SIGS = {
                                         C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(RateSeg), C.c_int32,
                                         C.c_void_p]),
     "sdumc_zero_segments": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(RateSeg), C.c_int32, C.c_void_p]),
+    "sdumc_adam_step_ema": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(RateSeg), C.c_int32,
+                                      C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
+    "sdumc_ema_multi": (C.c_int, [C.POINTER(EmaSeg), C.c_int32, C.c_float, C.c_void_p]),
     "sdumc_adam_multi": (C.c_int, [C.POINTER(AdamSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sdumc_copy2d": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

@@ -55,13 +55,54 @@ def flat_from_adam_state(net, opt_state, device):
     return m, v, step
 
 
-def save_checkpoint(path, model, optimizer_state, epoch):
-    """`model`: the get_models wrapper (keys get the 'model.' prefix) or the bare network."""
+def _ema_state_dict(net, ema, prefix):
+    """The averaged weights under the checkpoint's own names: `ema` is the flat tensor of the fused step (laid out like the
+    parameters: ParamLayout.total) or a name -> tensor dict over the network's parameter names"""
+    lay = net._layout
+    if torch.is_tensor(ema):
+        if ema.dtype != torch.float32 or ema.numel() != lay.total:
+            raise SdumcError(f"save_checkpoint: ema must be a flat fp32 tensor of {lay.total} elements (ParamLayout.total)")
+        named = lay.views(ema.detach().reshape(-1))
+    elif isinstance(ema, dict):
+        unknown = [k for k in ema if k not in lay.entries]
+        if unknown or len(ema) != len(lay.order):
+            raise SdumcError(f"save_checkpoint: ema must name the network's parameters, all of them (unknown: {unknown[:3]}, "
+                             f"{len(ema)} of {len(lay.order)} given)")
+        named = ema
+    else:
+        raise SdumcError(f"save_checkpoint: ema must be a flat tensor or a name -> tensor dict, not {type(ema).__name__}")
+    return {prefix + k: named[k].detach().cpu().clone() for k in lay.order}
+
+
+def save_checkpoint(path, model, optimizer_state, epoch, ema=None):
+    """`model`: the get_models wrapper (keys get the 'model.' prefix) or the bare network.
+    ema: the run's averaged weights (FusedTrainer.ema_params, or a name -> tensor dict): one more key, 'ema_state_dict', under the
+    same names as 'state_dict'; load_ema reads it back.  None: the file is the one without it."""
     sd = model.state_dict()
     if not hasattr(model, "model") or hasattr(model, "_flat"):
         sd = {"model." + k: v for k, v in sd.items()}
-    torch.save({"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in sd.items()}, "optimizer": optimizer_state},
-               path)
+    ck = {"epoch": epoch, "state_dict": {k: v.detach().cpu() for k, v in sd.items()}, "optimizer": optimizer_state}
+    if ema is not None:
+        ck["ema_state_dict"] = _ema_state_dict(_net(model), ema, "model.")
+    torch.save(ck, path)
+
+
+def load_ema(path, net, legacy_pickle=False):
+    """The averaged weights of a checkpoint as the flat tensor FusedTrainer.load_ema takes (CPU, ParamLayout.total elements, bit for
+    bit what save_checkpoint(ema=) was given), or None for a file without 'ema_state_dict'.  `net`: the network or its wrapper."""
+    ck = torch.load(path, map_location="cpu", weights_only=not legacy_pickle)
+    sd = ck.get("ema_state_dict")
+    if sd is None:
+        return None
+    lay = _net(net)._layout
+    sd = {k.replace("module.", ""): v for k, v in sd.items()}
+    sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in sd.items()}
+    flat = torch.zeros(lay.total)
+    for name, view in lay.views(flat).items():
+        if name not in sd or sd[name].numel() != view.numel():
+            raise SdumcError(f"{path}: 'ema_state_dict' has no tensor of {view.numel()} elements for {name!r}")
+        view.copy_(sd[name].reshape(view.shape))
+    return flat
 
 
 def load_checkpoint(path, model, strict=False, legacy_pickle=False):

@@ -5,6 +5,8 @@
 // sdumc_adam_multi is the same update for the loop that keeps `optimizer = optim.Adam(model.parameters(), ...)` of
 // main_frame_val_text_missing.py:317 as a line of its own (sdumc_amd/optim.py): ONE launch over the per-parameter gradient
 // tensors autograd left in p.grad, found through a segment table that travels in the kernel arguments.
+// sdumc_adam_step_ema is either flat-bucket launch with the averaged weights (an EMA of the parameters) riding along: one more stream,
+// loaded and stored where the parameter is; sdumc_ema_multi is that rule alone over per-parameter tensors, for the loop above.
 //
 // hyper (device, 4 floats): [0] lr (host-written, LambdaLR value)   [1] step count t (kernel-incremented)
 //                           [2] lr / (1 - beta1^t)                  [3] sqrt(1 - beta2^t)
@@ -36,11 +38,57 @@ __device__ __forceinline__ void adam_update(float& p, const float g, float& m, f
   p = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
 }
 
+// The averaged weights (sdumc_adam_step_ema, sdumc_ema_multi): torch.lerp(a, p, w)'s own rule in fp32, with the product that is fused
+// named (as in adam_update: the kernels of this file promise each other's bits).  With w = 0.25, 0.5 or 1 the product is exact and
+// the result is torch.lerp's bit for bit; w = 1 gives p's bits.
+__device__ __forceinline__ float ema_lerp(const float a, const float p, const float w) {
+  const float d = p - a;
+  return w < 0.5f ? __builtin_fmaf(w, d, a) : __builtin_fmaf(-d, 1.f - w, p);
+}
+// w = fp32(1 - d_eff) in double, rounded once; warm-up: d_eff = min(decay, (1 + t) / (10 + t)) with t = the step count as this
+// launch sees it (hyper[1] after the step's increment).  Uniform over the launch: nothing on the host changes per step.
+__device__ __forceinline__ float ema_weight(const float* hyper, const float decay, const int warmup) {
+  double d = (double)decay;
+  if (warmup) {
+    const double t = (double)hyper[1];
+    const double dw = (1.0 + t) / (10.0 + t);
+    d = dw < d ? dw : d;
+  }
+  return (float)(1.0 - d);
+}
+
+// ONE element through memory: the scalar tail and the per-element path at segment boundaries.  EMA: the average is read where the
+// parameter is, and the lerp is fed the parameter value just computed, from its register.
+template <bool EMA>
+__device__ __forceinline__ void adam_update1(float* p, const float* g, float* m, float* v, float* a, const int64_t t,
+                                             const float step_size,
+                                             const float bc2_sqrt, const float beta1, const float beta2, const float eps,
+                                             const float wd, const float gscale, const float ew) {
+  if constexpr (EMA) {
+    float pe = p[t], me = m[t], ve = v[t];
+    const float ae = a[t];
+    adam_update(pe, g[t], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    p[t] = pe; m[t] = me; v[t] = ve;
+    a[t] = ema_lerp(ae, pe, ew);
+  } else {
+    adam_update(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+  }
+}
+
+// What an EMA instantiation takes behind the arguments of the kernel it is a form of: the average, the decay, the warm-up flag.  The
+// plain instantiations take nothing there (an empty pack), so their signatures, and they, stay what they were.
+struct ema_opts { float* a; float decay; int warmup; };
+__device__ __forceinline__ ema_opts ema_of() { return {nullptr, 0.f, 0}; }
+__device__ __forceinline__ ema_opts ema_of(float* a, float decay, int warmup) { return {a, decay, warmup}; }
+
+// adam_kernel<false> is the kernel as it always was, instruction for instruction.  adam_kernel<true, float*, float, int> is its EMA
+// form: a fifth stream `a`, loaded and stored in 16-byte groups exactly where p is, under the same hold.
+template <bool EMA, typename... E>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                    int64_t n, const float* hyper, float beta1, float beta2, float eps,
                                                    float wd, float gscale, uint32_t* rng, uint32_t rng_inc,
-                                                   const sdumc_total_loss tl) {
+                                                   const sdumc_total_loss tl, E... ea) {
   const float step_size = hyper[2], bc2_sqrt = hyper[3];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // A clustered utterance-level kernel whose spin ran into its cap finished with wrong data: the gradients of this step are
@@ -50,20 +98,28 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   // ... and a step sdumc_grad_guard skipped (non-finite gradients, guard[3]) applies nothing either; its dropout counter and its
   // total below are those of a finite step
   const bool hold = poisoned || (tl.guard != nullptr && tl.guard[3] != 0.f);
+  const ema_opts eo = ema_of(ea...);
+  float* __restrict__ a = eo.a;
+  float ew = 0.f;
+  if constexpr (EMA) ew = ema_weight(hyper, eo.decay, eo.warmup);
   if (i < n4 && !hold) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 aa;
+    if constexpr (EMA) aa = reinterpret_cast<f32x4*>(a)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float pe = pp[e], me = mm[e], ve = vv[e];
       adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
       pp[e] = pe; mm[e] = me; vv[e] = ve;
+      if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, ew);
     }
     reinterpret_cast<f32x4*>(p)[i] = pp;
     reinterpret_cast<f32x4*>(m)[i] = mm;
     reinterpret_cast<f32x4*>(v)[i] = vv;
+    if constexpr (EMA) reinterpret_cast<f32x4*>(a)[i] = aa;
   }
   // scalar tail (+ the dropout call counter: every reader of this step is ordered before this launch)
   if (i == 0) {
@@ -76,7 +132,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
     }
     for (int64_t t = n4 * 4; t < n && !hold; ++t)
-      adam_update(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      adam_update1<EMA>(p, g, m, v, a, t, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
   }
 }
 
@@ -150,30 +206,38 @@ __device__ __forceinline__ int first_seg_behind(const rates_table& tb, int64_t e
   return lo;
 }
 // 16 bytes of ONE tensor (or of padding): adam_kernel's vector path
+template <bool EMA>
 __device__ __forceinline__ void adam_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                             float* __restrict__ v, const int64_t e0, const float step_size, const float bc2_sqrt,
-                                             const float beta1, const float beta2, const float eps, const float wd,
-                                             const float gscale) {
+                                             float* __restrict__ v, float* __restrict__ a, const int64_t e0, const float step_size,
+                                             const float bc2_sqrt, const float beta1, const float beta2, const float eps,
+                                             const float wd, const float gscale, const float ew) {
   f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
   const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
   f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
   f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
+  f32x4 aa;
+  if constexpr (EMA) aa = *reinterpret_cast<f32x4*>(a + e0);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float pe = pp[e], me = mm[e], ve = vv[e];
     adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
     pp[e] = pe; mm[e] = me; vv[e] = ve;
+    if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, ew);
   }
   *reinterpret_cast<f32x4*>(p + e0) = pp;
   *reinterpret_cast<f32x4*>(m + e0) = mm;
   *reinterpret_cast<f32x4*>(v + e0) = vv;
+  if constexpr (EMA) *reinterpret_cast<f32x4*>(a + e0) = aa;
 }
 // ONE element, on the per-element path.  s: the first segment that ends behind some element at or in front of t; moved on to t's.
-// An element of no segment (alignment padding) gets the default update; one of a frozen segment is neither read nor written.
+// An element of no segment (alignment padding) gets the default update; one of a frozen segment is neither read nor written -- nor is
+// its average.
+template <bool EMA>
 __device__ __forceinline__ void adam_rates_one(const rates_table& tb, int& s, const int64_t t, float* __restrict__ p,
                                                const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                               const float step_size, const float bc2_sqrt, const float beta1, const float beta2,
-                                               const float eps, const float wd, const float gscale) {
+                                               float* __restrict__ a, const float step_size, const float bc2_sqrt, const float beta1,
+                                               const float beta2, const float eps, const float wd, const float gscale,
+                                               const float ew) {
   while (s < tb.nseg && seg_end(tb, s) <= t) ++s;
   float ss = step_size, w = wd;
   if (s < tb.nseg && tb.seg[s].offset <= t) {
@@ -181,23 +245,30 @@ __device__ __forceinline__ void adam_rates_one(const rates_table& tb, int& s, co
     ss = step_size * tb.seg[s].lr_scale;
     w = wd * tb.seg[s].wd_scale;
   }
-  adam_update(p[t], g[t], m[t], v[t], ss, bc2_sqrt, beta1, beta2, eps, w, gscale);
+  adam_update1<EMA>(p, g, m, v, a, t, ss, bc2_sqrt, beta1, beta2, eps, w, gscale, ew);
 }
 
 // Thread i owns the 16-byte group [4 i, 4 i + 4) of the bucket, as in adam_kernel.  A wave whose 256 elements lie inside one segment
 // (all but a handful: the tensors are thousands of elements long) finds it with a scalar binary search and takes its scales from
 // scalar registers; a frozen segment's waves leave without touching memory.  In a wave that meets a boundary every lane walks on from
 // the wave's segment to its own: a group inside one segment (or inside padding) still moves 16 bytes, a group that straddles a boundary
-// -- segments start at any residue mod 4 -- goes element by element.  Holds and scalar tail are adam_kernel's.
+// -- segments start at any residue mod 4 -- goes element by element.  Holds and scalar tail are adam_kernel's.  EMA
+// (adam_rates_kernel<true, float*, float, int>): the average travels with the parameter on every one of these paths;
+// adam_rates_kernel<false> is the kernel as it always was, instruction for instruction.
+template <bool EMA, typename... E>
 __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t n4, int64_t n,
                                                          const float* hyper, float beta1, float beta2, float eps, float wd,
                                                          float gscale, uint32_t* rng, uint32_t rng_inc, const sdumc_total_loss tl,
-                                                         const rates_table tb) {
+                                                         const rates_table tb, E... ea) {
   const float step_size = hyper[2], bc2_sqrt = hyper[3];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool poisoned = tl.chain_err != nullptr && *tl.chain_err != 0;                   // (see adam_kernel)
   const bool hold = poisoned || (tl.guard != nullptr && tl.guard[3] != 0.f);
+  const ema_opts eo = ema_of(ea...);
+  float* __restrict__ a = eo.a;
+  float ew = 0.f;
+  if constexpr (EMA) ew = ema_weight(hyper, eo.decay, eo.warmup);
   // the wave's first element and the first segment that ends behind it: scalar registers, scalar loads
   const int64_t w0 = 4 * ((int64_t)blockIdx.x * blockDim.x + __builtin_amdgcn_readfirstlane((int)threadIdx.x));
   const int s0 = first_seg_behind(tb, w0);
@@ -205,18 +276,21 @@ __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, 
     const int64_t e0 = 4 * i;
     if (s0 < tb.nseg && tb.seg[s0].offset <= w0 && w0 + 256 <= seg_end(tb, s0)) {        // (wave-uniform)
       if (!tb.seg[s0].frozen)
-        adam_update4(p, g, m, v, e0, step_size * tb.seg[s0].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s0].wd_scale, gscale);
+        adam_update4<EMA>(p, g, m, v, a, e0, step_size * tb.seg[s0].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s0].wd_scale,
+                          gscale, ew);
     } else {
       int s = s0;
       while (s < tb.nseg && seg_end(tb, s) <= e0) ++s;
       const bool padding = s == tb.nseg || tb.seg[s].offset >= e0 + 4;                   // the group meets no segment
       if (padding) {
-        adam_update4(p, g, m, v, e0, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+        adam_update4<EMA>(p, g, m, v, a, e0, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
       } else if (tb.seg[s].offset <= e0 && e0 + 4 <= seg_end(tb, s)) {                   // ... lies inside one
         if (!tb.seg[s].frozen)
-          adam_update4(p, g, m, v, e0, step_size * tb.seg[s].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s].wd_scale, gscale);
+          adam_update4<EMA>(p, g, m, v, a, e0, step_size * tb.seg[s].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s].wd_scale,
+                            gscale, ew);
       } else {                                                                           // ... straddles a boundary
-        for (int e = 0; e < 4; ++e) adam_rates_one(tb, s, e0 + e, p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+        for (int e = 0; e < 4; ++e)
+          adam_rates_one<EMA>(tb, s, e0 + e, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
       }
     }
   }
@@ -231,8 +305,49 @@ __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, 
     }
     if (!hold && n4 * 4 < n) {
       int s = first_seg_behind(tb, n4 * 4);
-      for (int64_t t = n4 * 4; t < n; ++t) adam_rates_one(tb, s, t, p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      for (int64_t t = n4 * 4; t < n; ++t)
+        adam_rates_one<EMA>(tb, s, t, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
     }
+  }
+}
+
+// The averaged weights of the loop that keeps the module (sdumc_ema_multi): ema_lerp over per-parameter tensors, found like
+// adam_multi_kernel's -- workgroup b's (segment, chunk of SDUMC_ADAM_CHUNK elements) in the table's running workgroup counts, 16 bytes
+// per lane where both addresses are 16-byte aligned, one float per lane elsewhere; the same bits either way.
+struct ema_table {
+  sdumc_ema_seg seg[SDUMC_ADAM_MAX_SEGS];
+  uint32_t block_end[SDUMC_ADAM_MAX_SEGS];
+  int32_t nseg;
+};
+__global__ __launch_bounds__(256) void ema_multi_kernel(const ema_table tb, const float w) {
+  const uint32_t b = blockIdx.x;
+  int lo = 0, hi = tb.nseg - 1;
+  while (lo < hi) {                                         // first segment with block_end > b
+    const int mid = (lo + hi) >> 1;
+    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  const sdumc_ema_seg sg = tb.seg[lo];
+  const uint32_t b0 = lo > 0 ? tb.block_end[lo - 1] : 0u;
+  const int64_t base = (int64_t)(b - b0) * SDUMC_ADAM_CHUNK;
+  const int64_t left = sg.n - base;
+  const int cnt = left < SDUMC_ADAM_CHUNK ? (int)left : SDUMC_ADAM_CHUNK;
+  float* __restrict__ a = sg.ema + base;
+  const float* __restrict__ p = sg.param + base;
+  const int tid = threadIdx.x;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+  if (aligned) {
+    const int e0 = 4 * tid;
+    if (e0 + 4 <= cnt) {
+      f32x4 aa = *reinterpret_cast<f32x4*>(a + e0);
+      const f32x4 pp = *reinterpret_cast<const f32x4*>(p + e0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) aa[e] = ema_lerp(aa[e], pp[e], w);
+      *reinterpret_cast<f32x4*>(a + e0) = aa;
+    } else {
+      for (int e = e0; e < cnt; ++e) a[e] = ema_lerp(a[e], p[e], w);
+    }
+  } else {
+    for (int e = tid; e < cnt; e += 256) a[e] = ema_lerp(a[e], p[e], w);
   }
 }
 
@@ -310,7 +425,7 @@ extern "C" int sdumc_adam_apply_(float* param, const float* grad, float* exp_avg
     return SDUMC_EINVAL;
   const int64_t n4 = n / 4;
   const int64_t threads = n4 > 0 ? n4 : 1;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
+  hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
                      exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
@@ -356,7 +471,7 @@ extern "C" int sdumc_adam_apply_rates_(float* param, const float* grad, float* e
   for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
   const int64_t n4 = n / 4;
   const int64_t threads = n4 > 0 ? n4 : 1;
-  hipLaunchKernelGGL(adam_rates_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
+  hipLaunchKernelGGL(adam_rates_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
                      exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
@@ -372,6 +487,110 @@ extern "C" int sdumc_adam_step_rates(float* param, const float* grad, float* exp
   if (rc) return rc;
   return sdumc_adam_apply_rates_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
                                  0u, nullptr, segs, nseg, stream);
+}
+
+// what the averaged weights ask on top of Adam's own arguments: a 16-byte aligned buffer of n floats that is not the parameters',
+// a decay in [0, 1]
+extern "C" int sdumc_adam_ema_check_(const void* param, const void* ema, int64_t n, float ema_decay) {
+  if (!param || !ema || n <= 0 || (reinterpret_cast<uintptr_t>(ema) & 15)) return SDUMC_EINVAL;
+  if (!(ema_decay >= 0.f && ema_decay <= 1.f)) return SDUMC_EINVAL;      // (NaN fails both)
+  const uintptr_t a = reinterpret_cast<uintptr_t>(ema), p = reinterpret_cast<uintptr_t>(param), bytes = (uintptr_t)n * 4u;
+  if (a < p + bytes && p < a + bytes) return SDUMC_EINVAL;               // the two ranges overlap
+  return SDUMC_OK;
+}
+
+// what sdumc_adam_apply_ema_ refuses, without a launch (sdumc_train_step and sdumc_adam_step_ema ask before anything is enqueued)
+extern "C" int sdumc_adam_ema_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
+                                          const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return SDUMC_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+    return SDUMC_EINVAL;
+  if (segs != nullptr || nseg != 0) {
+    const int rc = rates_table_check(segs, nseg, n);
+    if (rc) return rc;
+  }
+  return sdumc_adam_ema_check_(param, ema, n, ema_decay);
+}
+
+extern "C" int sdumc_adam_apply_ema_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                     const float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                     uint32_t* rng_state, uint32_t rng_inc, const sdumc_total_loss* total,
+                                     const sdumc_rate_seg* segs, int32_t nseg, float* ema, float ema_decay, int32_t ema_warmup,
+                                     void* stream) {
+  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 144 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!hyper) return SDUMC_EINVAL;
+  const bool table = segs != nullptr || nseg != 0;
+  const int rc = sdumc_adam_ema_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay);
+  if (rc) return rc;
+  sdumc_total_loss tl;
+  tl.losses = nullptr;
+  tl.chain_err = nullptr;
+  tl.guard = nullptr;
+  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
+  if (total) tl = *total;
+  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();      // (as sdumc_adam_apply_)
+  const int64_t n4 = n / 4;
+  const int64_t threads = n4 > 0 ? n4 : 1;
+  const dim3 grid((unsigned)((threads + 255) / 256));
+  const int warm = ema_warmup != 0 ? 1 : 0;
+  if (table) {
+    rates_table tb;
+    memset(&tb, 0, sizeof(tb));
+    tb.nseg = nseg;
+    for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
+    hipLaunchKernelGGL((adam_rates_kernel<true, float*, float, int>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n4, n, hyper,
+                       beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb, ema, ema_decay, warm);
+  } else {
+    hipLaunchKernelGGL((adam_kernel<true, float*, float, int>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n4, n, hyper, beta1,
+                       beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, ema, ema_decay, warm);
+  }
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
+}
+
+extern "C" int sdumc_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper,
+                                   float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                   const sdumc_rate_seg* segs, int32_t nseg, float* ema, float ema_decay, int32_t ema_warmup,
+                                   void* stream) {
+  if (!hyper) return SDUMC_EINVAL;
+  int rc = sdumc_adam_ema_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay);   // (before the count advances)
+  if (rc) return rc;
+  rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
+  if (rc) return rc;
+  return sdumc_adam_apply_ema_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u,
+                               nullptr, segs, nseg, ema, ema_decay, ema_warmup, stream);
+}
+
+extern "C" int sdumc_ema_multi(const sdumc_ema_seg* segs, int32_t nseg, float weight, void* stream) {
+  static_assert(sizeof(ema_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!segs || nseg <= 0 || !(weight >= 0.f && weight <= 1.f)) return SDUMC_EINVAL;
+  uint64_t blocks_of_launch = 0;
+  for (int32_t i = 0; i < nseg; ++i) {
+    const sdumc_ema_seg& s = segs[i];
+    if (!s.ema || !s.param || s.n <= 0 || (reinterpret_cast<uintptr_t>(s.ema) & 3) || (reinterpret_cast<uintptr_t>(s.param) & 3))
+      return SDUMC_EINVAL;
+    if (i % SDUMC_ADAM_MAX_SEGS == 0) blocks_of_launch = 0;
+    blocks_of_launch += (uint64_t)((s.n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
+    if (blocks_of_launch > 0x7fffffffull) return SDUMC_EINVAL;     // (one launch's grid)
+  }
+  for (int32_t s0 = 0; s0 < nseg; s0 += SDUMC_ADAM_MAX_SEGS) {
+    ema_table tb;
+    tb.nseg = nseg - s0 < SDUMC_ADAM_MAX_SEGS ? nseg - s0 : SDUMC_ADAM_MAX_SEGS;
+    uint32_t blocks = 0;
+    for (int32_t i = 0; i < SDUMC_ADAM_MAX_SEGS; ++i) {
+      if (i < tb.nseg) {
+        tb.seg[i] = segs[s0 + i];
+        blocks += (uint32_t)((tb.seg[i].n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
+      } else {
+        tb.seg[i] = sdumc_ema_seg{nullptr, nullptr, 0};
+      }
+      tb.block_end[i] = blocks;
+    }
+    hipLaunchKernelGGL(ema_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, weight);
+    SDUMC_CHECK_LAUNCH();
+  }
+  return SDUMC_OK;
 }
 
 extern "C" int sdumc_zero_segments(float* buf, int64_t n, const sdumc_rate_seg* segs, int32_t nseg, void* stream) {

@@ -3137,6 +3137,11 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
     for (int m = 0; m < 3; ++m)      // weight AND bias frozen: this modality's frame dW is not computed (plan_backward)
       if (frozen_at(pm.frame[m].w) && frozen_at(pm.frame[m].b)) frozen_frame_dw |= 1u << m;
   }
+  // averaged weights (adam.hip): the options belong to `ema`, and what the EMA launch would refuse comes back here too
+  if (!cfg->ema && (cfg->ema_decay != 0.f || cfg->ema_warmup != 0)) return SDUMC_EINVAL;
+  if (cfg->ema)
+    RET(sdumc_adam_ema_args_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live,
+                                   cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema, cfg->ema_decay));
   if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   // clipping and the non-finite guard (grad_guard.hip) are asked for through `guard`: options without it, and whatever
   // sdumc_grad_guard itself would refuse, come back before the forward is enqueued
@@ -3190,7 +3195,11 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
                          stream));
   uint32_t* rng = d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr;
   const sdumc_total_loss* total = total_pending || cfg->guard ? &tl : nullptr;
-  if (cfg->rates)
+  if (cfg->ema)      // the same launch with the averaged weights riding along (rate_segs: none without `rates`)
+    RET(sdumc_adam_apply_ema_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
+                              cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema,
+                              cfg->ema_decay, cfg->ema_warmup, stream));
+  else if (cfg->rates)
     RET(sdumc_adam_apply_rates_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
                                 cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, rate_segs, n_rate_segs, stream));
   else

@@ -440,6 +440,25 @@ class _OptStateMixin:
         self.hyper[1] = float(step)
         self.rng.set_call(2 * step)
 
+    ema_params = None      # with ema_decay: the averaged weights, a flat tensor laid out like .params (ParamLayout.total)
+
+    def load_ema(self, flat):
+        """Resume: installs a saved average (checkpoint.load_ema gives the flat tensor) -- ParamLayout.total elements, copied to the
+        run's device; the next step continues an uninterrupted run's average bit for bit."""
+        if self.ema_params is None:
+            raise _lib.SdumcError("load_ema: this run keeps no averaged weights (ema_decay=)")
+        if not torch.is_tensor(flat) or flat.dtype != torch.float32 or flat.numel() != self.ema_params.numel():
+            raise _lib.SdumcError(f"load_ema: expected a flat fp32 tensor of {self.ema_params.numel()} elements (ParamLayout.total)")
+        if flat.device.type not in ("cpu", "cuda") or (flat.is_cuda and flat.device != self.ema_params.device):
+            raise _lib.SdumcError(f"load_ema: the average lives on {self.ema_params.device}, not on {flat.device}")
+        self.ema_params.copy_(flat.reshape(-1))
+
+    def reset_ema(self):
+        """The average starts again from the current parameters (a copy of their bits)."""
+        if self.ema_params is None:
+            raise _lib.SdumcError("reset_ema: this run keeps no averaged weights (ema_decay=)")
+        self.ema_params.copy_(self.params)
+
 
 _NO4 = (None,) * 4
 
@@ -490,8 +509,17 @@ class TrainStep(_OptStateMixin):
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
                  bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
-                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None):
-        """freeze / lr_scale / decay_scale (all None = today's step, launch for launch): per-tensor learning rates, decay and frozen
+                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None, ema_decay=None, ema_warmup=False):
+        """ema_decay (None = today's step, launch for launch) / ema_warmup: averaged weights, an exponential moving average of the
+        parameters kept by the step's last launch (Adam's, or the rates launch) at the cost of one more read-and-write stream in it: no
+        further launch, nothing on the host per step.  .ema_params is a flat tensor laid out like the parameters (the run's, through
+        share, or this step's own), a copy of them at construction; after every update ema <- torch.lerp(ema, params, w), w = fp32(1 -
+        fp32(ema_decay)), on params[:live] -- parameters that never get a gradient keep their copy.  ema_warmup=True: the decay is
+        min(ema_decay, (1 + t) / (10 + t)), t = the step count after the step (the timm / torch-ema warm-up), derived on the device.
+        ema_decay=0: the average holds the parameters' bits.  A step the guard skips leaves the average bit for bit alone; a frozen
+        tensor's average is never touched.  load_ema / reset_ema install a saved average / start over.  A step with an average is not
+        captured (capture() raises).
+        freeze / lr_scale / decay_scale (all None = today's step, launch for launch): per-tensor learning rates, decay and frozen
         tensors -- TensorRates has the patterns and their resolution.  Tensor i is updated with lr * lr_scale_i and coupled L2
         weight_decay * decay_scale_i (set_lr multiplies every tensor alike; lr_scale_i == 0: the parameter stays, the moments
         advance) by ONE launch in Adam's place.  A frozen tensor is torch's requires_grad = False: parameter and both moments stay bit
@@ -527,6 +555,10 @@ class TrainStep(_OptStateMixin):
         if (clip or skip) and not _lib.GUARD_ABI:
             raise _lib.SdumcError("clip_norm / skip_nonfinite: the library named by SDUMC_LIB is from before sdumc_grad_guard")
         self.clip_norm, self.skip_nonfinite, self.guard = clip_norm, bool(skip), None
+        ema_on, ema_d, ema_w = _lib.ema_args(ema_decay, ema_warmup)
+        if ema_on and not _lib.EMA_ABI:
+            raise _lib.SdumcError("ema_decay: the library named by SDUMC_LIB is from before sdumc_adam_step_ema")
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_w)
         _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)      # (rejected before any device work)
         self.contrast, self.contrast_temperature, self.contrast_classes = contrast, contrast_temperature, contrast_classes
         self.layout = ParamLayout.get(dims[0], dims[1], dims[2])
@@ -630,6 +662,12 @@ class TrainStep(_OptStateMixin):
             cfg.guard, cfg.guard_scratch = ptr(self.guard), ptr(self.guard_scratch)
         if rates is not None:
             cfg.rates = C.pointer(rates.c)      # (host memory, read during every call: self.rates keeps it alive)
+        if ema_on:
+            # the run's average (share.ema_params: one tensor for every shape of a FusedTrainer) or its own, a copy of the parameters
+            self.ema_params = getattr(share, "ema_params", None)
+            if self.ema_params is None:
+                self.ema_params = flat_params.clone()
+            cfg.ema, cfg.ema_decay, cfg.ema_warmup = ptr(self.ema_params), ema_d, ema_w
         self.graph = None
         goff = lib.sdumc_step_grads_offset(C.byref(self.dims))      # the same for every shape: the bucket leads the workspace
         self.grads = self.workspace[goff:goff + 4 * self.layout.live].view(torch.float32)
@@ -773,6 +811,8 @@ class TrainStep(_OptStateMixin):
             raise _lib.SdumcError("capture: a step with clip_norm / skip_nonfinite is not captured (not built)")
         if self.rates is not None:
             raise _lib.SdumcError("capture: a step with freeze / lr_scale / decay_scale is not captured (not built)")
+        if self.ema_params is not None:
+            raise _lib.SdumcError("capture: a step with ema_decay is not captured (not built)")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
@@ -910,8 +950,11 @@ class FusedTrainer:
 
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
                  inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
-                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, **step_kwargs):
+                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False, **step_kwargs):
         """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        ema_decay / ema_warmup: averaged weights (TrainStep has the rule): .ema_params is the run's ONE average, a flat tensor laid out
+        like the parameters that every step updates whatever its shape (None when off); eval_epoch / saliency_epoch(weights='ema')
+        read it, load_ema / reset_ema install a saved one / start over.  The average is not part of train_epoch's record.
         freeze / lr_scale / decay_scale: per-tensor learning rates, decay and frozen tensors of every step (TrainStep, TensorRates):
         resolved once, here; .rates is the ONE TensorRates every step of the run reads (None with all three off).
         clip_norm / skip_nonfinite: gradient-norm clipping and the non-finite guard of every step (TrainStep); .guard is the run's
@@ -928,12 +971,17 @@ class FusedTrainer:
         _lib.distill_code(distill)
         self.distill = distill
         clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
+        ema_on = _lib.ema_args(ema_decay, ema_warmup)[0]
+        if ema_on and not _lib.EMA_ABI:
+            raise _lib.SdumcError("ema_decay: the library named by SDUMC_LIB is from before sdumc_adam_step_ema")
         _lib.contrast_cfg(_lib.StepCfg(), contrast, contrast_temperature, contrast_classes)
         self.contrast = (contrast, contrast_temperature, contrast_classes)
         _require_cuda(flat_params)
         self.params, self.dims, self.max_cached = flat_params, tuple(dims), max(1, int(max_cached))
         self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill, contrast=contrast, contrast_temperature=contrast_temperature,
                        contrast_classes=contrast_classes, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
+        if ema_on:      # (off: the steps are built with the keywords they always were)
+            self.kw.update(ema_decay=ema_decay, ema_warmup=ema_warmup)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         self.rates = TensorRates(lay, lr_scale, decay_scale, freeze) if TensorRates.wanted(lr_scale, decay_scale, freeze) else None
         if self.rates is not None and not _lib.RATES_ABI:
@@ -944,6 +992,8 @@ class FusedTrainer:
         if clip or skip:
             self.guard, self.state.guard_scratch = _guard_buffers(lay.live, flat_params.device)
         self.state.guard = self.guard
+        if ema_on:
+            self.state.ema_params = flat_params.clone()      # the average starts as a copy: no bias correction exists
         self._steps = {}          # shape -> TrainStep, insertion order = recency
         self.arena = None
         self._arena_kw = dict(bf16=step_kwargs.get("bf16", False), sets=sets, planes=planes,
@@ -989,6 +1039,27 @@ class FusedTrainer:
 
     def optimizer_state(self):
         return self.state.optimizer_state()
+
+    @property
+    def ema_params(self):
+        """the run's averaged weights (ema_decay=): a flat tensor laid out like the parameters; None when off"""
+        return self.state.ema_params
+
+    def load_ema(self, flat):
+        self.state.load_ema(flat)
+
+    def reset_ema(self):
+        self.state.reset_ema()
+
+    def _weights(self, weights, what):
+        """the flat tensor eval_epoch / saliency_epoch(weights=) read: 'params' the trainer's parameters, 'ema' its averaged weights"""
+        if weights == "params":
+            return self.params
+        if weights != "ema":
+            raise _lib.SdumcError(f"{what}: weights must be 'params' or 'ema', not {weights!r}")
+        if self.ema_params is None:
+            raise _lib.SdumcError(f"{what}: weights='ema' on a trainer without averaged weights (ema_decay=)")
+        return self.ema_params
 
     def _launch(self, ts, next_step=None, prefetch=None):
         # keep-bits for a next step only when its shape is known (run_epoch) or has been repeating (a static-shape loader)
@@ -1143,29 +1214,36 @@ class FusedTrainer:
             r.grads, r.n_grads, r.scratch = ptr(ts.grads), ts.grads.numel(), ptr(rec.scratch)
         return r
 
-    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False):
+    def eval_epoch(self, store, batches, key_padding=False, embeddings=False, out=None, attention=False, weights="params"):
         """One evaluation pass (main :151-166: both streams, eval mode) over `batches` of `store` with the trainer's parameters, in its
         storage mode and with its inplace / planes choices -> evaluate.EvalResult in store order.  Evaluation owns its memory
         (evaluate.Evaluator, made on first use and kept): it touches nothing of the training run but reads the parameters.
-        attention=True also keeps the per-frame attention maps (EvalResult.attention; evaluate.eval_epoch has the semantics)."""
-        if getattr(self, "_evaluator", None) is None:
+        attention=True also keeps the per-frame attention maps (EvalResult.attention; evaluate.eval_epoch has the semantics).
+        weights='ema': the same pass over the averaged weights (ema_decay=), through a second Evaluator made on first use and kept; it
+        reads the average as it is when the call runs."""
+        flat = self._weights(weights, "eval_epoch")
+        attr = "_evaluator" if weights == "params" else "_evaluator_ema"
+        if getattr(self, attr, None) is None:
             from .evaluate import Evaluator
             kw = self._arena_kw
-            self._evaluator = Evaluator(self.params, self.dims, bf16=kw["bf16"], inplace=self.inplace, planes=kw["planes"],
-                                        prefetch_workgroups=kw["prefetch_workgroups"])
-        return self._evaluator.eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out, attention=attention)
+            setattr(self, attr, Evaluator(flat, self.dims, bf16=kw["bf16"], inplace=self.inplace, planes=kw["planes"],
+                                          prefetch_workgroups=kw["prefetch_workgroups"]))
+        return getattr(self, attr).eval_epoch(store, batches, key_padding=key_padding, embeddings=embeddings, out=out, attention=attention)
 
-    def saliency_epoch(self, store, batches, key_padding=False, streams=("full", "missing"), out=None):
+    def saliency_epoch(self, store, batches, key_padding=False, streams=("full", "missing"), out=None, weights="params"):
         """One saliency pass (saliency.saliency_epoch has the semantics) over `batches` of `store` with the trainer's parameters and its
         inplace / planes choices -> saliency.SaliencyResult in store order: per stream and modality the gradient x input and the gradient
         norm of the eval-mode prediction per frame.  Like eval_epoch it owns its memory (saliency.Saliency, made on first use and
-        kept) and only reads the parameters.  fp32 storage only: a bf16-storage trainer raises."""
-        if getattr(self, "_saliency", None) is None:
+        kept) and only reads the parameters.  fp32 storage only: a bf16-storage trainer raises.
+        weights='ema': the same pass over the averaged weights (ema_decay=), through a second Saliency made on first use and kept."""
+        flat = self._weights(weights, "saliency_epoch")
+        attr = "_saliency" if weights == "params" else "_saliency_ema"
+        if getattr(self, attr, None) is None:
             from .saliency import Saliency
             kw = self._arena_kw
-            self._saliency = Saliency(self.params, self.dims, bf16=kw["bf16"], inplace=self.inplace, planes=kw["planes"],
-                                      prefetch_workgroups=kw["prefetch_workgroups"])
-        return self._saliency.saliency_epoch(store, batches, key_padding=key_padding, streams=streams, out=out)
+            setattr(self, attr, Saliency(flat, self.dims, bf16=kw["bf16"], inplace=self.inplace, planes=kw["planes"],
+                                         prefetch_workgroups=kw["prefetch_workgroups"]))
+        return getattr(self, attr).saliency_epoch(store, batches, key_padding=key_padding, streams=streams, out=out)
 
     def step(self, audio, text, video, feat4, labels, lengths=None):
         """One optimisation step on one batch of any shape; returns the device loss vector

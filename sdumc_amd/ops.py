@@ -677,6 +677,33 @@ def adam_multi(params, grads, m, v, state_offsets, hyper, beta1=0.9, beta2=0.999
                                grad_scale, _st()), "sdumc_adam_multi")
 
 
+def adam_step_ema(param, grad, m, v, hyper, ema, ema_decay, ema_warmup=False, segments=None, beta1=0.9, beta2=0.999, eps=1e-8,
+                  weight_decay=1e-5, grad_scale=1.0):
+    """adam_step (segments None) or adam_step_rates (the same tuples) that also keeps `ema`, the averaged weights: after the update
+    ema <- torch.lerp(ema, param, w) with w = fp32(1 - ema_decay), or with ema_warmup fp32(1 - min(ema_decay, (1 + t) / (10 + t))),
+    t = the step count after this step.  Nothing is checked here: the library refuses bad arguments."""
+    segs = rate_segments(segments) if segments is not None else None
+    check(lib.sdumc_adam_step_ema(ptr(param), ptr(grad), ptr(m), ptr(v), param.numel(), ptr(hyper), beta1, beta2, eps, weight_decay,
+                                  grad_scale, segs, len(segments) if segments is not None else 0, ptr(ema), ema_decay,
+                                  int(bool(ema_warmup)), _st()), "sdumc_adam_step_ema")
+
+
+def ema_segments(emas, params):
+    """The ctypes segment table of ema_multi (kept by a caller that averages the same tensors again and again)."""
+    segs = (_lib.EmaSeg * max(1, len(emas)))()
+    for s, a, p in zip(segs, emas, params):
+        s.ema, s.param, s.n = a.data_ptr(), p.data_ptr(), a.numel()
+    return segs
+
+
+def ema_multi(emas, params, weight, segs=None):
+    """emas[i] <- torch.lerp(emas[i], params[i], weight) over per-parameter tensors in one launch (96 tensors per launch; contiguous
+    fp32 at any 4-byte-aligned address).  weight = 1 - decay, as an fp32 value in [0, 1]."""
+    if segs is None:
+        segs = ema_segments(emas, params)
+    check(lib.sdumc_ema_multi(segs, len(emas), weight, _st()), "sdumc_ema_multi")
+
+
 def scatter_segments(srcs, dsts):
     """The ctypes segment table of scatter_rows_multi: srcs[k] [rows_k, ...] -> dsts[k] [N_k, ...], both contiguous fp32 with the same
     row width (kept by a caller that scatters the same tensors again and again)."""

@@ -75,6 +75,55 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     return guard[0]
 
 
+_ema_cache = {}       # the last tensor set's pointer tuple -> segment table
+
+
+@torch.no_grad()
+def ema_update_(ema_params, params, decay):
+    """ema_params[i] <- torch.lerp(ema_params[i], params[i], 1 - decay) for every pair, as ONE launch per 96 tensors
+    (sdumc_ema_multi): what torch.optim.swa_utils.get_ema_multi_avg_fn(decay) does with torch._foreach_lerp_, with the weight
+    fp32(1 - decay) rounded once from the double.  Nothing synchronises; the tensors may be views at any element offset of a larger
+    one.  decay: a Python number in [0, 1].  There is no fallback: dense contiguous fp32 CUDA tensors of equal sizes on one device, or
+    SdumcError."""
+    on, d, _ = _lib.ema_args(decay, False)
+    if not on:
+        raise SdumcError("sdumc_amd.optim.ema_update_: decay must be a number in [0, 1]")
+    ema_params, params = list(ema_params), list(params)
+    if len(ema_params) != len(params):
+        raise SdumcError(f"sdumc_amd.optim.ema_update_: {len(ema_params)} averaged tensors for {len(params)} parameters")
+    if not params:
+        return
+    dev = ema_params[0].device
+    for a, p in zip(ema_params, params):
+        for t in (a, p):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.is_sparse or t.dtype != torch.float32 or not t.is_contiguous() \
+                    or t.device != dev:
+                raise SdumcError("sdumc_amd.optim.ema_update_: expected dense contiguous fp32 CUDA tensors on one device (there is "
+                                 "no fallback)")
+        if a.numel() != p.numel() or a.numel() == 0:
+            raise SdumcError(f"sdumc_amd.optim.ema_update_: an averaged tensor of {a.numel()} elements for a parameter of {p.numel()}")
+    key = (dev,) + tuple(t.data_ptr() for t in ema_params) + tuple(t.data_ptr() for t in params) + tuple(t.numel() for t in params)
+    with torch.cuda.device(dev):
+        segs = _ema_cache.get(key)
+        if segs is None:
+            _ema_cache.clear()
+            segs = _ema_cache[key] = ops.ema_segments(ema_params, params)
+        ops.ema_multi(ema_params, params, 1.0 - d, segs=segs)
+
+
+def get_ema_multi_avg_fn(decay=0.999):
+    """torch.optim.swa_utils.get_ema_multi_avg_fn with ema_update_ inside:
+    AveragedModel(model, multi_avg_fn=sdumc_amd.optim.get_ema_multi_avg_fn(0.999)) makes its whole update one launch."""
+    on, d, _ = _lib.ema_args(decay, False)
+    if not on:
+        raise SdumcError("sdumc_amd.optim.get_ema_multi_avg_fn: decay must be a number in [0, 1]")
+
+    def ema_update(ema_param_list, current_param_list, _num_averaged):
+        ema_update_(ema_param_list, current_param_list, d)
+
+    return ema_update
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
                  maximize=False, capturable=False, differentiable=False, fused=None):

@@ -214,10 +214,12 @@ class DataParallelStep:
     def __init__(self, flat_params, B, T, dims, weights=(0.5, 0.5, 0.1, 0.7, 0.1, 0.8), lr=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=1e-5, seed=0, exact=True, backend_factory=None, bf16=False,
                  force_collectives=False, planes=False, distill='rmse', contrast='rnc', clip_norm=None, skip_nonfinite=False,
-                 freeze=None, lr_scale=None, decay_scale=None):
+                 freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False):
         import collections
         import inspect
         from ._lib import SdumcError, contrast_code
+        if ema_decay is not None or ema_warmup:      # the fused single-GPU step's (TrainStep: the EMA form of its last launch)
+            raise SdumcError("DataParallelStep: ema_decay / ema_warmup are not built under data parallelism (single-GPU steps only)")
         if freeze is not None or lr_scale is not None or decay_scale is not None:      # the fused single-GPU step's (engine.TensorRates)
             raise SdumcError("DataParallelStep: freeze / lr_scale / decay_scale are not built under data parallelism (single-GPU steps only)")
         if clip_norm is not None or skip_nonfinite:      # the guard belongs behind the all-reduce, on the reduced bucket: not built
