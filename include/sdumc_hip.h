@@ -763,6 +763,29 @@ typedef struct sdumc_ema_seg {
 } sdumc_ema_seg;
 int sdumc_ema_multi(const sdumc_ema_seg* segs, int32_t nseg, float weight, void* stream);
 
+/* Decoupled weight decay: torch.optim.AdamW, or torch.optim.Adam(..., decoupled_weight_decay=True).  The decoupled form of
+ * sdumc_adam_step (segs NULL and nseg 0, ema NULL), sdumc_adam_step_rates (a table) or sdumc_adam_step_ema (an average, with or
+ * without a table): the same launches over the same bytes, and per element, under the launch's hold,
+ *     dk = (float)(1 - (lr * lr_scale) * (weight_decay * wd_scale))      on the device, in double, rounded once
+ *     p  = p * dk                                                        ONE fp32 multiply, rounded on its own
+ *     then the update of sdumc_adam_step on (p, g, m, v) with weight_decay = 0.
+ * lr = hyper[0] as the launch reads it, so whoever rewrites hyper[0] is followed without another word; lr_scale = wd_scale = 1 without
+ * a table and for elements of no segment; the four fp32 factors are multiplied in double, each pair exactly, the pairs' product
+ * rounded once.  dk is uniform over the launch, or over a segment.  The product p * dk is not contracted into the subtraction behind
+ * it: the result is, bit for bit, p.mul_(dk) followed by the coupled call with weight_decay = 0 -- and with weight_decay == 0 that
+ * call itself.  lr_scale == 0: dk == 1, the parameter stays and the moments advance.  A frozen segment is neither read nor written.
+ * grad_scale multiplies the gradient only.  The average is lerped towards the parameter after decay and update, from its register.
+ * SDUMC_EINVAL before anything is launched and before the step count advances: whatever the coupled call of the same form refuses;
+ * ema NULL with ema_decay or ema_warmup other than zero. */
+int sdumc_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper, float beta1,
+                     float beta2, float eps, float weight_decay, float grad_scale, const sdumc_rate_seg* segs, int32_t nseg,
+                     float* ema, float ema_decay, int32_t ema_warmup, void* stream);
+/* sdumc_adam_multi with that rule (lr_scale = wd_scale = 1): the same segments, launches and refusals, a kernel of its own
+ * (adamw_multi_kernel), the bits of sdumc_adamw_step over the concatenation. */
+int sdumc_adamw_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                      float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                      void* stream);
+
 /* Batch assembly from a device-resident packed feature store = the collater's padding
  * (toolkit/utils/read_data.py:139-151, :223-248; toolkit/data/feat_data.py:232-253) on the GPU:
  * out[b, t, :] = packed[start[b] + t, :] for t < len[b], zero beyond, out is [B, Tmax, d].
@@ -1454,6 +1477,11 @@ typedef struct sdumc_step_cfg {
   float weights[6];      /* full_mse, missing_mse, text_feat, text_query_feat, features, rnc (main :234-239) */
   float temperature;     /* RnCLoss temperature = 2 (loss.py:272) */
   float beta1, beta2, eps, weight_decay;   /* Adam (main :317) */
+  /* 0 (a zeroed struct) = the step as it always was, coupled L2, launch for launch; 1 = decoupled weight decay (sdumc_adamw_step,
+   * which has the rule): the decoupled form of whichever last launch the step would have made -- Adam's, the rates launch, either
+   * with the averaged weights -- with that launch's holds and scalar tail.  Anything else: SDUMC_EINVAL before the forward is
+   * enqueued.  (In the four bytes that were padding between weight_decay and labels: no other field moves, sizeof stays.) */
+  int32_t decoupled_decay;
   const float* labels;   /* [B] sentiment values of the local samples */
   float* adam_m;         /* [live count] */
   float* adam_v;         /* [live count] */

@@ -221,9 +221,32 @@ def ema_args(ema_decay, ema_warmup):
     return True, float(ema_decay), int(ema_warmup)
 
 
+def _adamw_abi():
+    """False only for an A/B against an older build (SDUMC_LIB, tools/adamw_bench.py) from before sdumc_adamw_step: that library reads
+    sdumc_step_cfg with four bytes of padding where decoupled_decay sits and would silently ignore the field, so StepCfg leaves it
+    out for it (the layout is the same either way) and decoupled_decay=True raises on the host."""
+    if not os.environ.get("SDUMC_LIB") or not os.path.exists(LIB_PATH):
+        return True
+    return hasattr(C.CDLL(LIB_PATH), "sdumc_adamw_step")
+
+
+ADAMW_ABI = _adamw_abi()
+_ADAMW_FIELDS = [("decoupled_decay", C.c_int32)]
+
+
+def decoupled_arg(decoupled_decay):
+    """TrainStep / FusedTrainer (decoupled_decay=) -> sdumc_step_cfg.decoupled_decay; a bool and nothing else."""
+    if not isinstance(decoupled_decay, bool):
+        raise SdumcError(f"decoupled_decay must be True or False, not {decoupled_decay!r}")
+    if decoupled_decay and not ADAMW_ABI:
+        raise SdumcError("decoupled_decay: the library named by SDUMC_LIB is from before sdumc_adamw_step")
+    return int(decoupled_decay)
+
+
 class StepCfg(C.Structure):
     _fields_ = [("weights", C.c_float * 6), ("temperature", C.c_float),
-                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)] + (
+                _ADAMW_FIELDS if ADAMW_ABI else []) + [
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
                 ("losses", C.c_void_p)] + (_GUARD_FIELDS if GUARD_ABI else []) + [
                 ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
@@ -499,6 +522,11 @@ _SIGS = {
                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(RateSeg), C.c_int32,
                                       C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
     "sdumc_ema_multi": (C.c_int, [C.POINTER(EmaSeg), C.c_int32, C.c_float, C.c_void_p]),
+    "sdumc_adamw_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(RateSeg), C.c_int32,
+                                   C.c_void_p, C.c_float, C.c_int32, C.c_void_p]),
+    "sdumc_adamw_multi": (C.c_int, [C.POINTER(AdamSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sdumc_adam_multi": (C.c_int, [C.POINTER(AdamSeg), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "sdumc_copy2d": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

@@ -16,9 +16,14 @@ def _net(model):
     return model.model if hasattr(model, "model") and not hasattr(model, "_flat") else model
 
 
-def adam_state_from_flat(net, adam_m, adam_v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5):
+def adam_state_from_flat(net, adam_m, adam_v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5,
+                         decoupled_weight_decay=False):
     """torch.optim.Adam.state_dict() equivalent for the fused step's flat moment buffers: parameter ids follow
-    named_parameters() order; parameters that never receive a gradient have no state entry (like torch)."""
+    named_parameters() order; parameters that never receive a gradient have no state entry (like torch).
+    decoupled_weight_decay=True (a run with decoupled_decay=True): the group says so, and torch.optim.AdamW or sdumc_amd.optim.AdamW
+    continue the run with the rule it had; moments and step count are the same either way."""
+    if not isinstance(decoupled_weight_decay, bool):
+        raise SdumcError(f"adam_state_from_flat: decoupled_weight_decay must be True or False, not {decoupled_weight_decay!r}")
     lay = net._layout
     state, ids = {}, []
     for i, name in enumerate(net._pnames):
@@ -32,7 +37,7 @@ def adam_state_from_flat(net, adam_m, adam_v, step, lr=1e-4, betas=(0.9, 0.999),
                     "exp_avg_sq": adam_v[off:off + n].view(shape).detach().cpu().clone()}
     group = {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay, "amsgrad": False,
              "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-             "decoupled_weight_decay": False, "params": ids}
+             "decoupled_weight_decay": decoupled_weight_decay, "params": ids}
     return {"state": state, "param_groups": [group]}
 
 

@@ -7,6 +7,8 @@
 // tensors autograd left in p.grad, found through a segment table that travels in the kernel arguments.
 // sdumc_adam_step_ema is either flat-bucket launch with the averaged weights (an EMA of the parameters) riding along: one more stream,
 // loaded and stored where the parameter is; sdumc_ema_multi is that rule alone over per-parameter tensors, for the loop above.
+// sdumc_adamw_step / sdumc_adamw_multi are torch.optim.AdamW's rule, decoupled weight decay, as a further form of each of these launches
+// (adam_decay_mul below has the rule); the coupled forms stay what they were, by name and by instruction.
 //
 // hyper (device, 4 floats): [0] lr (host-written, LambdaLR value)   [1] step count t (kernel-incremented)
 //                           [2] lr / (1 - beta1^t)                  [3] sqrt(1 - beta2^t)
@@ -14,6 +16,7 @@
 // captured hipGraph replays with the right step count.
 #include "common.h"
 #include <string.h>
+#include <type_traits>
 
 namespace {
 
@@ -38,6 +41,33 @@ __device__ __forceinline__ void adam_update(float& p, const float g, float& m, f
   p = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
 }
 
+// Decoupled weight decay (sdumc_adamw_step, sdumc_adamw_multi; torch.optim.AdamW): p <- p * dk in front of adam_update with no L2 term,
+//     dk = fp32(1 - (lr * lr_scale) * (weight_decay * wd_scale)),
+// the four fp32 factors multiplied in double -- each pair's product is exact there, so one rounding for the product, one for the
+// difference's conversion -- with lr = hyper[0] as the launch reads it and both scales 1 without a table.  Derived on the device, uniform
+// over the launch (over a segment with a table): nothing on the host changes per step, and set_lr is followed.
+__device__ __forceinline__ float adam_decay_factor(const float lr, const float lr_scale, const float wd, const float wd_scale) {
+  return (float)(1.0 - ((double)lr * (double)lr_scale) * ((double)wd * (double)wd_scale));
+}
+// ... and the product itself, ONE fp32 multiply rounded on its own: it must not be contracted into adam_update's last subtraction (the
+// kernels of this file promise each other's bits, and torch's p.mul_(1 - lr * wd) rounds here)
+__device__ __forceinline__ float adam_decay_mul(const float p, const float dk) {
+#pragma clang fp contract(off)
+  return p * dk;
+}
+// adam_update (DEC false: wd is the coupled L2 factor, dk is not read) or its decoupled form (DEC true: dk, and wd is not read)
+template <bool DEC>
+__device__ __forceinline__ void adam_update_d(float& p, const float g, float& m, float& v, const float step_size,
+                                              const float bc2_sqrt, const float beta1, const float beta2, const float eps,
+                                              const float wd, const float gscale, const float dk) {
+  if constexpr (DEC) {
+    p = adam_decay_mul(p, dk);
+    adam_update(p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, 0.f, gscale);
+  } else {
+    adam_update(p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+  }
+}
+
 // The averaged weights (sdumc_adam_step_ema, sdumc_ema_multi): torch.lerp(a, p, w)'s own rule in fp32, with the product that is fused
 // named (as in adam_update: the kernels of this file promise each other's bits).  With w = 0.25, 0.5 or 1 the product is exact and
 // the result is torch.lerp's bit for bit; w = 1 gives p's bits.
@@ -59,19 +89,19 @@ __device__ __forceinline__ float ema_weight(const float* hyper, const float deca
 
 // ONE element through memory: the scalar tail and the per-element path at segment boundaries.  EMA: the average is read where the
 // parameter is, and the lerp is fed the parameter value just computed, from its register.
-template <bool EMA>
+template <bool EMA, bool DEC>
 __device__ __forceinline__ void adam_update1(float* p, const float* g, float* m, float* v, float* a, const int64_t t,
                                              const float step_size,
                                              const float bc2_sqrt, const float beta1, const float beta2, const float eps,
-                                             const float wd, const float gscale, const float ew) {
+                                             const float wd, const float gscale, const float ew, const float dk) {
   if constexpr (EMA) {
     float pe = p[t], me = m[t], ve = v[t];
     const float ae = a[t];
-    adam_update(pe, g[t], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    adam_update_d<DEC>(pe, g[t], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
     p[t] = pe; m[t] = me; v[t] = ve;
     a[t] = ema_lerp(ae, pe, ew);
   } else {
-    adam_update(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    adam_update_d<DEC>(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
   }
 }
 
@@ -80,6 +110,13 @@ __device__ __forceinline__ void adam_update1(float* p, const float* g, float* m,
 struct ema_opts { float* a; float decay; int warmup; };
 __device__ __forceinline__ ema_opts ema_of() { return {nullptr, 0.f, 0}; }
 __device__ __forceinline__ ema_opts ema_of(float* a, float decay, int warmup) { return {a, decay, warmup}; }
+// ... and a decoupled instantiation takes this tag as the pack's last type: adam_kernel<false, decoupled>, adam_kernel<true, float*,
+// float, int, decoupled> and the same two of adam_rates_kernel are new kernels beside the four that exist, whose names stay.
+struct decoupled {};
+__device__ __forceinline__ ema_opts ema_of(decoupled) { return {nullptr, 0.f, 0}; }
+__device__ __forceinline__ ema_opts ema_of(float* a, float decay, int warmup, decoupled) { return {a, decay, warmup}; }
+template <typename... E>
+constexpr bool is_decoupled = (std::is_same<E, decoupled>::value || ...);
 
 // adam_kernel<false> is the kernel as it always was, instruction for instruction.  adam_kernel<true, float*, float, int> is its EMA
 // form: a fifth stream `a`, loaded and stored in 16-byte groups exactly where p is, under the same hold.
@@ -102,6 +139,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   float* __restrict__ a = eo.a;
   float ew = 0.f;
   if constexpr (EMA) ew = ema_weight(hyper, eo.decay, eo.warmup);
+  constexpr bool DEC = is_decoupled<E...>;
+  float dk = 0.f;
+  if constexpr (DEC) dk = adam_decay_factor(hyper[0], 1.f, wd, 1.f);
   if (i < n4 && !hold) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
     const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
@@ -112,7 +152,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float pe = pp[e], me = mm[e], ve = vv[e];
-      adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      adam_update_d<DEC>(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
       pp[e] = pe; mm[e] = me; vv[e] = ve;
       if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, ew);
     }
@@ -132,7 +172,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
     }
     for (int64_t t = n4 * 4; t < n && !hold; ++t)
-      adam_update1<EMA>(p, g, m, v, a, t, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
+      adam_update1<EMA, DEC>(p, g, m, v, a, t, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, dk);
   }
 }
 
@@ -187,6 +227,59 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sdumc_adam_table 
     for (int e = tid; e < cnt; e += 256) adam_update(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
   }
 }
+// The decoupled form (sdumc_adamw_multi): adam_multi_kernel's text with adam_decay_mul in front of every update, one factor for the
+// whole launch.  A kernel of its own and not a shared body: adam_multi_kernel keeps its name and, instruction for instruction, the
+// stream it had (a body shared through a template compiled to the same instructions with one scalar add's operands exchanged).
+__global__ __launch_bounds__(256) void adamw_multi_kernel(const sdumc_adam_table tb, float* __restrict__ m_all,
+                                                          float* __restrict__ v_all, const float* hyper, float beta1,
+                                                          float beta2, float eps, float wd, float gscale,
+                                                          const int32_t* chain_err) {
+  if (chain_err != nullptr && *chain_err != 0) return;     // garbage gradients (see adam_kernel): NOTHING is applied
+  const float step_size = hyper[2], bc2_sqrt = hyper[3];
+  const float dk = adam_decay_factor(hyper[0], 1.f, wd, 1.f);
+  const uint32_t b = blockIdx.x;
+  int lo = 0, hi = tb.nseg - 1;
+  while (lo < hi) {                                         // first segment with block_end > b
+    const int mid = (lo + hi) >> 1;
+    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  const sdumc_adam_seg sg = tb.seg[lo];
+  const uint32_t b0 = lo > 0 ? tb.block_end[lo - 1] : 0u;
+  const int64_t base = (int64_t)(b - b0) * SDUMC_ADAM_CHUNK;
+  const int64_t left = sg.n - base;
+  const int cnt = left < SDUMC_ADAM_CHUNK ? (int)left : SDUMC_ADAM_CHUNK;
+  float* __restrict__ p = sg.param + base;
+  const float* __restrict__ g = sg.grad + base;
+  float* __restrict__ m = m_all + sg.state_offset + base;
+  float* __restrict__ v = v_all + sg.state_offset + base;
+  const int tid = threadIdx.x;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                         reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  if (aligned) {
+    const int e0 = 4 * tid;
+    if (e0 + 4 <= cnt) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
+      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
+      f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
+      f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        adam_update_d<true>(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + e0) = pp;
+      *reinterpret_cast<f32x4*>(m + e0) = mm;
+      *reinterpret_cast<f32x4*>(v + e0) = vv;
+    } else {
+      for (int e = e0; e < cnt; ++e)
+        adam_update_d<true>(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
+    }
+  } else {
+    for (int e = tid; e < cnt; e += 256)
+      adam_update_d<true>(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
+  }
+}
 
 // Per-tensor learning rates, decay and frozen tensors (sdumc_adam_step_rates): adam_kernel's launch over the flat bucket, with each
 // element's tensor found through a segment table that travels in the kernel arguments.  The table is a kernel argument, so a lookup
@@ -206,11 +299,11 @@ __device__ __forceinline__ int first_seg_behind(const rates_table& tb, int64_t e
   return lo;
 }
 // 16 bytes of ONE tensor (or of padding): adam_kernel's vector path
-template <bool EMA>
+template <bool EMA, bool DEC>
 __device__ __forceinline__ void adam_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                              float* __restrict__ v, float* __restrict__ a, const int64_t e0, const float step_size,
                                              const float bc2_sqrt, const float beta1, const float beta2, const float eps,
-                                             const float wd, const float gscale, const float ew) {
+                                             const float wd, const float gscale, const float ew, const float dk) {
   f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
   const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
   f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
@@ -220,7 +313,7 @@ __device__ __forceinline__ void adam_update4(float* __restrict__ p, const float*
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float pe = pp[e], me = mm[e], ve = vv[e];
-    adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    adam_update_d<DEC>(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
     pp[e] = pe; mm[e] = me; vv[e] = ve;
     if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, ew);
   }
@@ -232,20 +325,28 @@ __device__ __forceinline__ void adam_update4(float* __restrict__ p, const float*
 // ONE element, on the per-element path.  s: the first segment that ends behind some element at or in front of t; moved on to t's.
 // An element of no segment (alignment padding) gets the default update; one of a frozen segment is neither read nor written -- nor is
 // its average.
-template <bool EMA>
+// Decoupled (DEC, lr0 = hyper[0]): the segment's factor is adam_decay_factor of its two scales, that of an element of no segment the
+// factor of sdumc_adamw_step without a table; the coupled forms read neither.
+template <bool DEC>
+__device__ __forceinline__ float seg_decay(const float lr0, const float wd, const float lr_scale, const float wd_scale) {
+  if constexpr (DEC) return adam_decay_factor(lr0, lr_scale, wd, wd_scale);
+  return 0.f;
+}
+template <bool EMA, bool DEC>
 __device__ __forceinline__ void adam_rates_one(const rates_table& tb, int& s, const int64_t t, float* __restrict__ p,
                                                const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                float* __restrict__ a, const float step_size, const float bc2_sqrt, const float beta1,
                                                const float beta2, const float eps, const float wd, const float gscale,
-                                               const float ew) {
+                                               const float ew, const float lr0) {
   while (s < tb.nseg && seg_end(tb, s) <= t) ++s;
-  float ss = step_size, w = wd;
+  float ss = step_size, w = wd, dk = seg_decay<DEC>(lr0, wd, 1.f, 1.f);
   if (s < tb.nseg && tb.seg[s].offset <= t) {
     if (tb.seg[s].frozen) return;
     ss = step_size * tb.seg[s].lr_scale;
     w = wd * tb.seg[s].wd_scale;
+    dk = seg_decay<DEC>(lr0, wd, tb.seg[s].lr_scale, tb.seg[s].wd_scale);
   }
-  adam_update1<EMA>(p, g, m, v, a, t, ss, bc2_sqrt, beta1, beta2, eps, w, gscale, ew);
+  adam_update1<EMA, DEC>(p, g, m, v, a, t, ss, bc2_sqrt, beta1, beta2, eps, w, gscale, ew, dk);
 }
 
 // Thread i owns the 16-byte group [4 i, 4 i + 4) of the bucket, as in adam_kernel.  A wave whose 256 elements lie inside one segment
@@ -269,6 +370,9 @@ __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, 
   float* __restrict__ a = eo.a;
   float ew = 0.f;
   if constexpr (EMA) ew = ema_weight(hyper, eo.decay, eo.warmup);
+  constexpr bool DEC = is_decoupled<E...>;
+  float lr0 = 0.f;
+  if constexpr (DEC) lr0 = hyper[0];
   // the wave's first element and the first segment that ends behind it: scalar registers, scalar loads
   const int64_t w0 = 4 * ((int64_t)blockIdx.x * blockDim.x + __builtin_amdgcn_readfirstlane((int)threadIdx.x));
   const int s0 = first_seg_behind(tb, w0);
@@ -276,21 +380,22 @@ __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, 
     const int64_t e0 = 4 * i;
     if (s0 < tb.nseg && tb.seg[s0].offset <= w0 && w0 + 256 <= seg_end(tb, s0)) {        // (wave-uniform)
       if (!tb.seg[s0].frozen)
-        adam_update4<EMA>(p, g, m, v, a, e0, step_size * tb.seg[s0].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s0].wd_scale,
-                          gscale, ew);
+        adam_update4<EMA, DEC>(p, g, m, v, a, e0, step_size * tb.seg[s0].lr_scale, bc2_sqrt, beta1, beta2, eps,
+                               wd * tb.seg[s0].wd_scale, gscale, ew, seg_decay<DEC>(lr0, wd, tb.seg[s0].lr_scale, tb.seg[s0].wd_scale));
     } else {
       int s = s0;
       while (s < tb.nseg && seg_end(tb, s) <= e0) ++s;
       const bool padding = s == tb.nseg || tb.seg[s].offset >= e0 + 4;                   // the group meets no segment
       if (padding) {
-        adam_update4<EMA>(p, g, m, v, a, e0, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
+        adam_update4<EMA, DEC>(p, g, m, v, a, e0, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew,
+                               seg_decay<DEC>(lr0, wd, 1.f, 1.f));
       } else if (tb.seg[s].offset <= e0 && e0 + 4 <= seg_end(tb, s)) {                   // ... lies inside one
         if (!tb.seg[s].frozen)
-          adam_update4<EMA>(p, g, m, v, a, e0, step_size * tb.seg[s].lr_scale, bc2_sqrt, beta1, beta2, eps, wd * tb.seg[s].wd_scale,
-                            gscale, ew);
+          adam_update4<EMA, DEC>(p, g, m, v, a, e0, step_size * tb.seg[s].lr_scale, bc2_sqrt, beta1, beta2, eps,
+                                 wd * tb.seg[s].wd_scale, gscale, ew, seg_decay<DEC>(lr0, wd, tb.seg[s].lr_scale, tb.seg[s].wd_scale));
       } else {                                                                           // ... straddles a boundary
         for (int e = 0; e < 4; ++e)
-          adam_rates_one<EMA>(tb, s, e0 + e, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
+          adam_rates_one<EMA, DEC>(tb, s, e0 + e, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, lr0);
       }
     }
   }
@@ -306,7 +411,7 @@ __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, 
     if (!hold && n4 * 4 < n) {
       int s = first_seg_behind(tb, n4 * 4);
       for (int64_t t = n4 * 4; t < n; ++t)
-        adam_rates_one<EMA>(tb, s, t, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew);
+        adam_rates_one<EMA, DEC>(tb, s, t, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, lr0);
     }
   }
 }
@@ -562,6 +667,77 @@ extern "C" int sdumc_adam_step_ema(float* param, const float* grad, float* exp_a
                                nullptr, segs, nseg, ema, ema_decay, ema_warmup, stream);
 }
 
+// what sdumc_adamw_apply_ refuses, without a launch (sdumc_train_step and sdumc_adamw_step ask before anything is enqueued): what the
+// coupled form of the same arguments refuses, and options of an average without one
+extern "C" int sdumc_adamw_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
+                                       const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay,
+                                       int32_t ema_warmup) {
+  if (ema) return sdumc_adam_ema_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay);
+  if (ema_decay != 0.f || ema_warmup != 0) return SDUMC_EINVAL;      // (a NaN decay compares unequal too)
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return SDUMC_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+    return SDUMC_EINVAL;
+  if (segs != nullptr || nseg != 0) return rates_table_check(segs, nseg, n);
+  return SDUMC_OK;
+}
+
+// The decoupled form of whichever of the four flat-bucket launches these arguments name: sdumc_adam_apply_'s (no table, no average),
+// sdumc_adam_apply_rates_'s (a table), sdumc_adam_apply_ema_'s two (an average).
+extern "C" int sdumc_adamw_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
+                                  float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
+                                  uint32_t rng_inc, const sdumc_total_loss* total, const sdumc_rate_seg* segs, int32_t nseg,
+                                  float* ema, float ema_decay, int32_t ema_warmup, void* stream) {
+  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 152 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!hyper) return SDUMC_EINVAL;
+  const int rc = sdumc_adamw_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay, ema_warmup);
+  if (rc) return rc;
+  sdumc_total_loss tl;
+  tl.losses = nullptr;
+  tl.chain_err = nullptr;
+  tl.guard = nullptr;
+  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
+  if (total) tl = *total;
+  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();      // (as sdumc_adam_apply_)
+  const int64_t n4 = n / 4;
+  const int64_t threads = n4 > 0 ? n4 : 1;
+  const dim3 grid((unsigned)((threads + 255) / 256));
+  const int warm = ema_warmup != 0 ? 1 : 0;
+  rates_table tb;
+  memset(&tb, 0, sizeof(tb));
+  tb.nseg = nseg;
+  for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
+  if (nseg != 0 && ema)
+    hipLaunchKernelGGL((adam_rates_kernel<true, float*, float, int, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad,
+                       exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb, ema,
+                       ema_decay, warm, decoupled{});
+  else if (nseg != 0)
+    hipLaunchKernelGGL((adam_rates_kernel<false, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq,
+                       n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb, decoupled{});
+  else if (ema)
+    hipLaunchKernelGGL((adam_kernel<true, float*, float, int, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg,
+                       exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, ema, ema_decay,
+                       warm, decoupled{});
+  else
+    hipLaunchKernelGGL((adam_kernel<false, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n4, n,
+                       hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, decoupled{});
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
+}
+
+extern "C" int sdumc_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper,
+                                float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                const sdumc_rate_seg* segs, int32_t nseg, float* ema, float ema_decay, int32_t ema_warmup,
+                                void* stream) {
+  if (!hyper) return SDUMC_EINVAL;
+  int rc = sdumc_adamw_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay, ema_warmup);   // (before the count advances)
+  if (rc) return rc;
+  rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
+  if (rc) return rc;
+  return sdumc_adamw_apply_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u,
+                            nullptr, segs, nseg, ema, ema_decay, ema_warmup, stream);
+}
+
 extern "C" int sdumc_ema_multi(const sdumc_ema_seg* segs, int32_t nseg, float weight, void* stream) {
   static_assert(sizeof(ema_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
   if (!segs || nseg <= 0 || !(weight >= 0.f && weight <= 1.f)) return SDUMC_EINVAL;
@@ -618,9 +794,11 @@ extern "C" int sdumc_zero_segments(float* buf, int64_t n, const sdumc_rate_seg* 
   return SDUMC_OK;
 }
 
-extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
-                                float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                                void* stream) {
+namespace {
+// sdumc_adam_multi (decoupled false) and sdumc_adamw_multi (true): the same refusals, tables and grids, the kernel of either rule
+int adam_multi_launch(const bool decoupled_decay, const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq,
+                      int64_t state_len, float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                      void* stream) {
   static_assert(sizeof(sdumc_adam_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
   if (!segs || nseg <= 0 || !exp_avg || !exp_avg_sq || !hyper || state_len <= 0) return SDUMC_EINVAL;
   uint64_t blocks_of_launch = 0;
@@ -649,11 +827,30 @@ extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float*
       }
       tb.block_end[i] = blocks;
     }
-    hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
-                       beta2, eps, weight_decay, grad_scale, chain_err);
+    if (decoupled_decay)
+      hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
+                         beta2, eps, weight_decay, grad_scale, chain_err);
+    else
+      hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
+                         beta2, eps, weight_decay, grad_scale, chain_err);
     SDUMC_CHECK_LAUNCH();
   }
   return SDUMC_OK;
+}
+}  // namespace
+
+extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                                float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                void* stream) {
+  return adam_multi_launch(false, segs, nseg, exp_avg, exp_avg_sq, state_len, hyper, beta1, beta2, eps, weight_decay, grad_scale,
+                           stream);
+}
+
+extern "C" int sdumc_adamw_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                                 float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                 void* stream) {
+  return adam_multi_launch(true, segs, nseg, exp_avg, exp_avg_sq, state_len, hyper, beta1, beta2, eps, weight_decay, grad_scale,
+                           stream);
 }
 
 SDUMC_PRELOAD_HOOK(adam)      // (common.h)

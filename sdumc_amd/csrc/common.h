@@ -147,6 +147,15 @@ int sdumc_adam_apply_ema_(float* param, const float* grad, float* exp_avg, float
 // ... and what that would refuse, without a launch
 int sdumc_adam_ema_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
                                const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay);
+// ... the decoupled form (sdumc_adamw_step) of whichever of those launches the arguments name (segs NULL and nseg 0: no table; ema
+// NULL: no average) ...
+int sdumc_adamw_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
+                       uint32_t rng_inc, const struct sdumc_total_loss* total, const sdumc_rate_seg* segs, int32_t nseg, float* ema,
+                       float ema_decay, int32_t ema_warmup, void* stream);
+// ... and what that would refuse, without a launch
+int sdumc_adamw_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
+                            const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay, int32_t ema_warmup);
 // grad_guard.hip: what sdumc_grad_guard would refuse for these arguments, without a launch
 int sdumc_grad_guard_check_(const float* grads, int64_t n, float max_norm, int32_t skip_nonfinite, const float* hyper,
                             const void* scratch, const float* guard);

@@ -3142,6 +3142,11 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   if (cfg->ema)
     RET(sdumc_adam_ema_args_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live,
                                    cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema, cfg->ema_decay));
+  // decoupled weight decay (adam.hip): 0 or 1, and the decoupled form of the last launch refuses what the launch it mirrors refuses
+  if (cfg->decoupled_decay != 0 && cfg->decoupled_decay != 1) return SDUMC_EINVAL;
+  if (cfg->decoupled_decay)
+    RET(sdumc_adamw_args_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live,
+                                cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema, cfg->ema_decay, cfg->ema_warmup));
   if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   // clipping and the non-finite guard (grad_guard.hip) are asked for through `guard`: options without it, and whatever
   // sdumc_grad_guard itself would refuse, come back before the forward is enqueued
@@ -3195,7 +3200,11 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
                          stream));
   uint32_t* rng = d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr;
   const sdumc_total_loss* total = total_pending || cfg->guard ? &tl : nullptr;
-  if (cfg->ema)      // the same launch with the averaged weights riding along (rate_segs: none without `rates`)
+  if (cfg->decoupled_decay)      // the decoupled form of whichever of the launches below this step would have made
+    RET(sdumc_adamw_apply_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
+                           cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema,
+                           cfg->ema_decay, cfg->ema_warmup, stream));
+  else if (cfg->ema)      // the same launch with the averaged weights riding along (rate_segs: none without `rates`)
     RET(sdumc_adam_apply_ema_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
                               cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema,
                               cfg->ema_decay, cfg->ema_warmup, stream));

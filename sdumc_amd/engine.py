@@ -441,6 +441,7 @@ class _OptStateMixin:
         self.rng.set_call(2 * step)
 
     ema_params = None      # with ema_decay: the averaged weights, a flat tensor laid out like .params (ParamLayout.total)
+    decoupled_decay = False      # True: decoupled weight decay, the decoupled form of the step's last launch (sdumc_adamw_step)
 
     def load_ema(self, flat):
         """Resume: installs a saved average (checkpoint.load_ema gives the flat tensor) -- ParamLayout.total elements, copied to the
@@ -509,8 +510,15 @@ class TrainStep(_OptStateMixin):
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
                  bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
-                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None, ema_decay=None, ema_warmup=False):
-        """ema_decay (None = today's step, launch for launch) / ema_warmup: averaged weights, an exponential moving average of the
+                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None, ema_decay=None, ema_warmup=False,
+                 decoupled_decay=False):
+        """decoupled_decay (False = today's step, launch for launch; a bool): torch.optim.AdamW's decoupled weight decay in place of
+        the coupled L2 -- the decoupled form of the step's last launch (sdumc_adamw_step has the rule): every updated parameter is
+        first multiplied by fp32(1 - lr * lr_scale_i * weight_decay * decay_scale_i), one fp32 multiply of its own with the factor
+        derived on the device from the lr the launch reads (set_lr is followed), then updated as with weight_decay = 0.  Combines
+        with clip_norm / skip_nonfinite (a skipped step decays nothing), freeze / lr_scale / decay_scale and ema_decay / ema_warmup.
+        A decoupled step is not captured (capture() raises).
+        ema_decay (None = today's step, launch for launch) / ema_warmup: averaged weights, an exponential moving average of the
         parameters kept by the step's last launch (Adam's, or the rates launch) at the cost of one more read-and-write stream in it: no
         further launch, nothing on the host per step.  .ema_params is a flat tensor laid out like the parameters (the run's, through
         share, or this step's own), a copy of them at construction; after every update ema <- torch.lerp(ema, params, w), w = fp32(1 -
@@ -551,6 +559,7 @@ class TrainStep(_OptStateMixin):
         Ta, Tt, Tv, T4 = T
         distill_code = _lib.distill_code(distill)
         self.distill = distill
+        self.decoupled_decay = bool(_lib.decoupled_arg(decoupled_decay))
         clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
         if (clip or skip) and not _lib.GUARD_ABI:
             raise _lib.SdumcError("clip_norm / skip_nonfinite: the library named by SDUMC_LIB is from before sdumc_grad_guard")
@@ -649,6 +658,8 @@ class TrainStep(_OptStateMixin):
             cfg.weights[i] = w
         _lib.contrast_cfg(cfg, contrast, contrast_temperature, contrast_classes)      # (temperature: 2.0 unless asked otherwise)
         cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay = betas[0], betas[1], eps, weight_decay
+        if self.decoupled_decay:
+            cfg.decoupled_decay = 1
         cfg.adam_m, cfg.adam_v = ptr(self.adam_m), ptr(self.adam_v)
         cfg.hyper, cfg.losses = ptr(self.hyper), ptr(self.losses)
         cfg.distill = distill_code
@@ -813,6 +824,8 @@ class TrainStep(_OptStateMixin):
             raise _lib.SdumcError("capture: a step with freeze / lr_scale / decay_scale is not captured (not built)")
         if self.ema_params is not None:
             raise _lib.SdumcError("capture: a step with ema_decay is not captured (not built)")
+        if self.decoupled_decay:
+            raise _lib.SdumcError("capture: a step with decoupled_decay is not captured (not built)")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
@@ -950,8 +963,10 @@ class FusedTrainer:
 
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
                  inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
-                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False, **step_kwargs):
+                 skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False,
+                 decoupled_decay=False, **step_kwargs):
         """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        decoupled_decay (a bool): torch.optim.AdamW's decoupled weight decay in every step of the run (TrainStep has the rule).
         ema_decay / ema_warmup: averaged weights (TrainStep has the rule): .ema_params is the run's ONE average, a flat tensor laid out
         like the parameters that every step updates whatever its shape (None when off); eval_epoch / saliency_epoch(weights='ema')
         read it, load_ema / reset_ema install a saved one / start over.  The average is not part of train_epoch's record.
@@ -970,6 +985,7 @@ class FusedTrainer:
         through per-batch row maps (4 bytes per frame; sdumc_net_io.row_map)."""
         _lib.distill_code(distill)
         self.distill = distill
+        self.decoupled_decay = bool(_lib.decoupled_arg(decoupled_decay))
         clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
         ema_on = _lib.ema_args(ema_decay, ema_warmup)[0]
         if ema_on and not _lib.EMA_ABI:
@@ -982,6 +998,8 @@ class FusedTrainer:
                        contrast_classes=contrast_classes, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
         if ema_on:      # (off: the steps are built with the keywords they always were)
             self.kw.update(ema_decay=ema_decay, ema_warmup=ema_warmup)
+        if self.decoupled_decay:
+            self.kw.update(decoupled_decay=True)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         self.rates = TensorRates(lay, lr_scale, decay_scale, freeze) if TensorRates.wanted(lr_scale, decay_scale, freeze) else None
         if self.rates is not None and not _lib.RATES_ABI:

@@ -688,6 +688,29 @@ def adam_step_ema(param, grad, m, v, hyper, ema, ema_decay, ema_warmup=False, se
                                   int(bool(ema_warmup)), _st()), "sdumc_adam_step_ema")
 
 
+def adamw_step(param, grad, m, v, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, grad_scale=1.0, segments=None,
+               ema=None, ema_decay=0.0, ema_warmup=False):
+    """torch.optim.AdamW's step over the flat buffers: param <- param * fp32(1 - lr * weight_decay) (one fp32 multiply of its own, lr =
+    hyper[0]), then adam_step's update with weight_decay = 0.  segments: adam_step_rates' tuples (the factor is then fp32(1 - lr *
+    lr_scale * weight_decay * decay_scale) per segment); ema: adam_step_ema's average.  Nothing is checked here: the library refuses
+    bad arguments."""
+    segs = rate_segments(segments) if segments is not None else None
+    check(lib.sdumc_adamw_step(ptr(param), ptr(grad), ptr(m), ptr(v), param.numel(), ptr(hyper), beta1, beta2, eps, weight_decay,
+                               grad_scale, segs, len(segments) if segments is not None else 0, ptr(ema), ema_decay,
+                               int(bool(ema_warmup)), _st()), "sdumc_adamw_step")
+
+
+def adamw_multi(params, grads, m, v, state_offsets, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2,
+                grad_scale=1.0, segs=None):
+    """adamw_step over per-parameter tensors in one launch: adam_multi's arguments, decoupled weight decay."""
+    if segs is None:
+        segs = adam_segments(params, grads, state_offsets)
+    if v.numel() != m.numel():
+        raise _lib.SdumcError("adamw_multi: the two moment buffers must have the same length")
+    check(lib.sdumc_adamw_multi(segs, len(params), ptr(m), ptr(v), m.numel(), ptr(hyper), beta1, beta2, eps, weight_decay,
+                                grad_scale, _st()), "sdumc_adamw_multi")
+
+
 def ema_segments(emas, params):
     """The ctypes segment table of ema_multi (kept by a caller that averages the same tensors again and again)."""
     segs = (_lib.EmaSeg * max(1, len(emas)))()

@@ -3,6 +3,7 @@
 :150): the same signature, param_groups, state_dict format and LambdaLR behaviour, with the whole step as ONE
 sdumc_adam_multi launch over the per-parameter gradient tensors autograd left in `p.grad`.  clip_grad_norm_ is the line that
 often stands in front of it, torch.nn.utils.clip_grad_norm_, as three launches over the same tensors and no host synchronisation.
+AdamW, and Adam(..., decoupled_weight_decay=True), are torch.optim.AdamW the same way: ONE sdumc_adamw_multi launch.
 
 The one divergence from torch.optim.Adam: ONE step count is shared by all parameters (torch keeps one per
 parameter).  That is the model's own situation -- every live parameter receives a gradient on every step -- and it
@@ -126,7 +127,7 @@ def get_ema_multi_avg_fn(decay=0.999):
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, foreach=None,
-                 maximize=False, capturable=False, differentiable=False, fused=None):
+                 maximize=False, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False):
         for name, on in (("amsgrad", amsgrad), ("maximize", maximize), ("capturable", capturable),
                          ("differentiable", differentiable)):
             if on:
@@ -137,9 +138,12 @@ class Adam(torch.optim.Optimizer):
             raise ValueError(f"invalid lr / eps / weight_decay: {lr}, {eps}, {weight_decay}")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"invalid betas: {betas}")
+        if not isinstance(decoupled_weight_decay, bool):
+            raise SdumcError(f"sdumc_amd.optim.Adam: decoupled_weight_decay must be True or False, not {decoupled_weight_decay!r}")
         # the keys torch.optim.Adam writes (and checkpoint.adam_state_from_flat with it); foreach / fused are accepted and ignored
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
+                        foreach=None, capturable=False, differentiable=False, fused=None,
+                        decoupled_weight_decay=decoupled_weight_decay)
         self._m = self._v = self._hyper = None      # flat fp32 moments [state_len], device {lr, t, lr/(1-b1^t), sqrt(1-b2^t)}
         self._live = None                            # the parameters of this optimizer's set, in param_groups order
         self._offsets = None                         # their offsets into the flat moments (multiples of 4: 16-byte aligned)
@@ -256,8 +260,10 @@ class Adam(torch.optim.Optimizer):
                 self._hyper[0] = lr
                 self._lr_written = lr
             beta1, beta2 = group["betas"]
-            ops.adam_multi(live, grads, self._m, self._v, self._offsets, self._hyper, beta1, beta2, group["eps"],
-                           group["weight_decay"], segs=self._segs)
+            # the group's flag decides, as in torch: the constructor's, or the one a loaded state_dict brought
+            multi = ops.adamw_multi if group.get("decoupled_weight_decay") else ops.adam_multi
+            multi(live, grads, self._m, self._v, self._offsets, self._hyper, beta1, beta2, group["eps"],
+                  group["weight_decay"], segs=self._segs)
         self._step_t += 1
         return loss
 
@@ -305,3 +311,13 @@ class Adam(torch.optim.Optimizer):
                 n = p.numel()
                 self.state[p] = {"step": self._step_t, "exp_avg": self._m[off:off + n].view(p.shape),
                                  "exp_avg_sq": self._v[off:off + n].view(p.shape)}
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW's signature and defaults (weight_decay=1e-2): Adam above with decoupled_weight_decay=True, so one group, one
+    launch (sdumc_adamw_multi), one step count, the same refusals, and torch's param_groups keys and state_dict format."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 foreach=None, capturable=False, differentiable=False, fused=None):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, foreach=foreach, maximize=maximize, capturable=capturable,
+                         differentiable=differentiable, fused=fused, decoupled_weight_decay=True)
