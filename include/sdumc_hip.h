@@ -780,8 +780,8 @@ int sdumc_ema_multi(const sdumc_ema_seg* segs, int32_t nseg, float weight, void*
 int sdumc_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper, float beta1,
                      float beta2, float eps, float weight_decay, float grad_scale, const sdumc_rate_seg* segs, int32_t nseg,
                      float* ema, float ema_decay, int32_t ema_warmup, void* stream);
-/* sdumc_adam_multi with that rule (lr_scale = wd_scale = 1): the same segments, launches and refusals, a kernel of its own
- * (adamw_multi_kernel), the bits of sdumc_adamw_step over the concatenation. */
+/* sdumc_adam_multi with that rule (lr_scale = wd_scale = 1): the same segments, launches and refusals, the decoupled
+ * instantiation of the same kernel, the bits of sdumc_adamw_step over the concatenation. */
 int sdumc_adamw_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
                       float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                       void* stream);

@@ -8,7 +8,12 @@
 // sdumc_adam_step_ema is either flat-bucket launch with the averaged weights (an EMA of the parameters) riding along: one more stream,
 // loaded and stored where the parameter is; sdumc_ema_multi is that rule alone over per-parameter tensors, for the loop above.
 // sdumc_adamw_step / sdumc_adamw_multi are torch.optim.AdamW's rule, decoupled weight decay, as a further form of each of these launches
-// (adam_decay_mul below has the rule); the coupled forms stay what they were, by name and by instruction.
+// (adam_decay_mul below has the rule).
+// The forms of a launch (table or none, average or none, coupled or decoupled) are instantiations of ONE body per kernel shape.  What
+// they promise is bits: each form gives the others' where their rules agree (a table of ones is no table, ...), and the bits of every
+// form are pinned by tests/golden/adam_bits.npz, recorded from the kernels as they were before the bodies were shared.  (Through three
+// added options each older form was also kept instruction for instruction; that promise cost a copy of the text per option and bought
+// nothing a user sees, so it was dropped for the recorded bits.)
 //
 // hyper (device, 4 floats): [0] lr (host-written, LambdaLR value)   [1] step count t (kernel-incremented)
 //                           [2] lr / (1 - beta1^t)                  [3] sqrt(1 - beta2^t)
@@ -16,7 +21,6 @@
 // captured hipGraph replays with the right step count.
 #include "common.h"
 #include <string.h>
-#include <type_traits>
 
 namespace {
 
@@ -34,7 +38,7 @@ __device__ __forceinline__ void adam_update(float& p, const float g, float& m, f
                                             const float wd, const float gscale) {
   // (the two sums of two products name the product that is fused: which one the compiler contracts is otherwise its choice per
   //  kernel -- a wd held in a vector register made it the other one -- and the kernels of this file promise each other's bits.
-  //  Written so that adam_kernel and adam_multi_kernel keep the instruction streams they had with `g * gscale + wd * p`.)
+  //  The fused one is the one adam_kernel and adam_multi_kernel got from `g * gscale + wd * p` when that was the compiler's choice.)
   const float ge = __builtin_fmaf(gscale, g, wd * p);
   m = m + (ge - m) * (1.f - beta1);
   v = __builtin_fmaf(v, beta2, (1.f - beta2) * ge * ge);
@@ -55,16 +59,19 @@ __device__ __forceinline__ float adam_decay_mul(const float p, const float dk) {
 #pragma clang fp contract(off)
   return p * dk;
 }
+// What one element's update is made of: uniform over a launch, or with a table over a segment.  ew: the average's weight (read by the
+// EMA forms only), dk: the decay factor (by the decoupled forms only).
+struct adam_consts {
+  float step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, dk;
+};
 // adam_update (DEC false: wd is the coupled L2 factor, dk is not read) or its decoupled form (DEC true: dk, and wd is not read)
 template <bool DEC>
-__device__ __forceinline__ void adam_update_d(float& p, const float g, float& m, float& v, const float step_size,
-                                              const float bc2_sqrt, const float beta1, const float beta2, const float eps,
-                                              const float wd, const float gscale, const float dk) {
+__device__ __forceinline__ void adam_update_d(float& p, const float g, float& m, float& v, const adam_consts& c) {
   if constexpr (DEC) {
-    p = adam_decay_mul(p, dk);
-    adam_update(p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, 0.f, gscale);
+    p = adam_decay_mul(p, c.dk);
+    adam_update(p, g, m, v, c.step_size, c.bc2_sqrt, c.beta1, c.beta2, c.eps, 0.f, c.gscale);
   } else {
-    adam_update(p, g, m, v, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+    adam_update(p, g, m, v, c.step_size, c.bc2_sqrt, c.beta1, c.beta2, c.eps, c.wd, c.gscale);
   }
 }
 
@@ -87,46 +94,79 @@ __device__ __forceinline__ float ema_weight(const float* hyper, const float deca
   return (float)(1.0 - d);
 }
 
-// ONE element through memory: the scalar tail and the per-element path at segment boundaries.  EMA: the average is read where the
-// parameter is, and the lerp is fed the parameter value just computed, from its register.
+// ONE element through memory: every scalar path of this file (the scalar tails, the per-element path at segment boundaries, the ragged
+// ends and unaligned tensors of the per-parameter kernel).  EMA: the average is read where the parameter is, and the lerp is fed the
+// parameter value just computed, from its register.
 template <bool EMA, bool DEC>
 __device__ __forceinline__ void adam_update1(float* p, const float* g, float* m, float* v, float* a, const int64_t t,
-                                             const float step_size,
-                                             const float bc2_sqrt, const float beta1, const float beta2, const float eps,
-                                             const float wd, const float gscale, const float ew, const float dk) {
+                                             const adam_consts& c) {
   if constexpr (EMA) {
     float pe = p[t], me = m[t], ve = v[t];
     const float ae = a[t];
-    adam_update_d<DEC>(pe, g[t], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
+    adam_update_d<DEC>(pe, g[t], me, ve, c);
     p[t] = pe; m[t] = me; v[t] = ve;
-    a[t] = ema_lerp(ae, pe, ew);
+    a[t] = ema_lerp(ae, pe, c.ew);
   } else {
-    adam_update_d<DEC>(p[t], g[t], m[t], v[t], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
+    adam_update_d<DEC>(p[t], g[t], m[t], v[t], c);
+  }
+}
+// 16 bytes of ONE tensor (or of padding) at element e0: every vector path of this file.  EMA: a fifth stream `a`, loaded and stored in
+// 16-byte groups exactly where p is.
+template <bool EMA, bool DEC>
+__device__ __forceinline__ void adam_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, float* __restrict__ a, const int64_t e0, const adam_consts& c) {
+  f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
+  const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
+  f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
+  f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
+  f32x4 aa;
+  if constexpr (EMA) aa = *reinterpret_cast<f32x4*>(a + e0);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float pe = pp[e], me = mm[e], ve = vv[e];
+    adam_update_d<DEC>(pe, gg[e], me, ve, c);
+    pp[e] = pe; mm[e] = me; vv[e] = ve;
+    if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, c.ew);
+  }
+  *reinterpret_cast<f32x4*>(p + e0) = pp;
+  *reinterpret_cast<f32x4*>(m + e0) = mm;
+  *reinterpret_cast<f32x4*>(v + e0) = vv;
+  if constexpr (EMA) *reinterpret_cast<f32x4*>(a + e0) = aa;
+}
+
+// The average of a flat-bucket launch, behind the arguments every form takes: the buffer (nullptr: none), the decay, the warm-up flag.
+struct ema_opts { float* a; float decay; int warmup; };
+// A launch's constants from its arguments: the bias corrections of hyper, the average's weight (EMA), the decay factor of an element of
+// no segment (DEC).
+template <bool EMA, bool DEC>
+__device__ __forceinline__ adam_consts launch_consts(const float* hyper, float beta1, float beta2, float eps, float wd, float gscale,
+                                                     const ema_opts& ea) {
+  adam_consts c{hyper[2], hyper[3], beta1, beta2, eps, wd, gscale, 0.f, 0.f};
+  if constexpr (EMA) c.ew = ema_weight(hyper, ea.decay, ea.warmup);
+  if constexpr (DEC) c.dk = adam_decay_factor(hyper[0], 1.f, wd, 1.f);
+  return c;
+}
+// What thread 0 of a flat-bucket launch does beside its elements: the dropout call counter (every reader of this step is ordered
+// before this launch) and the step's weighted total (main :149), for the caller's read-back: the six terms were final long ago
+__device__ __forceinline__ void step_tail(uint32_t* rng, const uint32_t rng_inc, const sdumc_total_loss& tl, const bool poisoned) {
+  if (rng) rng[2] += rng_inc;
+  if (tl.losses) {
+    float* L = tl.losses;
+    L[0] = tl.w[0] * L[1] + tl.w[1] * L[2] + tl.w[2] * L[3] + tl.w[3] * L[4] + tl.w[4] * L[5] + tl.w[5] * L[6];
+    L[7] = 0.f;
+    // fail loudly: a clustered utterance-level kernel whose spin ran into its cap finished with wrong data
+    if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
   }
 }
 
-// What an EMA instantiation takes behind the arguments of the kernel it is a form of: the average, the decay, the warm-up flag.  The
-// plain instantiations take nothing there (an empty pack), so their signatures, and they, stay what they were.
-struct ema_opts { float* a; float decay; int warmup; };
-__device__ __forceinline__ ema_opts ema_of() { return {nullptr, 0.f, 0}; }
-__device__ __forceinline__ ema_opts ema_of(float* a, float decay, int warmup) { return {a, decay, warmup}; }
-// ... and a decoupled instantiation takes this tag as the pack's last type: adam_kernel<false, decoupled>, adam_kernel<true, float*,
-// float, int, decoupled> and the same two of adam_rates_kernel are new kernels beside the four that exist, whose names stay.
-struct decoupled {};
-__device__ __forceinline__ ema_opts ema_of(decoupled) { return {nullptr, 0.f, 0}; }
-__device__ __forceinline__ ema_opts ema_of(float* a, float decay, int warmup, decoupled) { return {a, decay, warmup}; }
-template <typename... E>
-constexpr bool is_decoupled = (std::is_same<E, decoupled>::value || ...);
-
-// adam_kernel<false> is the kernel as it always was, instruction for instruction.  adam_kernel<true, float*, float, int> is its EMA
-// form: a fifth stream `a`, loaded and stored in 16-byte groups exactly where p is, under the same hold.
-template <bool EMA, typename... E>
+// Thread i owns the 16-byte group [4 i, 4 i + 4) of the bucket; thread 0 also has step_tail and the up to three elements behind the
+// last group.  EMA: the average travels with the parameter; DEC: decoupled weight decay, one factor for the whole launch.
+template <bool EMA, bool DEC>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                    int64_t n, const float* hyper, float beta1, float beta2, float eps,
                                                    float wd, float gscale, uint32_t* rng, uint32_t rng_inc,
-                                                   const sdumc_total_loss tl, E... ea) {
-  const float step_size = hyper[2], bc2_sqrt = hyper[3];
+                                                   const sdumc_total_loss tl, const ema_opts ea) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // A clustered utterance-level kernel whose spin ran into its cap finished with wrong data: the gradients of this step are
   // garbage, so NOTHING is applied -- parameters and moments stay as they were (every thread reads the word; it is sticky
@@ -135,66 +175,45 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   // ... and a step sdumc_grad_guard skipped (non-finite gradients, guard[3]) applies nothing either; its dropout counter and its
   // total below are those of a finite step
   const bool hold = poisoned || (tl.guard != nullptr && tl.guard[3] != 0.f);
-  const ema_opts eo = ema_of(ea...);
-  float* __restrict__ a = eo.a;
-  float ew = 0.f;
-  if constexpr (EMA) ew = ema_weight(hyper, eo.decay, eo.warmup);
-  constexpr bool DEC = is_decoupled<E...>;
-  float dk = 0.f;
-  if constexpr (DEC) dk = adam_decay_factor(hyper[0], 1.f, wd, 1.f);
-  if (i < n4 && !hold) {
-    f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-    f32x4 aa;
-    if constexpr (EMA) aa = reinterpret_cast<f32x4*>(a)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float pe = pp[e], me = mm[e], ve = vv[e];
-      adam_update_d<DEC>(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
-      pp[e] = pe; mm[e] = me; vv[e] = ve;
-      if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, ew);
-    }
-    reinterpret_cast<f32x4*>(p)[i] = pp;
-    reinterpret_cast<f32x4*>(m)[i] = mm;
-    reinterpret_cast<f32x4*>(v)[i] = vv;
-    if constexpr (EMA) reinterpret_cast<f32x4*>(a)[i] = aa;
-  }
-  // scalar tail (+ the dropout call counter: every reader of this step is ordered before this launch)
+  const adam_consts c = launch_consts<EMA, DEC>(hyper, beta1, beta2, eps, wd, gscale, ea);
+  float* __restrict__ a = ea.a;
+  if (i < n4 && !hold) adam_update4<EMA, DEC>(p, g, m, v, a, 4 * i, c);
   if (i == 0) {
-    if (rng) rng[2] += rng_inc;
-    if (tl.losses) {     // the step's weighted total (main :149), for the caller's read-back: the six terms were final long ago
-      float* L = tl.losses;
-      L[0] = tl.w[0] * L[1] + tl.w[1] * L[2] + tl.w[2] * L[3] + tl.w[3] * L[4] + tl.w[4] * L[5] + tl.w[5] * L[6];
-      L[7] = 0.f;
-      // fail loudly: a clustered utterance-level kernel whose spin ran into its cap finished with wrong data
-      if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
-    }
-    for (int64_t t = n4 * 4; t < n && !hold; ++t)
-      adam_update1<EMA, DEC>(p, g, m, v, a, t, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, dk);
+    step_tail(rng, rng_inc, tl, poisoned);
+    for (int64_t t = n4 * 4; t < n && !hold; ++t) adam_update1<EMA, DEC>(p, g, m, v, a, t, c);
   }
 }
 
-// The same update over per-parameter tensors (sdumc_adam_multi): workgroup b finds its (segment, chunk of SDUMC_ADAM_CHUNK
-// elements) in the table's running workgroup counts -- the table is a kernel argument, every lookup is a scalar load with a
-// wave-uniform index.  A chunk starts a multiple of 4 KiB behind its segment's base, so the segment's alignment is the chunk's:
-// 16 bytes per lane where param, grad and both moments are 16-byte aligned, one float per lane (stride 256, coalesced) elsewhere.
+// Workgroup b's place in a table of running workgroup counts (adam_multi_kernel, ema_multi_kernel, zero_segments_kernel): the first
+// segment with block_end > b, and which of that segment's chunks b is.  The table is a kernel argument, every lookup is a scalar load
+// with a wave-uniform index.  (Two steps, so that a kernel asks for its segment's record between them: the record's load and the
+// load of block_end[seg - 1] are then in flight together.)
+__device__ __forceinline__ int chunk_segment(const uint32_t* block_end, const int nseg, const uint32_t b) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (block_end[mid] > b) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ uint32_t chunk_index(const uint32_t* block_end, const int seg, const uint32_t b) {
+  return b - (seg > 0 ? block_end[seg - 1] : 0u);
+}
+
+// The same update over per-parameter tensors (sdumc_adam_multi; DEC: sdumc_adamw_multi, one factor for the whole launch): workgroup b
+// finds its (segment, chunk of SDUMC_ADAM_CHUNK elements) with chunk_segment and chunk_index.  A chunk starts a multiple of 4 KiB behind its segment's
+// base, so the segment's alignment is the chunk's: 16 bytes per lane where param, grad and both moments are 16-byte aligned, one float
+// per lane (stride 256, coalesced) elsewhere.
+template <bool DEC>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const sdumc_adam_table tb, float* __restrict__ m_all,
                                                          float* __restrict__ v_all, const float* hyper, float beta1,
                                                          float beta2, float eps, float wd, float gscale,
                                                          const int32_t* chain_err) {
   if (chain_err != nullptr && *chain_err != 0) return;     // garbage gradients (see adam_kernel): NOTHING is applied
-  const float step_size = hyper[2], bc2_sqrt = hyper[3];
-  const uint32_t b = blockIdx.x;
-  int lo = 0, hi = tb.nseg - 1;
-  while (lo < hi) {                                         // first segment with block_end > b
-    const int mid = (lo + hi) >> 1;
-    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  const sdumc_adam_seg sg = tb.seg[lo];
-  const uint32_t b0 = lo > 0 ? tb.block_end[lo - 1] : 0u;
-  const int64_t base = (int64_t)(b - b0) * SDUMC_ADAM_CHUNK;
+  const adam_consts c = launch_consts<false, DEC>(hyper, beta1, beta2, eps, wd, gscale, ema_opts{nullptr, 0.f, 0});
+  const int seg = chunk_segment(tb.block_end, tb.nseg, blockIdx.x);
+  const sdumc_adam_seg sg = tb.seg[seg];
+  const int64_t base = (int64_t)chunk_index(tb.block_end, seg, blockIdx.x) * SDUMC_ADAM_CHUNK;
   const int64_t left = sg.n - base;
   const int cnt = left < SDUMC_ADAM_CHUNK ? (int)left : SDUMC_ADAM_CHUNK;
   float* __restrict__ p = sg.param + base;
@@ -207,77 +226,12 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sdumc_adam_table 
   if (aligned) {
     const int e0 = 4 * tid;
     if (e0 + 4 <= cnt) {
-      f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
-      f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
-      f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pp[e], me = mm[e], ve = vv[e];
-        adam_update(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
-      }
-      *reinterpret_cast<f32x4*>(p + e0) = pp;
-      *reinterpret_cast<f32x4*>(m + e0) = mm;
-      *reinterpret_cast<f32x4*>(v + e0) = vv;
+      adam_update4<false, DEC>(p, g, m, v, nullptr, e0, c);
     } else {
-      for (int e = e0; e < cnt; ++e) adam_update(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
+      for (int e = e0; e < cnt; ++e) adam_update1<false, DEC>(p, g, m, v, nullptr, e, c);
     }
   } else {
-    for (int e = tid; e < cnt; e += 256) adam_update(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale);
-  }
-}
-// The decoupled form (sdumc_adamw_multi): adam_multi_kernel's text with adam_decay_mul in front of every update, one factor for the
-// whole launch.  A kernel of its own and not a shared body: adam_multi_kernel keeps its name and, instruction for instruction, the
-// stream it had (a body shared through a template compiled to the same instructions with one scalar add's operands exchanged).
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const sdumc_adam_table tb, float* __restrict__ m_all,
-                                                          float* __restrict__ v_all, const float* hyper, float beta1,
-                                                          float beta2, float eps, float wd, float gscale,
-                                                          const int32_t* chain_err) {
-  if (chain_err != nullptr && *chain_err != 0) return;     // garbage gradients (see adam_kernel): NOTHING is applied
-  const float step_size = hyper[2], bc2_sqrt = hyper[3];
-  const float dk = adam_decay_factor(hyper[0], 1.f, wd, 1.f);
-  const uint32_t b = blockIdx.x;
-  int lo = 0, hi = tb.nseg - 1;
-  while (lo < hi) {                                         // first segment with block_end > b
-    const int mid = (lo + hi) >> 1;
-    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  const sdumc_adam_seg sg = tb.seg[lo];
-  const uint32_t b0 = lo > 0 ? tb.block_end[lo - 1] : 0u;
-  const int64_t base = (int64_t)(b - b0) * SDUMC_ADAM_CHUNK;
-  const int64_t left = sg.n - base;
-  const int cnt = left < SDUMC_ADAM_CHUNK ? (int)left : SDUMC_ADAM_CHUNK;
-  float* __restrict__ p = sg.param + base;
-  const float* __restrict__ g = sg.grad + base;
-  float* __restrict__ m = m_all + sg.state_offset + base;
-  float* __restrict__ v = v_all + sg.state_offset + base;
-  const int tid = threadIdx.x;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                         reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-  if (aligned) {
-    const int e0 = 4 * tid;
-    if (e0 + 4 <= cnt) {
-      f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
-      f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
-      f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pp[e], me = mm[e], ve = vv[e];
-        adam_update_d<true>(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
-      }
-      *reinterpret_cast<f32x4*>(p + e0) = pp;
-      *reinterpret_cast<f32x4*>(m + e0) = mm;
-      *reinterpret_cast<f32x4*>(v + e0) = vv;
-    } else {
-      for (int e = e0; e < cnt; ++e)
-        adam_update_d<true>(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
-    }
-  } else {
-    for (int e = tid; e < cnt; e += 256)
-      adam_update_d<true>(p[e], g[e], m[e], v[e], step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
+    for (int e = tid; e < cnt; e += 256) adam_update1<false, DEC>(p, g, m, v, nullptr, e, c);
   }
 }
 
@@ -298,79 +252,49 @@ __device__ __forceinline__ int first_seg_behind(const rates_table& tb, int64_t e
   }
   return lo;
 }
-// 16 bytes of ONE tensor (or of padding): adam_kernel's vector path
-template <bool EMA, bool DEC>
-__device__ __forceinline__ void adam_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                             float* __restrict__ v, float* __restrict__ a, const int64_t e0, const float step_size,
-                                             const float bc2_sqrt, const float beta1, const float beta2, const float eps,
-                                             const float wd, const float gscale, const float ew, const float dk) {
-  f32x4 pp = *reinterpret_cast<f32x4*>(p + e0);
-  const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e0);
-  f32x4 mm = *reinterpret_cast<f32x4*>(m + e0);
-  f32x4 vv = *reinterpret_cast<f32x4*>(v + e0);
-  f32x4 aa;
-  if constexpr (EMA) aa = *reinterpret_cast<f32x4*>(a + e0);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float pe = pp[e], me = mm[e], ve = vv[e];
-    adam_update_d<DEC>(pe, gg[e], me, ve, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, dk);
-    pp[e] = pe; mm[e] = me; vv[e] = ve;
-    if constexpr (EMA) aa[e] = ema_lerp(aa[e], pe, ew);
-  }
-  *reinterpret_cast<f32x4*>(p + e0) = pp;
-  *reinterpret_cast<f32x4*>(m + e0) = mm;
-  *reinterpret_cast<f32x4*>(v + e0) = vv;
-  if constexpr (EMA) *reinterpret_cast<f32x4*>(a + e0) = aa;
-}
-// ONE element, on the per-element path.  s: the first segment that ends behind some element at or in front of t; moved on to t's.
-// An element of no segment (alignment padding) gets the default update; one of a frozen segment is neither read nor written -- nor is
-// its average.
-// Decoupled (DEC, lr0 = hyper[0]): the segment's factor is adam_decay_factor of its two scales, that of an element of no segment the
-// factor of sdumc_adamw_step without a table; the coupled forms read neither.
+// A segment's constants from the launch's: its two scales applied to step size and coupled L2 factor.  Decoupled (DEC, lr0 =
+// hyper[0]): its factor is adam_decay_factor of its two scales, derived where a path needs it; the coupled forms read neither.  An
+// element of no segment (alignment padding) has scales 1: the default update, and the factor of sdumc_adamw_step without a table.
 template <bool DEC>
-__device__ __forceinline__ float seg_decay(const float lr0, const float wd, const float lr_scale, const float wd_scale) {
-  if constexpr (DEC) return adam_decay_factor(lr0, lr_scale, wd, wd_scale);
-  return 0.f;
-}
+__device__ __forceinline__ adam_consts seg_consts(const adam_consts& c, const float lr0, const float lr_scale, const float wd_scale) {
+  adam_consts o = c;
+  o.step_size = c.step_size * lr_scale;
+  o.wd = c.wd * wd_scale;
+  if constexpr (DEC) o.dk = adam_decay_factor(lr0, lr_scale, c.wd, wd_scale);
+  return o;
+}// ONE element, on the per-element path.  s: the first segment that ends behind some element at or in front of t; moved on to t's.
+// An element of a frozen segment is neither read nor written -- nor is its average.
 template <bool EMA, bool DEC>
 __device__ __forceinline__ void adam_rates_one(const rates_table& tb, int& s, const int64_t t, float* __restrict__ p,
                                                const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                               float* __restrict__ a, const float step_size, const float bc2_sqrt, const float beta1,
-                                               const float beta2, const float eps, const float wd, const float gscale,
-                                               const float ew, const float lr0) {
+                                               float* __restrict__ a, const adam_consts& c, const float lr0) {
   while (s < tb.nseg && seg_end(tb, s) <= t) ++s;
-  float ss = step_size, w = wd, dk = seg_decay<DEC>(lr0, wd, 1.f, 1.f);
+  float lr_scale = 1.f, wd_scale = 1.f;
   if (s < tb.nseg && tb.seg[s].offset <= t) {
     if (tb.seg[s].frozen) return;
-    ss = step_size * tb.seg[s].lr_scale;
-    w = wd * tb.seg[s].wd_scale;
-    dk = seg_decay<DEC>(lr0, wd, tb.seg[s].lr_scale, tb.seg[s].wd_scale);
+    lr_scale = tb.seg[s].lr_scale;
+    wd_scale = tb.seg[s].wd_scale;
   }
-  adam_update1<EMA, DEC>(p, g, m, v, a, t, ss, bc2_sqrt, beta1, beta2, eps, w, gscale, ew, dk);
+  adam_update1<EMA, DEC>(p, g, m, v, a, t, seg_consts<DEC>(c, lr0, lr_scale, wd_scale));
 }
 
 // Thread i owns the 16-byte group [4 i, 4 i + 4) of the bucket, as in adam_kernel.  A wave whose 256 elements lie inside one segment
 // (all but a handful: the tensors are thousands of elements long) finds it with a scalar binary search and takes its scales from
 // scalar registers; a frozen segment's waves leave without touching memory.  In a wave that meets a boundary every lane walks on from
 // the wave's segment to its own: a group inside one segment (or inside padding) still moves 16 bytes, a group that straddles a boundary
-// -- segments start at any residue mod 4 -- goes element by element.  Holds and scalar tail are adam_kernel's.  EMA
-// (adam_rates_kernel<true, float*, float, int>): the average travels with the parameter on every one of these paths;
-// adam_rates_kernel<false> is the kernel as it always was, instruction for instruction.
-template <bool EMA, typename... E>
+// -- segments start at any residue mod 4 -- goes element by element.  Holds and scalar tail are adam_kernel's; EMA and DEC as there,
+// on every one of these paths.
+template <bool EMA, bool DEC>
 __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v, int64_t n4, int64_t n,
                                                          const float* hyper, float beta1, float beta2, float eps, float wd,
                                                          float gscale, uint32_t* rng, uint32_t rng_inc, const sdumc_total_loss tl,
-                                                         const rates_table tb, E... ea) {
-  const float step_size = hyper[2], bc2_sqrt = hyper[3];
+                                                         const rates_table tb, const ema_opts ea) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool poisoned = tl.chain_err != nullptr && *tl.chain_err != 0;                   // (see adam_kernel)
   const bool hold = poisoned || (tl.guard != nullptr && tl.guard[3] != 0.f);
-  const ema_opts eo = ema_of(ea...);
-  float* __restrict__ a = eo.a;
-  float ew = 0.f;
-  if constexpr (EMA) ew = ema_weight(hyper, eo.decay, eo.warmup);
-  constexpr bool DEC = is_decoupled<E...>;
+  const adam_consts c = launch_consts<EMA, false>(hyper, beta1, beta2, eps, wd, gscale, ea);      // (dk: seg_consts', per path)
+  float* __restrict__ a = ea.a;
   float lr0 = 0.f;
   if constexpr (DEC) lr0 = hyper[0];
   // the wave's first element and the first segment that ends behind it: scalar registers, scalar loads
@@ -380,60 +304,42 @@ __global__ __launch_bounds__(256) void adam_rates_kernel(float* __restrict__ p, 
     const int64_t e0 = 4 * i;
     if (s0 < tb.nseg && tb.seg[s0].offset <= w0 && w0 + 256 <= seg_end(tb, s0)) {        // (wave-uniform)
       if (!tb.seg[s0].frozen)
-        adam_update4<EMA, DEC>(p, g, m, v, a, e0, step_size * tb.seg[s0].lr_scale, bc2_sqrt, beta1, beta2, eps,
-                               wd * tb.seg[s0].wd_scale, gscale, ew, seg_decay<DEC>(lr0, wd, tb.seg[s0].lr_scale, tb.seg[s0].wd_scale));
+        adam_update4<EMA, DEC>(p, g, m, v, a, e0, seg_consts<DEC>(c, lr0, tb.seg[s0].lr_scale, tb.seg[s0].wd_scale));
     } else {
       int s = s0;
       while (s < tb.nseg && seg_end(tb, s) <= e0) ++s;
       const bool padding = s == tb.nseg || tb.seg[s].offset >= e0 + 4;                   // the group meets no segment
       if (padding) {
-        adam_update4<EMA, DEC>(p, g, m, v, a, e0, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew,
-                               seg_decay<DEC>(lr0, wd, 1.f, 1.f));
+        adam_update4<EMA, DEC>(p, g, m, v, a, e0, seg_consts<DEC>(c, lr0, 1.f, 1.f));
       } else if (tb.seg[s].offset <= e0 && e0 + 4 <= seg_end(tb, s)) {                   // ... lies inside one
         if (!tb.seg[s].frozen)
-          adam_update4<EMA, DEC>(p, g, m, v, a, e0, step_size * tb.seg[s].lr_scale, bc2_sqrt, beta1, beta2, eps,
-                                 wd * tb.seg[s].wd_scale, gscale, ew, seg_decay<DEC>(lr0, wd, tb.seg[s].lr_scale, tb.seg[s].wd_scale));
+          adam_update4<EMA, DEC>(p, g, m, v, a, e0, seg_consts<DEC>(c, lr0, tb.seg[s].lr_scale, tb.seg[s].wd_scale));
       } else {                                                                           // ... straddles a boundary
-        for (int e = 0; e < 4; ++e)
-          adam_rates_one<EMA, DEC>(tb, s, e0 + e, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, lr0);
+        for (int e = 0; e < 4; ++e) adam_rates_one<EMA, DEC>(tb, s, e0 + e, p, g, m, v, a, c, lr0);
       }
     }
   }
-  // scalar tail, as adam_kernel's
   if (i == 0) {
-    if (rng) rng[2] += rng_inc;
-    if (tl.losses) {
-      float* L = tl.losses;
-      L[0] = tl.w[0] * L[1] + tl.w[1] * L[2] + tl.w[2] * L[3] + tl.w[3] * L[4] + tl.w[4] * L[5] + tl.w[5] * L[6];
-      L[7] = 0.f;
-      if (poisoned) { L[0] = __int_as_float(0x7fc00000); L[7] = 1.f; }
-    }
+    step_tail(rng, rng_inc, tl, poisoned);
     if (!hold && n4 * 4 < n) {
       int s = first_seg_behind(tb, n4 * 4);
-      for (int64_t t = n4 * 4; t < n; ++t)
-        adam_rates_one<EMA, DEC>(tb, s, t, p, g, m, v, a, step_size, bc2_sqrt, beta1, beta2, eps, wd, gscale, ew, lr0);
+      for (int64_t t = n4 * 4; t < n; ++t) adam_rates_one<EMA, DEC>(tb, s, t, p, g, m, v, a, c, lr0);
     }
   }
 }
 
 // The averaged weights of the loop that keeps the module (sdumc_ema_multi): ema_lerp over per-parameter tensors, found like
-// adam_multi_kernel's -- workgroup b's (segment, chunk of SDUMC_ADAM_CHUNK elements) in the table's running workgroup counts, 16 bytes
-// per lane where both addresses are 16-byte aligned, one float per lane elsewhere; the same bits either way.
+// adam_multi_kernel's -- workgroup b's (segment, chunk of SDUMC_ADAM_CHUNK elements) with chunk_segment and chunk_index, 16 bytes per lane where both
+// addresses are 16-byte aligned, one float per lane elsewhere; the same bits either way.
 struct ema_table {
   sdumc_ema_seg seg[SDUMC_ADAM_MAX_SEGS];
   uint32_t block_end[SDUMC_ADAM_MAX_SEGS];
   int32_t nseg;
 };
 __global__ __launch_bounds__(256) void ema_multi_kernel(const ema_table tb, const float w) {
-  const uint32_t b = blockIdx.x;
-  int lo = 0, hi = tb.nseg - 1;
-  while (lo < hi) {                                         // first segment with block_end > b
-    const int mid = (lo + hi) >> 1;
-    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  const sdumc_ema_seg sg = tb.seg[lo];
-  const uint32_t b0 = lo > 0 ? tb.block_end[lo - 1] : 0u;
-  const int64_t base = (int64_t)(b - b0) * SDUMC_ADAM_CHUNK;
+  const int seg = chunk_segment(tb.block_end, tb.nseg, blockIdx.x);
+  const sdumc_ema_seg sg = tb.seg[seg];
+  const int64_t base = (int64_t)chunk_index(tb.block_end, seg, blockIdx.x) * SDUMC_ADAM_CHUNK;
   const int64_t left = sg.n - base;
   const int cnt = left < SDUMC_ADAM_CHUNK ? (int)left : SDUMC_ADAM_CHUNK;
   float* __restrict__ a = sg.ema + base;
@@ -457,9 +363,9 @@ __global__ __launch_bounds__(256) void ema_multi_kernel(const ema_table tb, cons
 }
 
 // +0.0f over the frozen segments of a bucket (sdumc_zero_segments).  The launch's table holds the frozen segments only; workgroup b
-// finds its (segment, chunk) in the running workgroup counts, as adam_multi_kernel does.  A segment's whole 16-byte groups are split
-// into chunks of ZERO_CHUNK elements, 16 bytes per store; its first workgroup also writes the up to three elements in front of the
-// first whole group and behind the last, one float per lane.
+// finds its (segment, chunk) with chunk_segment and chunk_index.  A segment's whole 16-byte groups are split into chunks of ZERO_CHUNK elements, 16 bytes
+// per store; its first workgroup also writes the up to three elements in front of the first whole group and behind the last, one float
+// per lane.
 constexpr int ZERO_CHUNK = 4096;
 struct zero_table {
   int64_t offset[SDUMC_RATES_MAX_SEGS], n[SDUMC_RATES_MAX_SEGS];
@@ -468,14 +374,9 @@ struct zero_table {
 };
 __host__ __device__ inline int64_t zero_groups_begin(int64_t first) { return (first + 3) & ~(int64_t)3; }
 __global__ __launch_bounds__(256) void zero_segments_kernel(float* __restrict__ buf, const zero_table tb) {
-  const uint32_t b = blockIdx.x;
-  int lo = 0, hi = tb.nseg - 1;
-  while (lo < hi) {                                         // first segment with block_end > b
-    const int mid = (lo + hi) >> 1;
-    if (tb.block_end[mid] > b) hi = mid; else lo = mid + 1;
-  }
-  const int64_t k = b - (lo > 0 ? tb.block_end[lo - 1] : 0u);
-  const int64_t first = tb.offset[lo], last = first + tb.n[lo];
+  const int seg = chunk_segment(tb.block_end, tb.nseg, blockIdx.x);
+  const int64_t k = chunk_index(tb.block_end, seg, blockIdx.x);
+  const int64_t first = tb.offset[seg], last = first + tb.n[seg];
   const int64_t a = zero_groups_begin(first), z = last & ~(int64_t)3;      // the whole groups: [a, z), none when a >= z
   const int tid = threadIdx.x;
   const int64_t c1 = a + (k + 1) * ZERO_CHUNK < z ? a + (k + 1) * ZERO_CHUNK : z;
@@ -489,7 +390,7 @@ __global__ __launch_bounds__(256) void zero_segments_kernel(float* __restrict__ 
   }
 }
 
-// what both entries ask of a table: 1 .. SDUMC_RATES_MAX_SEGS segments, ascending, disjoint, inside [0, n), scales finite and >= 0
+// what every entry asks of a table: 1 .. SDUMC_RATES_MAX_SEGS segments, ascending, disjoint, inside [0, n), scales finite and >= 0
 int rates_table_check(const sdumc_rate_seg* segs, int32_t nseg, int64_t n) {
   if (!segs || nseg < 1 || nseg > SDUMC_RATES_MAX_SEGS || n <= 0) return SDUMC_EINVAL;
   int64_t end = 0;
@@ -503,6 +404,26 @@ int rates_table_check(const sdumc_rate_seg* segs, int32_t nseg, int64_t n) {
   return SDUMC_OK;
 }
 
+bool misaligned16(const void* a, const void* b, const void* c, const void* d) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d)) & 15) != 0;
+}
+
+// the flat-bucket kernel of this form, with the table or without
+template <bool EMA, bool DEC>
+void launch_flat(const sdumc_adam_launch& L, const sdumc_total_loss& tl, const rates_table* tb, void* stream) {
+  const int64_t n4 = L.n / 4;
+  const int64_t threads = n4 > 0 ? n4 : 1;
+  const dim3 grid((unsigned)((threads + 255) / 256));
+  const ema_opts ea{L.ema, L.ema_decay, L.ema_warmup != 0 ? 1 : 0};
+  if (tb)
+    hipLaunchKernelGGL((adam_rates_kernel<EMA, DEC>), grid, dim3(256), 0, as_stream(stream), L.param, L.grad, L.exp_avg, L.exp_avg_sq,
+                       n4, L.n, L.hyper, L.beta1, L.beta2, L.eps, L.weight_decay, L.grad_scale, L.rng_state, L.rng_inc, tl, *tb, ea);
+  else
+    hipLaunchKernelGGL((adam_kernel<EMA, DEC>), grid, dim3(256), 0, as_stream(stream), L.param, L.grad, L.exp_avg, L.exp_avg_sq, n4,
+                       L.n, L.hyper, L.beta1, L.beta2, L.eps, L.weight_decay, L.grad_scale, L.rng_state, L.rng_inc, tl, ea);
+}
+
 }  // namespace
 
 extern "C" int sdumc_adam_hyper_(float* hyper, float beta1, float beta2, void* stream) {
@@ -512,257 +433,173 @@ extern "C" int sdumc_adam_hyper_(float* hyper, float beta1, float beta2, void* s
   return SDUMC_OK;
 }
 
-extern "C" int sdumc_adam_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                 const float* hyper, float beta1, float beta2, float eps, float weight_decay,
-                                 float grad_scale, uint32_t* rng_state, uint32_t rng_inc, const sdumc_total_loss* total,
-                                 void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || !hyper || n <= 0) return SDUMC_EINVAL;
-  sdumc_total_loss tl;
-  tl.losses = nullptr;
-  tl.chain_err = nullptr;
-  tl.guard = nullptr;
-  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
-  if (total) tl = *total;
-  // (callers without a loss record -- the data-parallel step, sdumc_adam_step -- are guarded by the device's error word too)
-  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();
-  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
+extern "C" int sdumc_adam_check_(const sdumc_adam_launch* L) {
+  if (!L || !L->param || !L->grad || !L->exp_avg || !L->exp_avg_sq || !L->hyper || L->n <= 0) return SDUMC_EINVAL;
+  if (misaligned16(L->param, L->grad, L->exp_avg, L->exp_avg_sq)) return SDUMC_EINVAL;
+  if (L->segs != nullptr || L->nseg != 0) {      // (a table without a count, and the reverse, are refused by the table's check)
+    const int rc = rates_table_check(L->segs, L->nseg, L->n);
+    if (rc) return rc;
+  }
+  if (L->ema) {      // a 16-byte aligned buffer of n floats that is not the parameters', a decay in [0, 1]
+    if (reinterpret_cast<uintptr_t>(L->ema) & 15) return SDUMC_EINVAL;
+    if (!(L->ema_decay >= 0.f && L->ema_decay <= 1.f)) return SDUMC_EINVAL;      // (NaN fails both)
+    const uintptr_t a = reinterpret_cast<uintptr_t>(L->ema), p = reinterpret_cast<uintptr_t>(L->param), bytes = (uintptr_t)L->n * 4u;
+    if (a < p + bytes && p < a + bytes) return SDUMC_EINVAL;                     // the two ranges overlap
+  } else if (L->ema_decay != 0.f || L->ema_warmup != 0) {      // options of an average without one (a NaN decay compares unequal too)
     return SDUMC_EINVAL;
-  const int64_t n4 = n / 4;
-  const int64_t threads = n4 > 0 ? n4 : 1;
-  hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
-                     exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl);
+  }
+  if (L->decoupled != 0 && L->decoupled != 1) return SDUMC_EINVAL;
+  return SDUMC_OK;
+}
+
+extern "C" int sdumc_adam_apply_(const sdumc_adam_launch* L, void* stream) {
+  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 152 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  const int rc = sdumc_adam_check_(L);
+  if (rc) return rc;
+  sdumc_total_loss tl{};      // (no loss record, no weights, no guard)
+  if (L->total) tl = *L->total;
+  // (callers without a loss record -- the data-parallel step, the public entries -- are guarded by the device's error word too)
+  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();
+  rates_table tb;
+  if (L->nseg != 0) {
+    memset(&tb, 0, sizeof(tb));
+    tb.nseg = L->nseg;
+    for (int32_t i = 0; i < L->nseg; ++i) tb.seg[i] = L->segs[i];
+  }
+  const rates_table* table = L->nseg != 0 ? &tb : nullptr;
+  if (L->ema && L->decoupled) launch_flat<true, true>(*L, tl, table, stream);
+  else if (L->ema) launch_flat<true, false>(*L, tl, table, stream);
+  else if (L->decoupled) launch_flat<false, true>(*L, tl, table, stream);
+  else launch_flat<false, false>(*L, tl, table, stream);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
 }
+
+namespace {
+// A public flat-bucket entry, behind its own precondition: every refusal before the step count advances, then the bias corrections,
+// then the launch.  The entries' records name no dropout counter and no loss record (the three fields in front of `segs`).
+int adam_step_entry(const sdumc_adam_launch& L, float* hyper, void* stream) {
+  int rc = sdumc_adam_check_(&L);
+  if (rc) return rc;
+  rc = sdumc_adam_hyper_(hyper, L.beta1, L.beta2, stream);
+  if (rc) return rc;
+  return sdumc_adam_apply_(&L, stream);
+}
+}  // namespace
 
 extern "C" int sdumc_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                                float* hyper, float beta1, float beta2, float eps, float weight_decay,
                                float grad_scale, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || !hyper || n <= 0) return SDUMC_EINVAL;
-  int rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
-  if (rc) return rc;
-  return sdumc_adam_apply_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
-                           0u, nullptr, stream);
-}
-
-extern "C" int sdumc_adam_rates_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
-                                       const sdumc_rate_seg* segs, int32_t nseg) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return SDUMC_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-    return SDUMC_EINVAL;
-  return rates_table_check(segs, nseg, n);
-}
-
-extern "C" int sdumc_adam_apply_rates_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                       const float* hyper, float beta1, float beta2, float eps, float weight_decay,
-                                       float grad_scale, uint32_t* rng_state, uint32_t rng_inc, const sdumc_total_loss* total,
-                                       const sdumc_rate_seg* segs, int32_t nseg, void* stream) {
-  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 128 <= 4096, "the table travels in the kernel arguments (4 KB)");
-  if (!hyper) return SDUMC_EINVAL;
-  const int rc = sdumc_adam_rates_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg);
-  if (rc) return rc;
-  sdumc_total_loss tl;
-  tl.losses = nullptr;
-  tl.chain_err = nullptr;
-  tl.guard = nullptr;
-  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
-  if (total) tl = *total;
-  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();      // (as sdumc_adam_apply_)
-  rates_table tb;
-  memset(&tb, 0, sizeof(tb));
-  tb.nseg = nseg;
-  for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
-  const int64_t n4 = n / 4;
-  const int64_t threads = n4 > 0 ? n4 : 1;
-  hipLaunchKernelGGL(adam_rates_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), param, grad,
-                     exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb);
-  SDUMC_CHECK_LAUNCH();
-  return SDUMC_OK;
+  return adam_step_entry({param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u, nullptr,
+                          nullptr, 0, nullptr, 0.f, 0, 0}, hyper, stream);
 }
 
 extern "C" int sdumc_adam_step_rates(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper,
                                      float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                      const sdumc_rate_seg* segs, int32_t nseg, void* stream) {
-  if (!hyper) return SDUMC_EINVAL;
-  int rc = sdumc_adam_rates_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg);      // (before the step count advances)
-  if (rc) return rc;
-  rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
-  if (rc) return rc;
-  return sdumc_adam_apply_rates_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr,
-                                 0u, nullptr, segs, nseg, stream);
-}
-
-// what the averaged weights ask on top of Adam's own arguments: a 16-byte aligned buffer of n floats that is not the parameters',
-// a decay in [0, 1]
-extern "C" int sdumc_adam_ema_check_(const void* param, const void* ema, int64_t n, float ema_decay) {
-  if (!param || !ema || n <= 0 || (reinterpret_cast<uintptr_t>(ema) & 15)) return SDUMC_EINVAL;
-  if (!(ema_decay >= 0.f && ema_decay <= 1.f)) return SDUMC_EINVAL;      // (NaN fails both)
-  const uintptr_t a = reinterpret_cast<uintptr_t>(ema), p = reinterpret_cast<uintptr_t>(param), bytes = (uintptr_t)n * 4u;
-  if (a < p + bytes && p < a + bytes) return SDUMC_EINVAL;               // the two ranges overlap
-  return SDUMC_OK;
-}
-
-// what sdumc_adam_apply_ema_ refuses, without a launch (sdumc_train_step and sdumc_adam_step_ema ask before anything is enqueued)
-extern "C" int sdumc_adam_ema_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
-                                          const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return SDUMC_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-    return SDUMC_EINVAL;
-  if (segs != nullptr || nseg != 0) {
-    const int rc = rates_table_check(segs, nseg, n);
-    if (rc) return rc;
-  }
-  return sdumc_adam_ema_check_(param, ema, n, ema_decay);
-}
-
-extern "C" int sdumc_adam_apply_ema_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                     const float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                                     uint32_t* rng_state, uint32_t rng_inc, const sdumc_total_loss* total,
-                                     const sdumc_rate_seg* segs, int32_t nseg, float* ema, float ema_decay, int32_t ema_warmup,
-                                     void* stream) {
-  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 144 <= 4096, "the table travels in the kernel arguments (4 KB)");
-  if (!hyper) return SDUMC_EINVAL;
-  const bool table = segs != nullptr || nseg != 0;
-  const int rc = sdumc_adam_ema_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay);
-  if (rc) return rc;
-  sdumc_total_loss tl;
-  tl.losses = nullptr;
-  tl.chain_err = nullptr;
-  tl.guard = nullptr;
-  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
-  if (total) tl = *total;
-  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();      // (as sdumc_adam_apply_)
-  const int64_t n4 = n / 4;
-  const int64_t threads = n4 > 0 ? n4 : 1;
-  const dim3 grid((unsigned)((threads + 255) / 256));
-  const int warm = ema_warmup != 0 ? 1 : 0;
-  if (table) {
-    rates_table tb;
-    memset(&tb, 0, sizeof(tb));
-    tb.nseg = nseg;
-    for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
-    hipLaunchKernelGGL((adam_rates_kernel<true, float*, float, int>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n4, n, hyper,
-                       beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb, ema, ema_decay, warm);
-  } else {
-    hipLaunchKernelGGL((adam_kernel<true, float*, float, int>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n4, n, hyper, beta1,
-                       beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, ema, ema_decay, warm);
-  }
-  SDUMC_CHECK_LAUNCH();
-  return SDUMC_OK;
+  if (!segs || nseg < 1) return SDUMC_EINVAL;      // (this entry's own: a table)
+  return adam_step_entry({param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u, nullptr,
+                          segs, nseg, nullptr, 0.f, 0, 0}, hyper, stream);
 }
 
 extern "C" int sdumc_adam_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper,
                                    float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                    const sdumc_rate_seg* segs, int32_t nseg, float* ema, float ema_decay, int32_t ema_warmup,
                                    void* stream) {
-  if (!hyper) return SDUMC_EINVAL;
-  int rc = sdumc_adam_ema_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay);   // (before the count advances)
-  if (rc) return rc;
-  rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
-  if (rc) return rc;
-  return sdumc_adam_apply_ema_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u,
-                               nullptr, segs, nseg, ema, ema_decay, ema_warmup, stream);
-}
-
-// what sdumc_adamw_apply_ refuses, without a launch (sdumc_train_step and sdumc_adamw_step ask before anything is enqueued): what the
-// coupled form of the same arguments refuses, and options of an average without one
-extern "C" int sdumc_adamw_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
-                                       const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay,
-                                       int32_t ema_warmup) {
-  if (ema) return sdumc_adam_ema_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay);
-  if (ema_decay != 0.f || ema_warmup != 0) return SDUMC_EINVAL;      // (a NaN decay compares unequal too)
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0) return SDUMC_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15)
-    return SDUMC_EINVAL;
-  if (segs != nullptr || nseg != 0) return rates_table_check(segs, nseg, n);
-  return SDUMC_OK;
-}
-
-// The decoupled form of whichever of the four flat-bucket launches these arguments name: sdumc_adam_apply_'s (no table, no average),
-// sdumc_adam_apply_rates_'s (a table), sdumc_adam_apply_ema_'s two (an average).
-extern "C" int sdumc_adamw_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
-                                  float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
-                                  uint32_t rng_inc, const sdumc_total_loss* total, const sdumc_rate_seg* segs, int32_t nseg,
-                                  float* ema, float ema_decay, int32_t ema_warmup, void* stream) {
-  static_assert(sizeof(rates_table) + sizeof(sdumc_total_loss) + 152 <= 4096, "the table travels in the kernel arguments (4 KB)");
-  if (!hyper) return SDUMC_EINVAL;
-  const int rc = sdumc_adamw_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay, ema_warmup);
-  if (rc) return rc;
-  sdumc_total_loss tl;
-  tl.losses = nullptr;
-  tl.chain_err = nullptr;
-  tl.guard = nullptr;
-  for (int i = 0; i < 6; ++i) tl.w[i] = 0.f;
-  if (total) tl = *total;
-  if (!tl.chain_err) tl.chain_err = sdumc_chain_cluster_err_ptr_();      // (as sdumc_adam_apply_)
-  const int64_t n4 = n / 4;
-  const int64_t threads = n4 > 0 ? n4 : 1;
-  const dim3 grid((unsigned)((threads + 255) / 256));
-  const int warm = ema_warmup != 0 ? 1 : 0;
-  rates_table tb;
-  memset(&tb, 0, sizeof(tb));
-  tb.nseg = nseg;
-  for (int32_t i = 0; i < nseg; ++i) tb.seg[i] = segs[i];
-  if (nseg != 0 && ema)
-    hipLaunchKernelGGL((adam_rates_kernel<true, float*, float, int, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad,
-                       exp_avg, exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb, ema,
-                       ema_decay, warm, decoupled{});
-  else if (nseg != 0)
-    hipLaunchKernelGGL((adam_rates_kernel<false, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq,
-                       n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, tb, decoupled{});
-  else if (ema)
-    hipLaunchKernelGGL((adam_kernel<true, float*, float, int, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg,
-                       exp_avg_sq, n4, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, ema, ema_decay,
-                       warm, decoupled{});
-  else
-    hipLaunchKernelGGL((adam_kernel<false, decoupled>), grid, dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n4, n,
-                       hyper, beta1, beta2, eps, weight_decay, grad_scale, rng_state, rng_inc, tl, decoupled{});
-  SDUMC_CHECK_LAUNCH();
-  return SDUMC_OK;
+  if (!ema) return SDUMC_EINVAL;      // (this entry's own: an average)
+  return adam_step_entry({param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u, nullptr,
+                          segs, nseg, ema, ema_decay, ema_warmup, 0}, hyper, stream);
 }
 
 extern "C" int sdumc_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float* hyper,
                                 float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                 const sdumc_rate_seg* segs, int32_t nseg, float* ema, float ema_decay, int32_t ema_warmup,
                                 void* stream) {
-  if (!hyper) return SDUMC_EINVAL;
-  int rc = sdumc_adamw_args_check_(param, grad, exp_avg, exp_avg_sq, n, segs, nseg, ema, ema_decay, ema_warmup);   // (before the count advances)
+  return adam_step_entry({param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u, nullptr,
+                          segs, nseg, ema, ema_decay, ema_warmup, 1}, hyper, stream);
+}
+
+namespace {
+// The per-parameter launches (sdumc_adam_multi, sdumc_adamw_multi, sdumc_ema_multi) walk their segment list in groups of
+// SDUMC_ADAM_MAX_SEGS, one launch each.  multi_grids_ok: no group's chunks of SDUMC_ADAM_CHUNK elements exceed one launch's grid (asked
+// before anything is enqueued; every n > 0).  multi_table: the table of the group that starts at segs[s0] -> its workgroups.
+template <class Seg>
+bool multi_grids_ok(const Seg* segs, int32_t nseg) {
+  uint64_t blocks = 0;
+  for (int32_t i = 0; i < nseg; ++i) {
+    if (i % SDUMC_ADAM_MAX_SEGS == 0) blocks = 0;
+    blocks += (uint64_t)((segs[i].n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
+    if (blocks > 0x7fffffffull) return false;
+  }
+  return true;
+}
+template <class Table, class Seg>
+uint32_t multi_table(Table& tb, const Seg* segs, int32_t nseg, int32_t s0) {
+  memset(&tb, 0, sizeof(tb));      // (segments behind the last one: null pointers, no elements)
+  tb.nseg = nseg - s0 < SDUMC_ADAM_MAX_SEGS ? nseg - s0 : SDUMC_ADAM_MAX_SEGS;
+  uint32_t blocks = 0;
+  for (int32_t i = 0; i < SDUMC_ADAM_MAX_SEGS; ++i) {
+    if (i < tb.nseg) {
+      tb.seg[i] = segs[s0 + i];
+      blocks += (uint32_t)((tb.seg[i].n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
+    }
+    tb.block_end[i] = blocks;
+  }
+  return blocks;
+}
+
+// sdumc_adam_multi (DEC false) and sdumc_adamw_multi (true): the same refusals, tables and grids, the kernel of either rule
+template <bool DEC>
+int adam_multi_launch(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len, float* hyper,
+                      float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream) {
+  static_assert(sizeof(sdumc_adam_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
+  if (!segs || nseg <= 0 || !exp_avg || !exp_avg_sq || !hyper || state_len <= 0) return SDUMC_EINVAL;
+  for (int32_t i = 0; i < nseg; ++i) {
+    const sdumc_adam_seg& s = segs[i];
+    if (!s.param || !s.grad || s.n <= 0 || s.state_offset < 0 || s.state_offset > state_len || s.n > state_len - s.state_offset)
+      return SDUMC_EINVAL;
+  }
+  if (!multi_grids_ok(segs, nseg)) return SDUMC_EINVAL;
+  int rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
   if (rc) return rc;
-  rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
-  if (rc) return rc;
-  return sdumc_adamw_apply_(param, grad, exp_avg, exp_avg_sq, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, nullptr, 0u,
-                            nullptr, segs, nseg, ema, ema_decay, ema_warmup, stream);
+  const int32_t* chain_err = sdumc_chain_cluster_err_ptr_();
+  for (int32_t s0 = 0; s0 < nseg; s0 += SDUMC_ADAM_MAX_SEGS) {
+    sdumc_adam_table tb;
+    const uint32_t blocks = multi_table(tb, segs, nseg, s0);
+    hipLaunchKernelGGL(adam_multi_kernel<DEC>, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
+                       beta2, eps, weight_decay, grad_scale, chain_err);
+    SDUMC_CHECK_LAUNCH();
+  }
+  return SDUMC_OK;
+}
+}  // namespace
+
+extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                                float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                void* stream) {
+  return adam_multi_launch<false>(segs, nseg, exp_avg, exp_avg_sq, state_len, hyper, beta1, beta2, eps, weight_decay, grad_scale,
+                                  stream);
+}
+
+extern "C" int sdumc_adamw_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
+                                 float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                 void* stream) {
+  return adam_multi_launch<true>(segs, nseg, exp_avg, exp_avg_sq, state_len, hyper, beta1, beta2, eps, weight_decay, grad_scale,
+                                 stream);
 }
 
 extern "C" int sdumc_ema_multi(const sdumc_ema_seg* segs, int32_t nseg, float weight, void* stream) {
   static_assert(sizeof(ema_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
   if (!segs || nseg <= 0 || !(weight >= 0.f && weight <= 1.f)) return SDUMC_EINVAL;
-  uint64_t blocks_of_launch = 0;
   for (int32_t i = 0; i < nseg; ++i) {
     const sdumc_ema_seg& s = segs[i];
     if (!s.ema || !s.param || s.n <= 0 || (reinterpret_cast<uintptr_t>(s.ema) & 3) || (reinterpret_cast<uintptr_t>(s.param) & 3))
       return SDUMC_EINVAL;
-    if (i % SDUMC_ADAM_MAX_SEGS == 0) blocks_of_launch = 0;
-    blocks_of_launch += (uint64_t)((s.n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
-    if (blocks_of_launch > 0x7fffffffull) return SDUMC_EINVAL;     // (one launch's grid)
   }
+  if (!multi_grids_ok(segs, nseg)) return SDUMC_EINVAL;
   for (int32_t s0 = 0; s0 < nseg; s0 += SDUMC_ADAM_MAX_SEGS) {
     ema_table tb;
-    tb.nseg = nseg - s0 < SDUMC_ADAM_MAX_SEGS ? nseg - s0 : SDUMC_ADAM_MAX_SEGS;
-    uint32_t blocks = 0;
-    for (int32_t i = 0; i < SDUMC_ADAM_MAX_SEGS; ++i) {
-      if (i < tb.nseg) {
-        tb.seg[i] = segs[s0 + i];
-        blocks += (uint32_t)((tb.seg[i].n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
-      } else {
-        tb.seg[i] = sdumc_ema_seg{nullptr, nullptr, 0};
-      }
-      tb.block_end[i] = blocks;
-    }
+    const uint32_t blocks = multi_table(tb, segs, nseg, s0);
     hipLaunchKernelGGL(ema_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, weight);
     SDUMC_CHECK_LAUNCH();
   }
@@ -792,65 +629,6 @@ extern "C" int sdumc_zero_segments(float* buf, int64_t n, const sdumc_rate_seg* 
   hipLaunchKernelGGL(zero_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), buf, tb);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
-}
-
-namespace {
-// sdumc_adam_multi (decoupled false) and sdumc_adamw_multi (true): the same refusals, tables and grids, the kernel of either rule
-int adam_multi_launch(const bool decoupled_decay, const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq,
-                      int64_t state_len, float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                      void* stream) {
-  static_assert(sizeof(sdumc_adam_table) + 64 <= 4096, "the table travels in the kernel arguments (4 KB)");
-  if (!segs || nseg <= 0 || !exp_avg || !exp_avg_sq || !hyper || state_len <= 0) return SDUMC_EINVAL;
-  uint64_t blocks_of_launch = 0;
-  for (int32_t i = 0; i < nseg; ++i) {
-    const sdumc_adam_seg& s = segs[i];
-    if (!s.param || !s.grad || s.n <= 0 || s.state_offset < 0 || s.state_offset > state_len || s.n > state_len - s.state_offset)
-      return SDUMC_EINVAL;
-    if (i % SDUMC_ADAM_MAX_SEGS == 0) blocks_of_launch = 0;
-    blocks_of_launch += (uint64_t)((s.n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
-    if (blocks_of_launch > 0x7fffffffull) return SDUMC_EINVAL;     // (one launch's grid)
-  }
-  int rc = sdumc_adam_hyper_(hyper, beta1, beta2, stream);
-  if (rc) return rc;
-  const int32_t* chain_err = sdumc_chain_cluster_err_ptr_();
-  for (int32_t s0 = 0; s0 < nseg; s0 += SDUMC_ADAM_MAX_SEGS) {
-    sdumc_adam_table tb;
-    tb.nseg = nseg - s0 < SDUMC_ADAM_MAX_SEGS ? nseg - s0 : SDUMC_ADAM_MAX_SEGS;
-    tb.reserved = 0;
-    uint32_t blocks = 0;
-    for (int32_t i = 0; i < SDUMC_ADAM_MAX_SEGS; ++i) {
-      if (i < tb.nseg) {
-        tb.seg[i] = segs[s0 + i];
-        blocks += (uint32_t)((tb.seg[i].n + SDUMC_ADAM_CHUNK - 1) / SDUMC_ADAM_CHUNK);
-      } else {
-        tb.seg[i] = sdumc_adam_seg{nullptr, nullptr, 0, 0};
-      }
-      tb.block_end[i] = blocks;
-    }
-    if (decoupled_decay)
-      hipLaunchKernelGGL(adamw_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
-                         beta2, eps, weight_decay, grad_scale, chain_err);
-    else
-      hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), tb, exp_avg, exp_avg_sq, hyper, beta1,
-                         beta2, eps, weight_decay, grad_scale, chain_err);
-    SDUMC_CHECK_LAUNCH();
-  }
-  return SDUMC_OK;
-}
-}  // namespace
-
-extern "C" int sdumc_adam_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
-                                float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                                void* stream) {
-  return adam_multi_launch(false, segs, nseg, exp_avg, exp_avg_sq, state_len, hyper, beta1, beta2, eps, weight_decay, grad_scale,
-                           stream);
-}
-
-extern "C" int sdumc_adamw_multi(const sdumc_adam_seg* segs, int32_t nseg, float* exp_avg, float* exp_avg_sq, int64_t state_len,
-                                 float* hyper, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                                 void* stream) {
-  return adam_multi_launch(true, segs, nseg, exp_avg, exp_avg_sq, state_len, hyper, beta1, beta2, eps, weight_decay, grad_scale,
-                           stream);
 }
 
 SDUMC_PRELOAD_HOOK(adam)      // (common.h)

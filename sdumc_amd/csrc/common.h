@@ -118,6 +118,24 @@ struct sdumc_total_loss {
   const int32_t* chain_err;   // chain_cluster.hip's error word (a cluster spin ran into its cap) or nullptr: poisons the total with NaN
   const float* guard;         // sdumc_grad_guard's float[4] or nullptr: guard[3] != 0 (a skipped step) applies nothing; the total stays
 };
+// the Adam launch over the flat bucket (adam.hip): the arguments of sdumc_adam_step and every option of its further forms
+struct sdumc_adam_launch {
+  float* param;
+  const float* grad;
+  float *exp_avg, *exp_avg_sq;                 // the four buffers: 16-byte aligned, n floats
+  int64_t n;
+  const float* hyper;                          // as sdumc_adam_hyper_ left it
+  float beta1, beta2, eps, weight_decay, grad_scale;
+  uint32_t* rng_state;                         // != NULL: its call counter advances by rng_inc in the same launch
+  uint32_t rng_inc;
+  const struct sdumc_total_loss* total;        // NULL: no loss record, no guard
+  const sdumc_rate_seg* segs;                  // sdumc_adam_step_rates' table (per-tensor step size and decay, frozen tensors) ...
+  int32_t nseg;                                // ... none: NULL and 0
+  float* ema;                                  // sdumc_adam_step_ema's averaged weights, decay and warm-up flag ...
+  float ema_decay;
+  int32_t ema_warmup;                          // ... none: NULL, 0, 0
+  int32_t decoupled;                           // 0: coupled L2; 1: sdumc_adamw_step's decoupled weight decay
+};
 extern "C" {
 // sdumc_zpool_bwd with dz := dz + dz_add (dz_add may be NULL): folds the external gradient of cross_fused_feat in
 int sdumc_zpool_bwd_add_(const float* h, const float* beta, const float* dz, const float* dz_add, float* dh, float* dbeta,
@@ -127,35 +145,10 @@ int sdumc_relu_drop_bwd_add_(const float* dy, const float* y, float scale, float
                              int32_t row_len, int32_t col0, int32_t width, void* stream);
 // the Adam bias-correction update alone (what sdumc_adam_step launches first) ...
 int sdumc_adam_hyper_(float* hyper, float beta1, float beta2, void* stream);
-// ... and the parameter update alone; rng_state != NULL: its call counter advances by rng_inc in the same launch
-int sdumc_adam_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
-                      float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
-                      uint32_t rng_inc, const struct sdumc_total_loss* total, void* stream);
-// ... the same with sdumc_adam_step_rates' segment table (per-tensor step size and decay, frozen tensors) ...
-int sdumc_adam_apply_rates_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
-                            float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
-                            uint32_t rng_inc, const struct sdumc_total_loss* total, const sdumc_rate_seg* segs, int32_t nseg,
-                            void* stream);
-// ... and what it would refuse for these arguments, without a launch
-int sdumc_adam_rates_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
-                            const sdumc_rate_seg* segs, int32_t nseg);
-// ... either of the two with the averaged weights (sdumc_adam_step_ema; segs NULL and nseg 0: sdumc_adam_apply_'s form) ...
-int sdumc_adam_apply_ema_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
-                          float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
-                          uint32_t rng_inc, const struct sdumc_total_loss* total, const sdumc_rate_seg* segs, int32_t nseg, float* ema,
-                          float ema_decay, int32_t ema_warmup, void* stream);
-// ... and what that would refuse, without a launch
-int sdumc_adam_ema_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
-                               const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay);
-// ... the decoupled form (sdumc_adamw_step) of whichever of those launches the arguments name (segs NULL and nseg 0: no table; ema
-// NULL: no average) ...
-int sdumc_adamw_apply_(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
-                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, uint32_t* rng_state,
-                       uint32_t rng_inc, const struct sdumc_total_loss* total, const sdumc_rate_seg* segs, int32_t nseg, float* ema,
-                       float ema_decay, int32_t ema_warmup, void* stream);
-// ... and what that would refuse, without a launch
-int sdumc_adamw_args_check_(const void* param, const void* grad, const void* exp_avg, const void* exp_avg_sq, int64_t n,
-                            const sdumc_rate_seg* segs, int32_t nseg, const void* ema, float ema_decay, int32_t ema_warmup);
+// ... and the parameter update alone, the step's last launch: ONE record names everything it can be asked for, one entry says what it
+// would refuse (no launch, nothing written), one entry makes it (and asks the first itself)
+int sdumc_adam_check_(const struct sdumc_adam_launch* launch);
+int sdumc_adam_apply_(const struct sdumc_adam_launch* launch, void* stream);
 // grad_guard.hip: what sdumc_grad_guard would refuse for these arguments, without a launch
 int sdumc_grad_guard_check_(const float* grads, int64_t n, float max_norm, int32_t skip_nonfinite, const float* hyper,
                             const void* scratch, const float* guard);

@@ -3111,8 +3111,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   if (!contrast_ok(cfg) || (cfg->contrast == SDUMC_CONTRAST_SUPCON && 2 * d->B > 2048)) return SDUMC_EINVAL;
   const StepLayout sl = step_layout(*d);
   char* base = static_cast<char*>(io->workspace);
-  // per-tensor rates (adam.hip): the segment table from the layout's own offsets; what the rates launch would refuse comes back here,
-  // like the other options' refusals before the workspace is looked at
+  // per-tensor rates (adam.hip): the segment table from the layout's own offsets (what the launch would refuse of it: the check below)
   sdumc_rate_seg rate_segs[SDUMC_RATES_MAX_SEGS];
   int32_t n_rate_segs = 0;
   bool any_frozen = false;
@@ -3128,7 +3127,6 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
       any_frozen = any_frozen || r.frozen[i];
     }
     if (n_rate_segs != r.n) return SDUMC_EINVAL;
-    RET(sdumc_adam_rates_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, rate_segs, n_rate_segs));
     auto frozen_at = [&](int64_t off) {
       for (int i = 0; i < n_rate_segs; ++i)
         if (rate_segs[i].offset == off) return rate_segs[i].frozen != 0;
@@ -3137,16 +3135,16 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
     for (int m = 0; m < 3; ++m)      // weight AND bias frozen: this modality's frame dW is not computed (plan_backward)
       if (frozen_at(pm.frame[m].w) && frozen_at(pm.frame[m].b)) frozen_frame_dw |= 1u << m;
   }
-  // averaged weights (adam.hip): the options belong to `ema`, and what the EMA launch would refuse comes back here too
+  // averaged weights (adam.hip): the options belong to `ema`; decoupled weight decay: 0 or 1
   if (!cfg->ema && (cfg->ema_decay != 0.f || cfg->ema_warmup != 0)) return SDUMC_EINVAL;
-  if (cfg->ema)
-    RET(sdumc_adam_ema_args_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live,
-                                   cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema, cfg->ema_decay));
-  // decoupled weight decay (adam.hip): 0 or 1, and the decoupled form of the last launch refuses what the launch it mirrors refuses
   if (cfg->decoupled_decay != 0 && cfg->decoupled_decay != 1) return SDUMC_EINVAL;
-  if (cfg->decoupled_decay)
-    RET(sdumc_adamw_args_check_(io->params, base + sl.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live,
-                                cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema, cfg->ema_decay, cfg->ema_warmup));
+  // the step's last launch, with every option this step names: what it would refuse comes back here, before the workspace is looked at
+  // and before anything is enqueued (the dropout counter and the loss record are filled in below)
+  sdumc_adam_launch adam = {io->params, reinterpret_cast<const float*>(base + sl.grads), cfg->adam_m, cfg->adam_v, (int64_t)sl.live,
+                            cfg->hyper, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, 1.0f, nullptr, 2u, nullptr,
+                            cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema, cfg->ema_decay, cfg->ema_warmup,
+                            cfg->decoupled_decay};
+  RET(sdumc_adam_check_(&adam));
   if (io->workspace_bytes < sl.total) return SDUMC_ENOMEM;
   // clipping and the non-finite guard (grad_guard.hip) are asked for through `guard`: options without it, and whatever
   // sdumc_grad_guard itself would refuse, come back before the forward is enqueued
@@ -3198,22 +3196,9 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   if (cfg->guard)
     RET(sdumc_grad_guard(g.grads, (int64_t)sl.live, cfg->clip_norm, cfg->skip_nonfinite, cfg->hyper, cfg->guard_scratch, cfg->guard,
                          stream));
-  uint32_t* rng = d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr;
-  const sdumc_total_loss* total = total_pending || cfg->guard ? &tl : nullptr;
-  if (cfg->decoupled_decay)      // the decoupled form of whichever of the launches below this step would have made
-    RET(sdumc_adamw_apply_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
-                           cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema,
-                           cfg->ema_decay, cfg->ema_warmup, stream));
-  else if (cfg->ema)      // the same launch with the averaged weights riding along (rate_segs: none without `rates`)
-    RET(sdumc_adam_apply_ema_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
-                              cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, cfg->rates ? rate_segs : nullptr, n_rate_segs, cfg->ema,
-                              cfg->ema_decay, cfg->ema_warmup, stream));
-  else if (cfg->rates)
-    RET(sdumc_adam_apply_rates_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
-                                cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, rate_segs, n_rate_segs, stream));
-  else
-    RET(sdumc_adam_apply_(io->params, g.grads, cfg->adam_m, cfg->adam_v, (int64_t)sl.live, cfg->hyper, cfg->beta1, cfg->beta2,
-                          cfg->eps, cfg->weight_decay, 1.0f, rng, 2u, total, stream));
+  adam.rng_state = d->train ? const_cast<uint32_t*>(io->rng_state) : nullptr;
+  adam.total = total_pending || cfg->guard ? &tl : nullptr;
+  RET(sdumc_adam_apply_(&adam, stream));
   mark(static_cast<hipStream_t>(stream), 10);
   return SDUMC_OK;      // (the backward's last act joined lane 3: the next batch's assembly, too, is ordered before whatever follows)
 }

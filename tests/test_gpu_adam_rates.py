@@ -252,5 +252,8 @@ def test_refusals_write_nothing(ops):
     assert lib.sdumc_adam_step_rates(odd.data_ptr(), *[b.data_ptr() for b in bufs[1:]], n, hyper.data_ptr(), 0.9, 0.999, 1e-8, 1e-5, 1.0,
                                      tb, 1, _lib.current_stream()) == -1
     assert lib.sdumc_zero_segments(odd.data_ptr(), n, tb, 1, _lib.current_stream()) == -1
+    # ... and sdumc_adam_step itself refuses it before the step count advances (hyper is compared below)
+    assert lib.sdumc_adam_step(odd.data_ptr(), *[b.data_ptr() for b in bufs[1:]], n, hyper.data_ptr(), 0.9, 0.999, 1e-8, 1e-5, 1.0,
+                               _lib.current_stream()) == -1
     torch.cuda.synchronize()
     assert bool((odd == -55.0).all()) and hyper.tolist() == [np.float32(1e-3), 5.0, 0.25, 0.5]

@@ -1,5 +1,5 @@
 """Decoupled weight decay at the kernel level: sdumc_adamw_step (the decoupled forms of adam_kernel and adam_rates_kernel, with and
-without the averaged weights), sdumc_adamw_multi (adamw_multi_kernel) and sdumc_amd.optim.AdamW, against the kernels that were there
+without the averaged weights), sdumc_adamw_multi (adam_multi_kernel<true>) and sdumc_amd.optim.AdamW, against the kernels that were there
 before -- bit for bit -- and against torch.optim.AdamW in float64.
 
 The buffer is the one of tests/test_gpu_adam_rates.py, restated: ONE flat buffer of N (about 40 k) floats, segments of 1, 3, 7, 64, 255,

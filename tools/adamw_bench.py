@@ -14,14 +14,14 @@ call (the one-thread hyper launch in front of each included, as the C entries ma
 sdumc_adam_step / _rates / _ema without and with a table of ones, sdumc_adam_multi over the layout's live tensors -- then the drop-in
 loop's step() over those tensors with gradients: sdumc_amd.optim.Adam, sdumc_amd.optim.AdamW, torch.optim.AdamW(foreach=True) and
 torch.optim.AdamW(foreach=False), microseconds per step() by the same events (the host's share included: that is what a loop pays).
-`parent` times `off` and the coupled kernels alone -- ONE trainer in the process; with SDUMC_LIB=<the parent build's libsdumc_hip.so>
-on that library (it has no sdumc_adamw_step).
+`parent` times `off` and the kernels alone -- ONE trainer in the process, no drop-in loops; with SDUMC_LIB=<the parent build's
+libsdumc_hip.so> on that library (the decoupled entries are timed on whichever library has them, sdumc_ema_multi beside them).
 ab=<that library>: the A/B itself -- `pairs` times a fresh process of `parent` on the parent's library and the same `parent` process
 on this tree (like for like: one trainer, one leg; the two swap places from pair to pair), then this tree's four legs, one process at a
 time (fresh child processes: the library is chosen when sdumc_amd is imported) -- and one JSON line with both sides' `off` epochs, the
 run-to-run spread BETWEEN the parent's processes (best epoch of each: the yardstick for "off costs nothing"), tree over parent, the
-tree's legs, and each decoupled kernel beside the PARENT library's kernel of the same form with the spread between the parent's
-processes.
+tree's legs, and every kernel form of the two like-for-like processes side by side with the spread between the parent's processes (a
+decoupled form the parent's library lacks stands beside its coupled kernel of the same form).
 usage: python tools/adamw_bench.py [n=2048] [B=64] [bf16] [rounds=5] [parent] [ab=<parent .so>] [pairs=3]"""
 import json
 import os
@@ -76,7 +76,10 @@ def kernels(engine, layout, dev, parent, calls=200):
             "adam_step_ema_rates_ones": lambda: chk(lib.sdumc_adam_step_ema(*ptrs, *adam, ones, len(ones), a.data_ptr(), DECAY, 0, st),
                                                     "sdumc_adam_step_ema"),
             "adam_multi": lambda: chk(lib.sdumc_adam_multi(msegs, *multi), "sdumc_adam_multi")}
-    if not parent:
+    avg = full.clone()      # (kept: the table holds addresses)
+    esegs = ops.ema_segments(_views(layout, avg), params)
+    runs["ema_multi"] = lambda: chk(lib.sdumc_ema_multi(esegs, len(params), 1.0 - DECAY, st), "sdumc_ema_multi")
+    if _lib.ADAMW_ABI:      # (whichever library has the decoupled entries: an A/B is then like for like on every form)
         w = lib.sdumc_adamw_step
         runs.update({"adamw_step": lambda: chk(w(*ptrs, *adam, None, 0, None, 0.0, 0, st), "sdumc_adamw_step"),
                      "adamw_step_rates_ones": lambda: chk(w(*ptrs, *adam, ones, len(ones), None, 0.0, 0, st), "sdumc_adamw_step"),
@@ -84,7 +87,7 @@ def kernels(engine, layout, dev, parent, calls=200):
                      "adamw_step_ema_rates_ones": lambda: chk(w(*ptrs, *adam, ones, len(ones), a.data_ptr(), DECAY, 0, st),
                                                               "sdumc_adamw_step"),
                      "adamw_multi": lambda: chk(lib.sdumc_adamw_multi(msegs, *multi), "sdumc_adamw_multi")})
-
+    if not parent:
         def loop(cls, **kw):      # the drop-in loop's optimizer line over the live tensors, gradients in place
             ps = [torch.nn.Parameter(t.clone()) for t in params]
             for q, gr in zip(ps, grads):
@@ -207,15 +210,17 @@ def ab(args, parent_lib):
         out[name] = {"ms_per_step": [r[name]["ms_per_step"] for r in runs["tree"]],
                      "extra_us_per_step_best": [r[name]["extra_us_per_step_best"] for r in runs["tree"]],
                      "extra_us_per_step_median_of_rounds": [r[name]["extra_us_per_step_median_of_rounds"] for r in runs["tree"]]}
-    # each decoupled kernel beside the PARENT library's kernel of the same form
+    # every form both libraries have, like for like (the same one-trainer process on either side), with the spread between the parent's
+    # processes; a decoupled form the parent lacks stands beside the parent's coupled kernel of the same form
     forms = {}
-    for form in FORMS:
-        par = [r["kernels_us_per_call"][form] for r in runs["parent"]]
-        same = [r["kernels_us_per_call"][form] for r in runs["tree"]]
-        dec = [r["kernels_us_per_call"][form.replace("adam_", "adamw_", 1)] for r in runs["tree"]]
-        forms[form] = {"parent_us": par, "tree_us": same, "decoupled_us": dec, "parent_process_spread": round(max(par) / min(par) - 1, 4),
-                       "decoupled_over_parent_best": round(min(dec) / min(par) - 1, 4),
-                       "decoupled_over_parent_median": round(med(dec) / med(par) - 1, 4)}
+    for form in FORMS + tuple(f.replace("adam_", "adamw_", 1) for f in FORMS) + ("ema_multi",):
+        tree = [r["kernels_us_per_call"][form] for r in runs["tree_off"]]
+        beside = form if form in runs["parent"][0]["kernels_us_per_call"] else form.replace("adamw_", "adam_", 1)
+        par = [r["kernels_us_per_call"][beside] for r in runs["parent"]]
+        forms[form] = {"parent_form": beside, "parent_us": par, "tree_us": tree,
+                       "parent_process_spread": round(max(par) / min(par) - 1, 4),
+                       "tree_over_parent_best": round(min(tree) / min(par) - 1, 4),
+                       "tree_over_parent_median": round(med(tree) / med(par) - 1, 4)}
     out["kernels"] = forms
     out["loop_step_us"] = {k: [r["kernels_us_per_call"][k] for r in runs["tree"]] for k in runs["tree"][0]["kernels_us_per_call"]
                            if k.endswith(".step")}
