@@ -580,6 +580,27 @@ int sdumc_zpool_bwd(const float* h, const float* beta, const float* dz, float* d
 int sdumc_mse_fwd_bwd(const float* pred, const float* target, int32_t rows, float denom, float weight,
                       float* loss_out, float* dpred, void* stream);
 
+/* The regression criteria beside MSELoss, value and gradient in one launch of one workgroup (fixed summation order, bitwise
+ * reproducible).  d_i = pred_i - target_i in fp32, inv = fp32(1 / denom), denom as for sdumc_mse_fwd_bwd:
+ *   SDUMC_REGRESS_MSE    sdumc_mse_fwd_bwd's launch, bit for bit
+ *   SDUMC_REGRESS_L1     torch.nn.L1Loss under MSELoss's reduction: sum |d_i| / denom; dpred_i = (weight * sign(d_i)) * inv,
+ *                        sign(0) = 0, a NaN d_i gives NaN
+ *   SDUMC_REGRESS_HUBER  torch.nn.HuberLoss(delta) likewise: h_i = 0.5 d_i^2 where |d_i| <= delta, delta (|d_i| - 0.5 delta)
+ *                        elsewhere; dpred_i = (weight * g_i) * inv, g_i = d_i or delta * sign(d_i)
+ *   SDUMC_REGRESS_CCC    1 - concordance correlation coefficient = 1 - 2 s_py / (s_pp + s_yy + (m_p - m_y)^2), population
+ *                        moments over the `rows` elements (denom is not read), accumulated in double in two passes; dpred_i =
+ *                        weight * fp32(dLoss/dpred_i in double).  pred and target one shared constant: 0/0 = NaN, value and
+ *                        gradient; rows = 1: value 1, gradient +0.
+ * loss_out (device scalar) is WRITTEN with the unweighted value (L1 / Huber: the local sum / denom); dpred ([rows], overwritten)
+ * may be NULL.  SDUMC_EINVAL before a launch: a NULL pred / target / loss_out, rows < 1, denom <= 0, an unknown code, delta not
+ * positive and finite under HUBER (delta is read by HUBER alone). */
+#define SDUMC_REGRESS_MSE 0
+#define SDUMC_REGRESS_L1 1
+#define SDUMC_REGRESS_HUBER 2
+#define SDUMC_REGRESS_CCC 3
+int sdumc_reg_fwd_bwd(const float* pred, const float* target, int32_t rows, float denom, float weight, int32_t regress,
+                      float delta, float* loss_out, float* dpred, void* stream);
+
 /* Sum of squared differences, for RMSELoss (loss.py:37-51) = sqrt(ssd / numel).
  * Splitting ssd from the sqrt lets data-parallel ranks all-reduce ssd first. */
 int sdumc_ssd(const float* a, const float* b, int64_t n, float* ssd_out, float* workspace, void* stream);
@@ -1501,7 +1522,16 @@ typedef struct sdumc_step_cfg {
   void* guard_scratch;   /* sdumc_grad_guard_scratch_bytes(live count) bytes, 16-byte aligned */
   /* data-parallel exactness; all zero/NULL on one GPU */
   int32_t B_global;      /* 0 -> B */
-  const float* ssd_global;        /* device float[3]: all-reduced sums of squared differences (text, query, fused) */
+  /* The criterion of the two regression terms (losses[1], losses[2], weights[0], weights[1]; main :137-138): SDUMC_REGRESS_MSE (0 =
+   * a zeroed struct) the step as it always was, launch for launch and bit for bit; _L1, _HUBER (with regress_delta, the struct's
+   * last four bytes) and _CCC as sdumc_reg_fwd_bwd has them, computed by the workgroups of the loss stage that held the MSE terms:
+   * no further launch.  L1 / Huber entries are the LOCAL sum / B_global like the MSE entries.  SDUMC_EINVAL before a launch: a code
+   * outside 0..3, a regress_delta that is not positive and finite under _HUBER (it is read by _HUBER alone), _CCC with B_global
+   * set and different from B (its moments would need an exchange that is not built).
+   * (In the four bytes that were padding between B_global and ssd_global, as regress_delta is in the four behind `distill`: no
+   * other field moves and sizeof stays, which tests pin together with `distill` as the last declaration.) */
+  int32_t regress;
+  const float* ssd_global;       /* device float[3]: all-reduced sums of squared differences (text, query, fused) */
   const float* rnc_feats_global;  /* [2*B_global, 64] = cat(r_stream0 of all ranks, r_stream1 of all ranks) */
   const float* rnc_labels_global; /* [2*B_global] */
   /* Per-tensor learning rates, decay and frozen tensors (sdumc_adam_step_rates, which see); NULL = the step without them, launch
@@ -1541,8 +1571,9 @@ typedef struct sdumc_step_cfg {
    * SDUMC_DISTILL_RMSE (0 = a zeroed struct) RMSELoss, _COSINE CosineSimilarityLoss4Seq, _KL KLLoss; anything else:
    * SDUMC_EINVAL before a launch.  losses[3..5] hold the chosen criterion's values.  Cosine and KL are sums over rows
    * divided by B_global: like the MSE entries, a data-parallel rank writes its LOCAL sum / B_global and ssd_global is
-   * not read. */
-  int32_t distill;
+   * not read.
+   * regress_delta: Huber's delta of `regress` (which see), in what was the struct's tail padding. */
+  int32_t distill; float regress_delta;
 } sdumc_step_cfg;
 #define SDUMC_DISTILL_RMSE 0
 #define SDUMC_DISTILL_COSINE 1

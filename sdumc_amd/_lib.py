@@ -249,11 +249,59 @@ class StepCfg(C.Structure):
                 _ADAMW_FIELDS if ADAMW_ABI else []) + [
                 ("labels", C.c_void_p), ("adam_m", C.c_void_p), ("adam_v", C.c_void_p), ("hyper", C.c_void_p),
                 ("losses", C.c_void_p)] + (_GUARD_FIELDS if GUARD_ABI else []) + [
-                ("B_global", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
+                ("B_global", C.c_int32), ("regress", C.c_int32), ("ssd_global", C.c_void_p), ("rnc_feats_global", C.c_void_p),
                 ("rnc_labels_global", C.c_void_p)] + (_RATES_FIELDS if RATES_ABI else []) + (
                 _EMA_FIELDS if EMA_ABI else []) + [("rnc_row0", C.c_int32 * 2),
                 ("contrast", C.c_int32), ("supcon_label_mode", C.c_int32), ("supcon_temperature", C.c_float),
                 ("supcon_base_temperature", C.c_float), ("distill", C.c_int32)]
+
+    # sdumc_step_cfg.regress_delta: the float in the struct's last four bytes, behind `distill` -- tail padding until now, so sizeof
+    # and every offset stay (`regress` likewise fills the padding behind B_global; an older library reads neither).  `distill` stays
+    # the mirror's last entry, which tests pin: the field is reached at its offset.
+    @property
+    def regress_delta(self):
+        return C.c_float.from_buffer(self, StepCfg.distill.offset + 4).value
+
+    @regress_delta.setter
+    def regress_delta(self, v):
+        C.c_float.from_buffer(self, StepCfg.distill.offset + 4).value = v
+
+
+REGRESS_DELTA_OFFSET = StepCfg.distill.offset + 4
+assert REGRESS_DELTA_OFFSET + 4 == C.sizeof(StepCfg)
+
+
+def _regress_abi():
+    """False only for an A/B against an older build (SDUMC_LIB, tools/regress_bench.py) from before sdumc_reg_fwd_bwd: that library
+    reads sdumc_step_cfg's two regression fields as padding and would silently run MSE, so regress != 'mse' raises on the host."""
+    if not os.environ.get("SDUMC_LIB") or not os.path.exists(LIB_PATH):
+        return True
+    return hasattr(C.CDLL(LIB_PATH), "sdumc_reg_fwd_bwd")
+
+
+REGRESS_ABI = _regress_abi()
+
+# sdumc_step_cfg.regress: the criterion of the two regression terms (SDUMC_REGRESS_* of include/sdumc_hip.h)
+REGRESS = {"mse": 0, "l1": 1, "huber": 2, "ccc": 3}
+
+
+def regress_args(regress, regress_delta=1.0):
+    """TrainStep / FusedTrainer (regress=, regress_delta=) -> (sdumc_step_cfg.regress, .regress_delta).  regress: one of REGRESS;
+    regress_delta: Huber's delta, a positive finite Python number (no bool, no string, no tensor) that is positive and finite as
+    fp32 too; it is read by 'huber' alone, so anything but the default 1.0 beside another criterion raises."""
+    import math
+    if not isinstance(regress, str) or regress not in REGRESS:
+        raise SdumcError(f"regress must be one of {sorted(REGRESS)}, not {regress!r}")
+    d = regress_delta
+    if isinstance(d, bool) or not isinstance(d, (int, float)) or not math.isfinite(d) or d <= 0:
+        raise SdumcError(f"regress_delta must be a positive finite number, not {d!r}")
+    if C.c_float(d).value in (0.0, float("inf")):      # (what the kernel would see)
+        raise SdumcError(f"regress_delta must be a positive finite fp32 value, not {d!r}")
+    if regress != "huber" and d != 1.0:
+        raise SdumcError(f"regress_delta is read by regress='huber' alone, not by {regress!r}")
+    if regress != "mse" and not REGRESS_ABI:
+        raise SdumcError("regress: the library named by SDUMC_LIB is from before sdumc_reg_fwd_bwd")
+    return REGRESS[regress], float(d)
 
 
 # sdumc_step_cfg.distill: the criterion of the three distillation pairs (SDUMC_DISTILL_* of include/sdumc_hip.h)
@@ -488,6 +536,8 @@ _SIGS = {
     "sdumc_zpool_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "sdumc_zpool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "sdumc_mse_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sdumc_reg_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "sdumc_ssd_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "sdumc_ssd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdumc_rmse_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_float, C.c_void_p,

@@ -208,6 +208,12 @@ struct sdumc_chain_args {
   uint32_t* cl_dbg;               // diagnosis records (sdumc_chain_cluster_debug_read_)
 };
 
+// a known SDUMC_REGRESS_* code and, under Huber, a positive finite delta: loss.hip's entries and the step's early refusals
+inline bool sdumc_regress_valid(int32_t regress, float delta) {
+  if (regress < SDUMC_REGRESS_MSE || regress > SDUMC_REGRESS_CCC) return false;
+  return regress != SDUMC_REGRESS_HUBER || (delta > 0.f && delta < __builtin_inff());
+}
+
 extern "C" {
 // loss.hip: the six loss launches of a single-GPU step in two (1 = shape not taken)
 // hyper != nullptr: the second pass also makes the Adam bias-correction update of this step (as total_loss_kernel did)
@@ -215,10 +221,21 @@ int sdumc_losses_fused_(int32_t B, const float* vals, const float* labels, const
                         const float* rnc_feats, int32_t rd, float temperature, const float* weights6, float* d_vals, float* d_th,
                         float* d_ct, float* d_z, float* d_rnc, float* losses, float* distill_ws, float* rnc_workspace,
                         float* hyper, double beta1, double beta2, int32_t distill, void* stream);
+// ... with the criterion of the two regression terms (SDUMC_REGRESS_*, Huber's delta): sdumc_losses_fused_ is its MSE case
+int sdumc_losses_fused_reg_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct, const float* z,
+                            const float* rnc_feats, int32_t rd, float temperature, const float* weights6, float* d_vals,
+                            float* d_th, float* d_ct, float* d_z, float* d_rnc, float* losses, float* distill_ws,
+                            float* rnc_workspace, float* hyper, double beta1, double beta2, int32_t distill, int32_t regress,
+                            float regress_delta, void* stream);
 // loss.hip: sdumc_distill_fwd_bwd with the criterion of the three pairs (SDUMC_DISTILL_*)
 int sdumc_distill_crit_(int32_t B, float denom, const float* vals, const float* labels, const float* th, const float* ct,
                         const float* z, const float* weights5, const float* ssd_global, float* d_vals, float* d_th, float* d_ct,
                         float* d_z, float* losses, float* workspace, int32_t distill, void* stream);
+// ... with the criterion of the two regression terms: sdumc_distill_crit_ is its MSE case
+int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals, const float* labels, const float* th, const float* ct,
+                            const float* z, const float* weights5, const float* ssd_global, float* d_vals, float* d_th,
+                            float* d_ct, float* d_z, float* losses, float* workspace, int32_t distill, int32_t regress,
+                            float regress_delta, void* stream);
 // which: 0 = stage A forward, 1 = stage B forward, 2 = stage B backward, 3 = stage A backward
 int sdumc_chain_launch_(const sdumc_chain_args* a, int which, void* stream);
 // the same four stages with every layer's output columns split over clusters of 4 workgroups (chain_cluster.hip);

@@ -2988,6 +2988,12 @@ bool contrast_ok(const sdumc_step_cfg* cfg) {
   return !cfg->rnc_feats_global && cfg->supcon_temperature > 0.f && cfg->supcon_base_temperature >= 0.f &&
          cfg->supcon_label_mode >= 0 && cfg->supcon_label_mode <= 1;
 }
+// the regression criterion of a step: known, Huber's delta positive and finite, and CCC not over a share of a larger batch (its
+// moments are the whole batch's: an exchange that is not built)
+bool regress_ok(const sdumc_step_cfg* cfg, int B) {
+  if (!sdumc_regress_valid(cfg->regress, cfg->regress_delta)) return false;
+  return cfg->regress != SDUMC_REGRESS_CCC || cfg->B_global <= 0 || cfg->B_global == B;
+}
 }
 extern "C" int sdumc_loss_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
                                    const sdumc_net_grads* g, void* scratch, size_t scratch_bytes, void* stream) {
@@ -3004,7 +3010,7 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   if (!g->d_vals || !g->d_fused || !g->d_rnc || !g->d_text_hidden || !g->d_cross_text) return SDUMC_EINVAL;
   if (!cfg->labels || !cfg->losses) return SDUMC_EINVAL;
   if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;
-  if (!contrast_ok(cfg)) return SDUMC_EINVAL;
+  if (!contrast_ok(cfg) || !regress_ok(cfg, d->B)) return SDUMC_EINVAL;
   const bool supcon = cfg->contrast == SDUMC_CONTRAST_SUPCON;
   hipStream_t st = as_stream(stream);
   const int B = d->B, Bg = cfg->B_global > 0 ? cfg->B_global : B;
@@ -3024,10 +3030,10 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   // single GPU (no global sums / features handed in): the distillation terms and RnC share their two passes (loss.hip)
   bool done = false;
   if (!supcon && !cfg->rnc_feats_global && !cfg->ssd_global && Bg == B) {
-    const int rc = sdumc_losses_fused_(B, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, io->rnc, RD,
-                                       cfg->temperature, w, dv, dth, dct, df, dr, L, ls.ssd_ws, ls.rnc_ws,
-                                       total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2, cfg->distill,
-                                       stream);
+    const int rc = sdumc_losses_fused_reg_(B, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, io->rnc, RD,
+                                           cfg->temperature, w, dv, dth, dct, df, dr, L, ls.ssd_ws, ls.rnc_ws,
+                                           total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2, cfg->distill,
+                                           cfg->regress, cfg->regress_delta, stream);
     if (rc < 0) return rc;
     done = rc == 0;
     if (done && total_pending && hyper) {
@@ -3038,8 +3044,8 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   if (!done) {
   // MSELoss x2 (main :137-138) + the distillation criterion x3 (main :148; teacher side detached for text_feat /
   // text_query_feat, not for features): value and gradients in two launches
-  RET(sdumc_distill_crit_(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
-                          cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, cfg->distill, stream));
+  RET(sdumc_distill_crit_reg_(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
+                              cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, cfg->distill, cfg->regress, cfg->regress_delta, stream));
   // RnCLoss over cat(r_stream0, r_stream1) with labels repeated (main :134,:140; loss.py:282-283)
   if (supcon) {
     // SupConLoss instead (loss.py:143-240): the two streams are the two views of a sample, rows normalised in the kernel
@@ -3109,6 +3115,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   if (!cfg || d->streams != 2 || !cfg->adam_m || !cfg->adam_v || !cfg->hyper) return SDUMC_EINVAL;
   if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;   // before anything is launched
   if (!contrast_ok(cfg) || (cfg->contrast == SDUMC_CONTRAST_SUPCON && 2 * d->B > 2048)) return SDUMC_EINVAL;
+  if (!regress_ok(cfg, d->B)) return SDUMC_EINVAL;
   const StepLayout sl = step_layout(*d);
   char* base = static_cast<char*>(io->workspace);
   // per-tensor rates (adam.hip): the segment table from the layout's own offsets (what the launch would refuse of it: the check below)

@@ -33,6 +33,103 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* pred, const float
   if (threadIdx.x == 0) *loss_out = s * inv;
 }
 
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double block_sum_256_d(double v, double* red /*[4]*/) {
+  v = wave_sum_d(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+// ---- the regression criterion of main :137-138 beside MSELoss (SDUMC_REGRESS_*): one helper per criterion, the element's term
+// and its gradient before the weight and 1 / denom.  d = pred - target in fp32.  The gradient expressions hold no addition (no
+// contraction can change them): a fp32 host expression reproduces them bit for bit.
+__device__ __forceinline__ float reg_sign(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == d ? 0.f : d)); }   // sign(0) = 0, NaN stays NaN
+// torch.nn.L1Loss: |d|, sign(d)
+__device__ __forceinline__ void l1_elem(float d, float& h, float& g) {
+  h = fabsf(d);
+  g = reg_sign(d);
+}
+// torch.nn.HuberLoss(delta): 0.5 d^2, d inside |d| <= delta; delta (|d| - 0.5 delta), delta sign(d) outside (a NaN d compares false:
+// the outer forms, which keep it)
+__device__ __forceinline__ void huber_elem(float d, float delta, float& h, float& g) {
+  const float ad = fabsf(d);
+  if (ad <= delta) {
+    h = 0.5f * d * d;
+    g = d;
+  } else {
+    h = delta * (ad - 0.5f * delta);
+    g = delta * reg_sign(d);
+  }
+}
+// Concordance correlation coefficient, 1 - 2 s_py / (s_pp + s_yy + (m_p - m_y)^2) with population moments over the n elements: a
+// whole-stream quantity, so the ONE workgroup that owns the stream makes two passes with double accumulators (the means, then the
+// centred sums: thread-strided partials, wave reduce, the four wave sums in index order) and a third for the gradient, each
+// element's in double, rounded to fp32 once and then multiplied by the weight.  No special cases: D == 0 is 0/0 = NaN; n = 1 gives
+// value 1 and gradient +0 (0.0 - x negates like -x except that it turns -0 into +0).
+__device__ __forceinline__ void ccc_stream(const float* p, const float* y, int n, float w, float* loss_out, float* dp) {
+  __shared__ double red[4];
+  double sp = 0.0, sy = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    sp += (double)p[i];
+    sy += (double)y[i];
+  }
+  sp = block_sum_256_d(sp, red);
+  sy = block_sum_256_d(sy, red);
+  const double nn = (double)n, mp = sp / nn, my = sy / nn;
+  double spp = 0.0, syy = 0.0, spy = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double a = (double)p[i] - mp, b = (double)y[i] - my;
+    spp += a * a;
+    syy += b * b;
+    spy += a * b;
+  }
+  spp = block_sum_256_d(spp, red) / nn;
+  syy = block_sum_256_d(syy, red) / nn;
+  spy = block_sum_256_d(spy, red) / nn;
+  const double dm = mp - my;
+  const double D = spp + syy + dm * dm, N = 2.0 * spy;
+  if (threadIdx.x == 0) *loss_out = (float)(1.0 - N / D);
+  if (!dp) return;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const double dN = 2.0 * ((double)y[i] - my) / nn;
+    const double dD = 2.0 * ((double)p[i] - mp) / nn + 2.0 * dm / nn;
+    const double g = 0.0 - (dN * D - N * dD) / (D * D);
+    dp[i] = w * (float)g;
+  }
+}
+// One stream of `rows` elements under criterion reg != MSE, by one workgroup of 256: value -> *loss_out, weight * gradient -> dpred
+// (may be null).  L1 / Huber sum in fp32 in the order and with the helper of the MSE form; their value is the LOCAL sum / denom.
+__device__ __forceinline__ void reg_stream(int reg, float delta, const float* pred, const float* target, int rows, float denom,
+                                           float weight, float* loss_out, float* dpred, float* red /*[4]*/) {
+  if (reg == SDUMC_REGRESS_CCC) {
+    ccc_stream(pred, target, rows, weight, loss_out, dpred);
+    return;
+  }
+  const float inv = 1.f / denom;
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    const float d = pred[i] - target[i];
+    float h, g;
+    if (reg == SDUMC_REGRESS_L1) l1_elem(d, h, g);
+    else huber_elem(d, delta, h, g);
+    acc += h;
+    if (dpred) dpred[i] = (weight * g) * inv;
+  }
+  const float s = block_sum_256(acc, red);
+  if (threadIdx.x == 0) *loss_out = s * inv;
+}
+__global__ __launch_bounds__(256) void reg_kernel(int reg, float delta, const float* pred, const float* target, int rows, float denom,
+                                                  float weight, float* loss_out, float* dpred) {
+  __shared__ float red[4];
+  reg_stream(reg, delta, pred, target, rows, denom, weight, loss_out, dpred, red);
+}
+
 constexpr int SSD_CHUNK = 8192;
 __global__ __launch_bounds__(256) void ssd_stage1(const float* a, const float* b, int64_t n, float* part) {
   __shared__ float red[4];
@@ -710,6 +807,8 @@ struct DistillArgs {
   float* part;      // [3][nblk]
   int nblk[3];
   int crit;         // SDUMC_DISTILL_*: uniform per launch
+  int reg;          // SDUMC_REGRESS_*: the criterion of the two regression terms, uniform per launch
+  float reg_delta;  // Huber's delta (read by SDUMC_REGRESS_HUBER alone)
 };
 constexpr int DCH = 4096;   // elements per block
 static_assert(DCH % SDUMC_D == 0 && DCH % SDUMC_H == 0 && SDUMC_D <= ROW_MAXW && SDUMC_H <= ROW_MAXW,
@@ -794,6 +893,11 @@ __device__ __forceinline__ void distill_apply_body(const DistillArgs a, const in
   if (p == 3) {   // MSELoss on both streams (loss.py:19-33): value + gradient
     if (bx > 1) return;
     const int sidx = bx;
+    if (a.reg != SDUMC_REGRESS_MSE) {   // L1 / Huber / CCC instead (sdumc_step_cfg.regress): the same workgroup, no further launch
+      reg_stream(a.reg, a.reg_delta, a.vals + sidx * a.B, a.labels, a.B, a.denom, a.w[sidx], a.losses + 1 + sidx,
+                 a.d_vals + sidx * a.B, red);
+      return;
+    }
     const float inv = 1.f / a.denom;
     float acc = 0.f;
     for (int i = threadIdx.x; i < a.B; i += 256) {
@@ -971,6 +1075,18 @@ extern "C" int sdumc_mse_fwd_bwd(const float* pred, const float* target, int32_t
   return SDUMC_OK;
 }
 
+extern "C" int sdumc_reg_fwd_bwd(const float* pred, const float* target, int32_t rows, float denom, float weight, int32_t regress,
+                                 float delta, float* loss_out, float* dpred, void* stream) {
+  if (!pred || !target || !loss_out || rows < 1 || !(denom > 0.f) || !sdumc_regress_valid(regress, delta)) return SDUMC_EINVAL;
+  if (regress == SDUMC_REGRESS_MSE)
+    hipLaunchKernelGGL(mse_kernel, dim3(1), dim3(256), 0, as_stream(stream), pred, target, rows, denom, weight, loss_out, dpred);
+  else
+    hipLaunchKernelGGL(reg_kernel, dim3(1), dim3(256), 0, as_stream(stream), regress, delta, pred, target, rows, denom, weight,
+                       loss_out, dpred);
+  SDUMC_CHECK_LAUNCH();
+  return SDUMC_OK;
+}
+
 extern "C" size_t sdumc_ssd_workspace_bytes(int64_t n) { return (size_t)((n + SSD_CHUNK - 1) / SSD_CHUNK) * sizeof(float); }
 
 extern "C" int sdumc_ssd(const float* a, const float* b, int64_t n, float* ssd_out, float* workspace, void* stream) {
@@ -1059,16 +1175,20 @@ extern "C" size_t sdumc_distill_workspace_bytes(int32_t B) {
 
 // MSE x2 + the chosen criterion x3 of main :137-148 (value + gradients w.r.t. the network outputs) in two launches.
 // distill != RMSE: ssd_global is not read (the value is a sum over local rows / denom) and pass 1 always runs.
-extern "C" int sdumc_distill_crit_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
-                                   const float* ct, const float* z, const float* weights5, const float* ssd_global,
-                                   float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
-                                   int32_t distill, void* stream) {
+// regress: the criterion of the two regression terms (SDUMC_REGRESS_*; the p == 3 workgroups of the second launch).
+extern "C" int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                       const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                       float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                       int32_t distill, int32_t regress, float regress_delta, void* stream) {
   if (B <= 0 || denom <= 0.f || !vals || !labels || !th || !ct || !z || !weights5 || !d_vals || !d_th || !d_ct || !d_z ||
-      !losses || !workspace || distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL)
+      !losses || !workspace || distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL ||
+      !sdumc_regress_valid(regress, regress_delta))
     return SDUMC_EINVAL;
   if (distill != SDUMC_DISTILL_RMSE) ssd_global = nullptr;
   DistillArgs a;
   a.crit = distill;
+  a.reg = regress;
+  a.reg_delta = regress_delta;
   a.B = B;
   a.denom = denom;
   a.vals = vals; a.labels = labels; a.th = th; a.ct = ct; a.z = z;
@@ -1091,6 +1211,14 @@ extern "C" int sdumc_distill_crit_(int32_t B, float denom, const float* vals, co
   hipLaunchKernelGGL(distill_apply_kernel, dim3(mx > 2 ? mx : 2, 4), dim3(256), 0, st, a);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
+}
+
+extern "C" int sdumc_distill_crit_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                   const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                   float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                   int32_t distill, void* stream) {
+  return sdumc_distill_crit_reg_(B, denom, vals, labels, th, ct, z, weights5, ssd_global, d_vals, d_th, d_ct, d_z, losses,
+                                 workspace, distill, SDUMC_REGRESS_MSE, 0.f, stream);
 }
 
 extern "C" int sdumc_distill_fwd_bwd(int32_t B, float denom, const float* vals, const float* labels, const float* th,
@@ -1127,13 +1255,14 @@ extern "C" int sdumc_ce_fwd_bwd(const float* a, const float* b, int32_t rows, in
 
 // MSE x2 + the distillation criterion x3 + RnC over cat(stream 0, stream 1) with the labels repeated (main :134-148): values and every gradient
 // w.r.t. the network outputs in two launches.  Returns 1 when the shape is not one it takes (n = 2B > 256: the sorted RnC form).
-extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
-                                   const float* z, const float* rnc_feats, int32_t rd, float temperature, const float* weights6,
-                                   float* d_vals, float* d_th, float* d_ct, float* d_z, float* d_rnc, float* losses,
-                                   float* distill_ws, float* rnc_workspace, float* hyper, double beta1, double beta2,
-                                   int32_t distill, void* stream) {
+// regress: the criterion of the two regression terms (SDUMC_REGRESS_*; the p == 3 workgroups of the second launch).
+extern "C" int sdumc_losses_fused_reg_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
+                                       const float* z, const float* rnc_feats, int32_t rd, float temperature,
+                                       const float* weights6, float* d_vals, float* d_th, float* d_ct, float* d_z, float* d_rnc,
+                                       float* losses, float* distill_ws, float* rnc_workspace, float* hyper, double beta1,
+                                       double beta2, int32_t distill, int32_t regress, float regress_delta, void* stream) {
   const int n = 2 * B;
-  if (distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;
+  if (distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL || !sdumc_regress_valid(regress, regress_delta)) return SDUMC_EINVAL;
   if (B <= 0 || n > 256 || rd <= 0 || temperature <= 0.f) return 1;
   const size_t lds1 = (((size_t)rd + 3) & ~(size_t)3) * sizeof(float) + 5 * (size_t)n * sizeof(float);
   const size_t lds2 = ((size_t)n + 256) * sizeof(float);
@@ -1145,6 +1274,8 @@ extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* la
   for (int i = 0; i < 5; ++i) a.w[i] = weights6[i];
   a.ssd_global = nullptr;
   a.crit = distill;
+  a.reg = regress;
+  a.reg_delta = regress_delta;
   a.d_vals = d_vals; a.d_th = d_th; a.d_ct = d_ct; a.d_z = d_z;
   a.losses = losses;
   a.part = distill_ws;
@@ -1167,6 +1298,15 @@ extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* la
   hipLaunchKernelGGL(loss_stage2_kernel, dim3(n + 4 * amx + 1), dim3(256), lds2, st, a, r, amx, hyper, beta1, beta2);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
+}
+
+extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
+                                   const float* z, const float* rnc_feats, int32_t rd, float temperature, const float* weights6,
+                                   float* d_vals, float* d_th, float* d_ct, float* d_z, float* d_rnc, float* losses,
+                                   float* distill_ws, float* rnc_workspace, float* hyper, double beta1, double beta2,
+                                   int32_t distill, void* stream) {
+  return sdumc_losses_fused_reg_(B, vals, labels, th, ct, z, rnc_feats, rd, temperature, weights6, d_vals, d_th, d_ct, d_z, d_rnc,
+                                 losses, distill_ws, rnc_workspace, hyper, beta1, beta2, distill, SDUMC_REGRESS_MSE, 0.f, stream);
 }
 
 #if SDUMC_LOSS_DBG
@@ -1209,18 +1349,7 @@ namespace {
 constexpr int SUPCON_MAX_N = 2048, SUPCON_MAX_D = 1024;
 constexpr double SUPCON_NORM_EPS = 1e-12;   // F.normalize's eps
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double block_sum_256_d(double v, double* red /*[4]*/) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
+// (wave_sum_d / block_sum_256_d: beside block_sum_256, at the head of the file)
 __device__ __forceinline__ double block_max_256_d(double v, double* red /*[4]*/) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));

@@ -511,8 +511,14 @@ class TrainStep(_OptStateMixin):
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
                  bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
                  skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None, ema_decay=None, ema_warmup=False,
-                 decoupled_decay=False):
-        """decoupled_decay (False = today's step, launch for launch; a bool): torch.optim.AdamW's decoupled weight decay in place of
+                 decoupled_decay=False, regress='mse', regress_delta=1.0):
+        """regress ('mse' = today's step, launch for launch and bit for bit): the criterion of the two regression terms (main :137-138;
+        losses[1:3], the seed of the backward): 'l1' (torch.nn.L1Loss), 'huber' (torch.nn.HuberLoss(delta=regress_delta)), both under
+        MSELoss's reduction (sum over rows / B), or 'ccc' (1 - the concordance correlation coefficient of the batch, moments in
+        double).  Computed by the workgroups of the loss stage that held the MSE terms: no further launch, so it combines with
+        everything behind the loss stage (guard, rates, freeze, EMA, AdamW, bf16 storage, capture()).  regress_delta: a positive finite
+        number, read by 'huber' alone (anything but 1.0 beside another criterion raises).
+        decoupled_decay (False = today's step, launch for launch; a bool): torch.optim.AdamW's decoupled weight decay in place of
         the coupled L2 -- the decoupled form of the step's last launch (sdumc_adamw_step has the rule): every updated parameter is
         first multiplied by fp32(1 - lr * lr_scale_i * weight_decay * decay_scale_i), one fp32 multiply of its own with the factor
         derived on the device from the lr the launch reads (set_lr is followed), then updated as with weight_decay = 0.  Combines
@@ -559,6 +565,8 @@ class TrainStep(_OptStateMixin):
         Ta, Tt, Tv, T4 = T
         distill_code = _lib.distill_code(distill)
         self.distill = distill
+        regress_code, regress_d = _lib.regress_args(regress, regress_delta)
+        self.regress, self.regress_delta = regress, regress_d
         self.decoupled_decay = bool(_lib.decoupled_arg(decoupled_decay))
         clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
         if (clip or skip) and not _lib.GUARD_ABI:
@@ -663,6 +671,8 @@ class TrainStep(_OptStateMixin):
         cfg.adam_m, cfg.adam_v = ptr(self.adam_m), ptr(self.adam_v)
         cfg.hyper, cfg.losses = ptr(self.hyper), ptr(self.losses)
         cfg.distill = distill_code
+        if regress_code:      # (a zeroed pair of fields = MSE: the struct of the default step is written as it always was)
+            cfg.regress, cfg.regress_delta = regress_code, regress_d
         if clip or skip:
             # the guard vector and the reduce's scratch: the run's (share.guard, one vector for every shape of a FusedTrainer) or its own
             if getattr(share, "guard", None) is not None:
@@ -964,8 +974,10 @@ class FusedTrainer:
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
                  inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
                  skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False,
-                 decoupled_decay=False, **step_kwargs):
+                 decoupled_decay=False, regress='mse', regress_delta=1.0, **step_kwargs):
         """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+        regress: 'mse' | 'l1' | 'huber' | 'ccc' with regress_delta, the regression criterion of every step (TrainStep); columns 1-2 of
+        train_epoch's record hold its values.
         decoupled_decay (a bool): torch.optim.AdamW's decoupled weight decay in every step of the run (TrainStep has the rule).
         ema_decay / ema_warmup: averaged weights (TrainStep has the rule): .ema_params is the run's ONE average, a flat tensor laid out
         like the parameters that every step updates whatever its shape (None when off); eval_epoch / saliency_epoch(weights='ema')
@@ -985,6 +997,7 @@ class FusedTrainer:
         through per-batch row maps (4 bytes per frame; sdumc_net_io.row_map)."""
         _lib.distill_code(distill)
         self.distill = distill
+        self.regress = (regress, _lib.regress_args(regress, regress_delta)[1])
         self.decoupled_decay = bool(_lib.decoupled_arg(decoupled_decay))
         clip, skip = _lib.guard_args(clip_norm, skip_nonfinite)
         ema_on = _lib.ema_args(ema_decay, ema_warmup)[0]
@@ -1000,6 +1013,8 @@ class FusedTrainer:
             self.kw.update(ema_decay=ema_decay, ema_warmup=ema_warmup)
         if self.decoupled_decay:
             self.kw.update(decoupled_decay=True)
+        if regress != 'mse':
+            self.kw.update(regress=regress, regress_delta=regress_delta)
         lay = ParamLayout.get(dims[0], dims[1], dims[2])
         self.rates = TensorRates(lay, lr_scale, decay_scale, freeze) if TensorRates.wanted(lr_scale, decay_scale, freeze) else None
         if self.rates is not None and not _lib.RATES_ABI:
@@ -1030,7 +1045,8 @@ class FusedTrainer:
             self.kw.update(planes=False, bits_next=False)
 
     def _get(self, B, T):
-        key = (B,) + tuple(T) + self.contrast + (self.distill,)      # the criteria are part of the key: one cache never mixes them
+        # the criteria are part of the key: one cache never mixes them
+        key = (B,) + tuple(T) + self.regress + self.contrast + (self.distill,)
         ts = self._steps.pop(key, None)
         if ts is None:
             while len(self._steps) >= self.max_cached:

@@ -1,14 +1,17 @@
 """Drop-in replacements of the six loss callables the driver builds (main_frame_val_text_missing.py:310-315,
 toolkit/utils/loss.py): MSELoss (:19-33), RMSELoss (:37-51), RnCLoss (:271-315), CosineSimilarityLoss4Seq (:100-119),
 KLLoss (:74-97), CELoss (:6-16), and of the file's second contrastive criterion, SupConLoss (:143-240).  Same constructor
-and call signatures, 0-dim results with grad; value and gradient come from the HIP kernels (sdumc_amd/csrc/loss.hip)."""
+and call signatures, 0-dim results with grad; value and gradient come from the HIP kernels (sdumc_amd/csrc/loss.hip).
+L1Loss, HuberLoss and CCCLoss are the regression criteria the fused step offers beside MSELoss (TrainStep(regress=)), with
+MSELoss's shape rules and reduction."""
 import torch
 import torch.nn as nn
 
 from . import ops
 from ._lib import SdumcError
 
-__all__ = ["MSELoss", "RMSELoss", "RnCLoss", "CosineSimilarityLoss4Seq", "KLLoss", "CELoss", "SupConLoss"]
+__all__ = ["MSELoss", "RMSELoss", "RnCLoss", "CosineSimilarityLoss4Seq", "KLLoss", "CELoss", "SupConLoss", "L1Loss", "HuberLoss",
+           "CCCLoss"]
 
 
 def _flat2(pred, target):
@@ -49,6 +52,57 @@ class MSELoss(nn.Module):
         if p.shape != t.shape:
             raise SdumcError(f"MSELoss: shapes {tuple(p.shape)} vs {tuple(t.shape)}")
         return _MSE.apply(p, t)
+
+
+class _Reg(torch.autograd.Function):
+    """L1 / Huber / CCC: value and the gradient to the prediction from one launch (sdumc_reg_fwd_bwd); none to the target."""
+
+    @staticmethod
+    def forward(ctx, pred, target, regress, delta):
+        p, t = pred.contiguous().float(), target.contiguous().float()
+        loss, dp = ops.reg_fwd_bwd(p.view(-1), t.view(-1), regress, delta, 1.0, denom=pred.shape[0], need_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(dp)
+        ctx.shape = pred.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dp,) = ctx.saved_tensors
+        return (None if dp is None else (dp * g).view(ctx.shape)), None, None, None
+
+
+class _RegLoss(nn.Module):
+    """MSELoss's shape rules (loss.py:26-31) and reduction (the sum over every element / len(pred)) with another element term."""
+    regress, delta = None, 1.0
+
+    def forward(self, pred, target):
+        _dev(pred, target)
+        p, t = _flat2(pred, target)
+        if p.shape != t.shape:
+            raise SdumcError(f"{type(self).__name__}: shapes {tuple(p.shape)} vs {tuple(t.shape)}")
+        return _Reg.apply(p, t.detach(), self.regress, self.delta)
+
+
+class L1Loss(_RegLoss):
+    """torch.nn.L1Loss under MSELoss's reduction: sum |pred - target| / len(pred)."""
+    regress = "l1"
+
+
+class HuberLoss(_RegLoss):
+    """torch.nn.HuberLoss(delta=delta) under MSELoss's reduction: the sum of 0.5 d^2 (|d| <= delta) or delta (|d| - 0.5 delta) over
+    every element / len(pred)."""
+    regress = "huber"
+
+    def __init__(self, delta=1.0):
+        super().__init__()
+        from ._lib import regress_args
+        self.delta = regress_args("huber", delta)[1]
+
+
+class CCCLoss(_RegLoss):
+    """1 - the concordance correlation coefficient of every element of pred and target (population moments, accumulated in double):
+    1 - 2 s_py / (s_pp + s_yy + (m_p - m_y)^2).  pred and target one shared constant: NaN, like the expression in torch."""
+    regress = "ccc"
 
 
 class _RMSE(torch.autograd.Function):

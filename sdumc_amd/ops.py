@@ -534,6 +534,18 @@ def mse_fwd_bwd(pred, target, weight=1.0, denom=None):
     return loss, dpred
 
 
+def reg_fwd_bwd(pred, target, regress, delta=1.0, weight=1.0, denom=None, need_grad=True):
+    """sdumc_reg_fwd_bwd: the regression criterion `regress` ('mse' | 'l1' | 'huber' | 'ccc', _lib.REGRESS) of two flat fp32 tensors ->
+    (value [1], weight * dLoss/dpred or None)."""
+    code, delta = _lib.regress_args(regress, delta)
+    rows = pred.numel()
+    loss = torch.empty(1, device=pred.device)
+    dpred = torch.empty_like(pred) if need_grad else None
+    check(lib.sdumc_reg_fwd_bwd(ptr(pred), ptr(target), rows, float(denom or rows), weight, code, delta, ptr(loss), ptr(dpred),
+                                _st()), "sdumc_reg_fwd_bwd")
+    return loss, dpred
+
+
 def ssd(a, b):
     n = a.numel()
     out = torch.empty(1, device=a.device)

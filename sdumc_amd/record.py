@@ -27,6 +27,8 @@ from .epoch import StoreOrdered
 LOG_COLS = _lib.LOG_COLS
 # columns 0..7 of a log row: the step's loss vector (sdumc_step_cfg.losses).  Entries 3..5 hold the chosen distillation criterion's
 # values for the text_hidden, cross_text and fused pairs, entry 6 the chosen contrastive criterion's, entry 7 is not used by the step.
+# Entries 1..2 ("mse_full", "mse_missing": the names stay) hold the chosen regression criterion's values (regress='mse' | 'l1' | 'huber'
+# | 'ccc'); train_val_mse_* are computed from the predictions and are the MSE whatever the criterion.
 LOSS_NAMES = ("total", "mse_full", "mse_missing", "distill_text", "distill_query", "distill_fused", "contrast", "unused")
 COL_GRAD_NORM, COL_NONFINITE, COL_B, COL_LR = 8, 9, 10, 11
 

@@ -34,10 +34,13 @@ class HipBackend:
     """Per-rank compute on one MI355X through the C ABI."""
 
     def __init__(self, flat_params, B, T, dims, weights, lr, betas, eps, weight_decay, seed, sample0, B_global,
-                 bf16=False, share=None, planes=False, distill='rmse'):
+                 bf16=False, share=None, planes=False, distill='rmse', regress='mse', regress_delta=1.0):
         """distill: 'rmse' | 'cosine' | 'kl', the criterion of the three distillation pairs (engine.TrainStep).  Cosine and KL
         are sums over rows / B_global: the rank's loss entries 3..5 are then LOCAL shares like the MSE entries, and the
         sums of squares of the exchange record are carried but not read.
+        regress: 'mse' | 'l1' | 'huber' (with regress_delta), the criterion of the two regression terms (engine.TrainStep).  L1 and
+        Huber entries are local sums / B_global and add over ranks exactly like the MSE entries: no exchange changes.  'ccc' is a
+        quantity of the whole batch's moments, which no exchange carries: refused.
         share: the run state (engine._RunState: rng, Adam moments, hyper, losses, gradient bucket) of the training run
         this backend belongs to.  planes=True: the batches installed by set_batch are RESIDENT (each runs many steps): their bf16
         planes are split once per set_batch (engine.planes_wanted); default off -- a fresh batch per step would pay the split for one use.
@@ -47,6 +50,9 @@ class HipBackend:
         from . import _lib, engine
         self._lib, self._engine = _lib, engine
         lib = _lib.lib
+        regress_code, regress_d = _lib.regress_args(regress, regress_delta)
+        if regress == 'ccc':
+            raise _lib.SdumcError("HipBackend: regress='ccc' is not built under data parallelism (single-GPU steps only)")
         dev = flat_params.device
         Ta, Tt, Tv, T4 = T
         self.B, self.B_global = B, B_global
@@ -90,6 +96,8 @@ class HipBackend:
         cfg.hyper, cfg.losses = _lib.ptr(self.hyper), _lib.ptr(self.losses)
         cfg.B_global = B_global
         cfg.distill = _lib.distill_code(distill)
+        if regress_code:
+            cfg.regress, cfg.regress_delta = regress_code, regress_d
         self.cfg = cfg
         g = _lib.NetGrads()
         g.d_vals, g.d_fused, g.d_rnc = _lib.ptr(self.d_vals), _lib.ptr(self.d_fused), _lib.ptr(self.d_rnc)
@@ -214,10 +222,14 @@ class DataParallelStep:
     def __init__(self, flat_params, B, T, dims, weights=(0.5, 0.5, 0.1, 0.7, 0.1, 0.8), lr=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=1e-5, seed=0, exact=True, backend_factory=None, bf16=False,
                  force_collectives=False, planes=False, distill='rmse', contrast='rnc', clip_norm=None, skip_nonfinite=False,
-                 freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False):
+                 freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False, regress='mse', regress_delta=1.0):
         import collections
         import inspect
-        from ._lib import SdumcError, contrast_code
+        from ._lib import SdumcError, contrast_code, regress_args
+        regress_args(regress, regress_delta)
+        if regress == 'ccc':      # the moments of the whole batch would need an exchange of their own: no local-only CCC
+            raise SdumcError("DataParallelStep: regress='ccc' is not built under data parallelism (single-GPU steps only)")
+        self.regress = regress
         if ema_decay is not None or ema_warmup:      # the fused single-GPU step's (TrainStep: the EMA form of its last launch)
             raise SdumcError("DataParallelStep: ema_decay / ema_warmup are not built under data parallelism (single-GPU steps only)")
         if freeze is not None or lr_scale is not None or decay_scale is not None:      # the fused single-GPU step's (engine.TensorRates)
@@ -244,6 +256,8 @@ class DataParallelStep:
         self.distill = distill
         if distill != 'rmse':
             extra["distill"] = distill  # (a backend without the argument refuses it: no silent RMSE)
+        if regress != 'mse':
+            extra.update(regress=regress, regress_delta=regress_delta)      # (likewise: no silent MSE)
         # One backend per batch shape (B, T_audio, T_text, T_video, T_feat4), least recently used first out, all continuing
         # ONE run state: the reference pads every batch to its own maximum and ends an epoch on a short batch.
         self._shares = "share" in inspect.signature(factory).parameters
