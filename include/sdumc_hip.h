@@ -657,6 +657,34 @@ int sdumc_distill_fwd_bwd(int32_t B, float denom, const float* vals, const float
                           const float* ct, const float* z, const float* weights5, const float* ssd_global,
                           float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
                           void* stream);
+/* Distillation targets from a STORED teacher instead of stream 0 (main :148 compares the text-missing stream with the full stream of
+ * the same step; a trained full-modality checkpoint, or the averaged weights once per epoch, are the other two teachers).  Up to three
+ * device fp32 tables in store order; for a pair whose table is given
+ *   - the target of sample b is table row idx[b] (idx NULL: row b, the tables are then [B, ...] in batch order); cosine / KL row
+ *     (b, q) of cross_text reads teacher row idx[b] * 7 + q;
+ *   - the student is stream 1, the first argument, as before;
+ *   - the target is a constant: rows [0, B) of that pair's gradient buffer are written +0.0 -- for `fused` too, whose stream 0
+ *     self-distillation does NOT detach;
+ *   - the value goes to losses[3 + p] as before.
+ * A pair whose table is NULL is computed as without a teacher.  Arithmetic, chunking, partials and their order are the self-
+ * distillation's: tables that hold bit copies of stream 0's rows give the same bits.  An index outside [0, n_rows) is never turned
+ * into an address: the kernels take a NaN target row for it (NaN value; NaN gradient rows of that sample, of the whole pair for RMSE).
+ * SDUMC_EINVAL before anything is enqueued: n_rows < 1 with a table given, idx NULL with n_rows != B, a table or idx that is not
+ * 4-byte (idx: 8-byte) aligned, a teacher beside ssd_global or a B_global different from B (the data-parallel exchange carries no
+ * teacher), B * 896 beyond int32. */
+typedef struct sdumc_teacher {
+  const float* text_hidden;   /* [n_rows, 256]    or NULL: that pair as the step always had it */
+  const float* cross_text;    /* [n_rows, 7, 128] or NULL */
+  const float* fused;         /* [n_rows, 128]    or NULL */
+  const int64_t* idx;         /* device [B] rows of the tables, or NULL: row b */
+  int64_t n_rows;
+} sdumc_teacher;
+/* sdumc_distill_fwd_bwd with the criterion of the three pairs (SDUMC_DISTILL_*) and a teacher.  teacher NULL, or all three of its
+ * tables NULL: the same launches as without one. */
+int sdumc_distill_teacher_fwd_bwd(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                  const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                  float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                  int32_t distill, const sdumc_teacher* teacher, void* stream);
 /* Row-wise criteria for the drop-in loss modules: value and gradient in ONE launch, one wavefront per row, fixed
  * summation order (rows in index order per wavefront, wavefronts in index order: bitwise reproducible).
  * a, b: [rows, groups, width] contiguous (groups = 1 for 2-D inputs), width <= 1024; denom = size(0) of the GLOBAL
@@ -1607,10 +1635,18 @@ int sdumc_dp_unpack(const float* records, int32_t W, int32_t B, int32_t rd, floa
  * which here are OUTPUTS and must all be non-NULL) */
 int sdumc_loss_backward(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
                         const sdumc_net_grads* g, void* scratch, size_t scratch_bytes, void* stream);
+/* ... with the distillation targets of a stored teacher (sdumc_teacher; NULL, or no table: sdumc_loss_backward launch for launch) */
+int sdumc_loss_backward_teacher(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
+                                const sdumc_net_grads* g, const sdumc_teacher* teacher, void* scratch, size_t scratch_bytes,
+                                void* stream);
 
 /* forward (both streams) + losses + backward + Adam on one GPU.  workspace >= sdumc_step_workspace_bytes. */
 size_t sdumc_step_workspace_bytes(const sdumc_net_dims* d);
 int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg, void* stream);
+/* The same step with the distillation targets of a stored teacher: no further launch, the loss stage's kernels read the tables
+ * through teacher->idx.  sdumc_step_cfg is full, so the teacher travels beside it.  teacher NULL, or no table: sdumc_train_step. */
+int sdumc_train_step_teacher(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
+                             const sdumc_teacher* teacher, void* stream);
 /* byte offset of the flat gradient bucket inside the sdumc_train_step workspace (tests, DP all-reduce) */
 size_t sdumc_step_grads_offset(const sdumc_net_dims* d);
 

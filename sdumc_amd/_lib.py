@@ -304,6 +304,22 @@ def regress_args(regress, regress_delta=1.0):
     return REGRESS[regress], float(d)
 
 
+class Teacher(C.Structure):         # sdumc_teacher: a stored teacher's tables beside a step (teacher.TeacherTargets fills it)
+    _fields_ = [("text_hidden", C.c_void_p), ("cross_text", C.c_void_p), ("fused", C.c_void_p), ("idx", C.c_void_p),
+                ("n_rows", C.c_int64)]
+
+
+def _teacher_abi():
+    """False only for an A/B against an older build (SDUMC_LIB, tools/teacher_bench.py) from before sdumc_train_step_teacher: a
+    teacher then raises on the host (that library has no entry that takes one)."""
+    if not os.environ.get("SDUMC_LIB") or not os.path.exists(LIB_PATH):
+        return True
+    return hasattr(C.CDLL(LIB_PATH), "sdumc_train_step_teacher")
+
+
+TEACHER_ABI = _teacher_abi()
+
+
 # sdumc_step_cfg.distill: the criterion of the three distillation pairs (SDUMC_DISTILL_* of include/sdumc_hip.h)
 DISTILL = {"rmse": 0, "cosine": 1, "kl": 2}
 
@@ -559,6 +575,7 @@ _SIGS = {
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdumc_distill_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "sdumc_distill_fwd_bwd": (C.c_int, [C.c_int32, C.c_float] + [C.c_void_p] * 14),
+    "sdumc_distill_teacher_fwd_bwd": (C.c_int, [C.c_int32, C.c_float] + [C.c_void_p] * 13 + [C.c_int32, C.POINTER(Teacher), C.c_void_p]),
     "sdumc_rnc_dfeat_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "sdumc_rnc_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -638,10 +655,13 @@ _SIGS = {
     "sdumc_net_feature_grad_scratch_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_step_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_train_step": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(StepCfg), C.c_void_p]),
+    "sdumc_train_step_teacher": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(StepCfg), C.POINTER(Teacher), C.c_void_p]),
     "sdumc_loss_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims), C.c_int32]),
     "sdumc_loss_ssd": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sdumc_loss_backward": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(StepCfg), C.POINTER(NetGrads),
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sdumc_loss_backward_teacher": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.POINTER(StepCfg), C.POINTER(NetGrads),
+                                              C.POINTER(Teacher), C.c_void_p, C.c_size_t, C.c_void_p]),
     "sdumc_dp_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "sdumc_dp_record_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "sdumc_dp_record": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

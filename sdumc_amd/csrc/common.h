@@ -214,6 +214,19 @@ inline bool sdumc_regress_valid(int32_t regress, float delta) {
   return regress != SDUMC_REGRESS_HUBER || (delta > 0.f && delta < __builtin_inff());
 }
 
+// a stored teacher (sdumc_teacher) beside a step of B samples per stream: 0 = none (NULL, or no table), 1 = one to use, SDUMC_EINVAL
+// = what every entry that takes one refuses before anything is enqueued.  exchange: the call also carries global sums or a
+// B_global different from B (the data-parallel exchange carries no teacher).
+inline int sdumc_teacher_check(const sdumc_teacher* t, int64_t B, bool exchange) {
+  if (!t || (!t->text_hidden && !t->cross_text && !t->fused)) return 0;
+  if (exchange || B < 1 || B * (SDUMC_NQ * SDUMC_H) > INT32_MAX) return SDUMC_EINVAL;
+  if (t->n_rows < 1 || (!t->idx && t->n_rows != B)) return SDUMC_EINVAL;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(t->text_hidden) | reinterpret_cast<uintptr_t>(t->cross_text) |
+                         reinterpret_cast<uintptr_t>(t->fused);
+  if ((bits & 3) || (reinterpret_cast<uintptr_t>(t->idx) & 7)) return SDUMC_EINVAL;
+  return 1;
+}
+
 extern "C" {
 // loss.hip: the six loss launches of a single-GPU step in two (1 = shape not taken)
 // hyper != nullptr: the second pass also makes the Adam bias-correction update of this step (as total_loss_kernel did)
@@ -236,6 +249,16 @@ int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals, const flo
                             const float* z, const float* weights5, const float* ssd_global, float* d_vals, float* d_th,
                             float* d_ct, float* d_z, float* losses, float* workspace, int32_t distill, int32_t regress,
                             float regress_delta, void* stream);
+// ... and both with a stored teacher's tables as the targets of the three pairs (nullptr, or no table: the entries above)
+int sdumc_losses_fused_teacher_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct, const float* z,
+                                const float* rnc_feats, int32_t rd, float temperature, const float* weights6, float* d_vals,
+                                float* d_th, float* d_ct, float* d_z, float* d_rnc, float* losses, float* distill_ws,
+                                float* rnc_workspace, float* hyper, double beta1, double beta2, int32_t distill, int32_t regress,
+                                float regress_delta, const sdumc_teacher* teacher, void* stream);
+int sdumc_distill_crit_teacher_(int32_t B, float denom, const float* vals, const float* labels, const float* th, const float* ct,
+                                const float* z, const float* weights5, const float* ssd_global, float* d_vals, float* d_th,
+                                float* d_ct, float* d_z, float* losses, float* workspace, int32_t distill, int32_t regress,
+                                float regress_delta, const sdumc_teacher* teacher, void* stream);
 // which: 0 = stage A forward, 1 = stage B forward, 2 = stage B backward, 3 = stage A backward
 int sdumc_chain_launch_(const sdumc_chain_args* a, int which, void* stream);
 // the same four stages with every layer's output columns split over clusters of 4 workgroups (chain_cluster.hip);

@@ -2979,7 +2979,12 @@ extern "C" int sdumc_loss_ssd(const sdumc_net_dims* d, const sdumc_net_io* io, f
 
 namespace {
 int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg, const sdumc_net_grads* g,
-                       void* scratch, size_t scratch_bytes, void* stream, float* hyper, bool* total_pending = nullptr);
+                       void* scratch, size_t scratch_bytes, void* stream, float* hyper, bool* total_pending = nullptr,
+                       const sdumc_teacher* teacher = nullptr);
+// a stored teacher beside this step's options (sdumc_teacher_check): 0 none, 1 one to use, SDUMC_EINVAL refused
+int teacher_ok(const sdumc_teacher* t, const sdumc_net_dims* d, const sdumc_step_cfg* cfg) {
+  return sdumc_teacher_check(t, d->B, cfg->ssd_global != nullptr || (cfg->B_global > 0 && cfg->B_global != d->B));
+}
 // the contrastive criterion of a step: known, and SupCon neither under the data-parallel exchange (it carries RnC records only)
 // nor with a temperature or label mode its kernel would refuse after the distillation launches
 bool contrast_ok(const sdumc_step_cfg* cfg) {
@@ -2999,13 +3004,22 @@ extern "C" int sdumc_loss_backward(const sdumc_net_dims* d, const sdumc_net_io* 
                                    const sdumc_net_grads* g, void* scratch, size_t scratch_bytes, void* stream) {
   return loss_backward_impl(d, io, cfg, g, scratch, scratch_bytes, stream, nullptr);
 }
+extern "C" int sdumc_loss_backward_teacher(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
+                                           const sdumc_net_grads* g, const sdumc_teacher* teacher, void* scratch,
+                                           size_t scratch_bytes, void* stream) {
+  return loss_backward_impl(d, io, cfg, g, scratch, scratch_bytes, stream, nullptr, nullptr, teacher);
+}
 namespace {
 // total_pending (the fused step): when the merged loss passes ran, the Adam bias correction has been made by their second pass
 // and losses[0] is left to the Adam launch (sdumc_total_loss) -- no one-thread total_loss launch on the critical path
 int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg, const sdumc_net_grads* g,
-                       void* scratch, size_t scratch_bytes, void* stream, float* hyper, bool* total_pending) {
+                       void* scratch, size_t scratch_bytes, void* stream, float* hyper, bool* total_pending,
+                       const sdumc_teacher* teacher) {
   if (total_pending) *total_pending = false;
   if (!d || !io || !cfg || !g || !scratch || d->streams != 2) return SDUMC_EINVAL;
+  const int have_teacher = teacher_ok(teacher, d, cfg);
+  if (have_teacher < 0) return SDUMC_EINVAL;
+  if (!have_teacher) teacher = nullptr;
   if (!io->vals || !io->fused || !io->rnc || !io->text_hidden || !io->cross_text) return SDUMC_EINVAL;
   if (!g->d_vals || !g->d_fused || !g->d_rnc || !g->d_text_hidden || !g->d_cross_text) return SDUMC_EINVAL;
   if (!cfg->labels || !cfg->losses) return SDUMC_EINVAL;
@@ -3030,10 +3044,10 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   // single GPU (no global sums / features handed in): the distillation terms and RnC share their two passes (loss.hip)
   bool done = false;
   if (!supcon && !cfg->rnc_feats_global && !cfg->ssd_global && Bg == B) {
-    const int rc = sdumc_losses_fused_reg_(B, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, io->rnc, RD,
-                                           cfg->temperature, w, dv, dth, dct, df, dr, L, ls.ssd_ws, ls.rnc_ws,
-                                           total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2, cfg->distill,
-                                           cfg->regress, cfg->regress_delta, stream);
+    const int rc = sdumc_losses_fused_teacher_(B, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, io->rnc, RD,
+                                               cfg->temperature, w, dv, dth, dct, df, dr, L, ls.ssd_ws, ls.rnc_ws,
+                                               total_pending ? hyper : nullptr, (double)cfg->beta1, (double)cfg->beta2,
+                                               cfg->distill, cfg->regress, cfg->regress_delta, teacher, stream);
     if (rc < 0) return rc;
     done = rc == 0;
     if (done && total_pending && hyper) {
@@ -3044,8 +3058,9 @@ int loss_backward_impl(const sdumc_net_dims* d, const sdumc_net_io* io, const sd
   if (!done) {
   // MSELoss x2 (main :137-138) + the distillation criterion x3 (main :148; teacher side detached for text_feat /
   // text_query_feat, not for features): value and gradients in two launches
-  RET(sdumc_distill_crit_reg_(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
-                              cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, cfg->distill, cfg->regress, cfg->regress_delta, stream));
+  RET(sdumc_distill_crit_teacher_(B, (float)Bg, io->vals, cfg->labels, io->text_hidden, io->cross_text, io->fused, w,
+                                  cfg->ssd_global, dv, dth, dct, df, L, ls.ssd_ws, cfg->distill, cfg->regress, cfg->regress_delta,
+                                  teacher, stream));
   // RnCLoss over cat(r_stream0, r_stream1) with labels repeated (main :134,:140; loss.py:282-283)
   if (supcon) {
     // SupConLoss instead (loss.py:143-240): the two streams are the two views of a sample, rows normalised in the kernel
@@ -3111,8 +3126,14 @@ extern "C" size_t sdumc_step_workspace_bytes(const sdumc_net_dims* d) {
 
 extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
                                 void* stream) {
+  return sdumc_train_step_teacher(d, io, cfg, nullptr, stream);
+}
+
+extern "C" int sdumc_train_step_teacher(const sdumc_net_dims* d, const sdumc_net_io* io, const sdumc_step_cfg* cfg,
+                                        const sdumc_teacher* teacher, void* stream) {
   RET(check_io(d, io));
   if (!cfg || d->streams != 2 || !cfg->adam_m || !cfg->adam_v || !cfg->hyper) return SDUMC_EINVAL;
+  if (teacher_ok(teacher, d, cfg) < 0) return SDUMC_EINVAL;      // before anything is launched, like every option below
   if (cfg->distill < SDUMC_DISTILL_RMSE || cfg->distill > SDUMC_DISTILL_KL) return SDUMC_EINVAL;   // before anything is launched
   if (!contrast_ok(cfg) || (cfg->contrast == SDUMC_CONTRAST_SUPCON && 2 * d->B > 2048)) return SDUMC_EINVAL;
   if (!regress_ok(cfg, d->B)) return SDUMC_EINVAL;
@@ -3186,7 +3207,7 @@ extern "C" int sdumc_train_step(const sdumc_net_dims* d, const sdumc_net_io* io,
   RET(forward(c, fs));
   // the Adam bias-correction update rides in the loss's last launch, the dropout call counter in the Adam launch
   bool total_pending = false;
-  RET(loss_backward_impl(d, &nio, cfg, &g, base + sl.loss, sl.net - sl.loss, stream, cfg->hyper, &total_pending));
+  RET(loss_backward_impl(d, &nio, cfg, &g, base + sl.loss, sl.net - sl.loss, stream, cfg->hyper, &total_pending, teacher));
   mark(static_cast<hipStream_t>(stream), 5);
   RET(backward(c, g, sch));
   mark(static_cast<hipStream_t>(stream), 9);

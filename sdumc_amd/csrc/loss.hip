@@ -809,10 +809,41 @@ struct DistillArgs {
   int crit;         // SDUMC_DISTILL_*: uniform per launch
   int reg;          // SDUMC_REGRESS_*: the criterion of the two regression terms, uniform per launch
   float reg_delta;  // Huber's delta (read by SDUMC_REGRESS_HUBER alone)
+  // a stored teacher (sdumc_teacher): tt[p] != nullptr -> the target of pair p's sample b is row tidx[b] (tidx nullptr: row b) of
+  // that table instead of row b of stream 0, and stream 0 gets no gradient from the pair
+  const float* tt[3];     // text_hidden [tn_rows, 256] | cross_text [tn_rows, 7, 128] | fused [tn_rows, 128]
+  const int64_t* tidx;    // [B] or nullptr
+  int64_t tn_rows;
 };
 constexpr int DCH = 4096;   // elements per block
 static_assert(DCH % SDUMC_D == 0 && DCH % SDUMC_H == 0 && SDUMC_D <= ROW_MAXW && SDUMC_H <= ROW_MAXW,
               "a block's chunk is a whole number of rows of every distillation pair");
+// The teacher's rows of one block's chunk.  A chunk of DCH elements touches at most 32 samples of a pair (`fused`: 32 rows of 128;
+// text_hidden 16; cross_text, whose 896-element samples straddle chunk edges, at most 6): their indices are read ONCE, in front of the loops, one per thread, into LDS as element offsets into the
+// table -- the loops then wait for no global read of an index.  An index outside [0, tn_rows) is never turned into an address: its
+// slot holds -1, teacher_row gives nullptr and the caller takes NaN for the row.
+constexpr int T_SLOTS = 40;
+struct TeacherChunk {
+  int b0;               // first sample of the chunk
+  long long* off;       // LDS [T_SLOTS]
+};
+__device__ __forceinline__ TeacherChunk teacher_chunk(const DistillArgs& a, const int p, const int bx, const int64_t n, long long* off) {
+  const int per = p == 0 ? SDUMC_D : (p == 1 ? SDUMC_NQ * SDUMC_H : SDUMC_H);
+  const int64_t e0 = (int64_t)bx * DCH, e1 = min(n, e0 + DCH);      // (e0 < e1 <= B * per: every sample below is one of the batch)
+  const int b0 = (int)(e0 / per), nb = (int)((e1 - 1) / per) - b0 + 1;
+  if ((int)threadIdx.x < nb && (int)threadIdx.x < T_SLOTS) {
+    const int b = b0 + threadIdx.x;
+    const int64_t r = a.tidx ? a.tidx[b] : (int64_t)b;
+    off[threadIdx.x] = (r >= 0 && r < a.tn_rows) ? r * per : -1;
+  }
+  __syncthreads();
+  return TeacherChunk{b0, off};
+}
+// (b is the same in every lane of a wavefront wherever this is called: a pair's samples are whole multiples of 64 elements)
+__device__ __forceinline__ const float* teacher_row(const DistillArgs& a, const int p, const TeacherChunk& c, const int b) {
+  const long long o = c.off[b - c.b0];
+  return o >= 0 ? a.tt[p] + o : nullptr;
+}
 __device__ __forceinline__ void distill_pair(const DistillArgs& a, int p, const float*& s1, const float*& s0, float*& g,
                                              int64_t& n) {
   const int64_t per = p == 0 ? SDUMC_D : (p == 1 ? SDUMC_NQ * SDUMC_H : SDUMC_H);
@@ -825,7 +856,7 @@ __device__ __forceinline__ void distill_pair(const DistillArgs& a, int p, const 
 // cosine / KL: the rows of a pair are its last axis (text_hidden [B,256], cross_text [B*7,128], fused [B,128]); a block's chunk
 // of DCH elements is 16 or 32 whole rows.  Pass 1: wavefront w adds the values of rows w, w + 4, ... of the chunk, the four sums
 // are added in order -> one partial per block, in the slots the sums of squares take.
-__device__ __forceinline__ void distill_rows_partials(const DistillArgs& a, const int bx, const int p, float* red) {
+__device__ __forceinline__ void distill_rows_partials(const DistillArgs& a, const int bx, const int p, float* red, long long* toff) {
   const float *s1, *s0;
   float* g;
   int64_t n;
@@ -835,15 +866,26 @@ __device__ __forceinline__ void distill_rows_partials(const DistillArgs& a, cons
   const int r1 = min(rows, (bx + 1) * rpb);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   float acc = 0.f;
-  for (int r = bx * rpb + wave; r < r1; r += 4)
-    acc += crit_row<false>(a.crit, s1 + (size_t)r * W, s0 + (size_t)r * W, W, lane, 0.f, nullptr, nullptr);
+  if (a.tt[p]) {      // the same rows against the teacher's: row r of the pair is row r % rps of sample r / rps
+    const int rps = p == 1 ? SDUMC_NQ : 1;
+    const TeacherChunk tc = teacher_chunk(a, p, bx, n, toff);
+    for (int r = bx * rpb + wave; r < r1; r += 4) {
+      const int b = __builtin_amdgcn_readfirstlane(r / rps);
+      const float* t = teacher_row(a, p, tc, b);
+      // (no row to read: the value a NaN target row gives, without running the row body on an address that does not exist)
+      acc += t ? crit_row<false>(a.crit, s1 + (size_t)r * W, t + (r - b * rps) * W, W, lane, 0.f, nullptr, nullptr) : NAN;
+    }
+  } else {
+    for (int r = bx * rpb + wave; r < r1; r += 4)
+      acc += crit_row<false>(a.crit, s1 + (size_t)r * W, s0 + (size_t)r * W, W, lane, 0.f, nullptr, nullptr);
+  }
   if (lane == 0) red[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) a.part[p * a.nblk[1] + bx] = red[0] + red[1] + red[2] + red[3];
 }
 // Pass 2: block 0 of a pair adds the partials in index order (the value); every block writes the gradients of its rows, which
 // need nothing from other rows.  Stream 1 is the first argument (main :148: loss(x_1, x_0.detach())).
-__device__ __forceinline__ void distill_rows_apply(const DistillArgs& a, const int bx, const int p, float* red) {
+__device__ __forceinline__ void distill_rows_apply(const DistillArgs& a, const int bx, const int p, float* red, long long* toff) {
   const float *s1, *s0;
   float* g;
   int64_t n;
@@ -860,6 +902,22 @@ __device__ __forceinline__ void distill_rows_apply(const DistillArgs& a, const i
   const int r1 = min(rows, (bx + 1) * rpb);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const float scale = a.w[2 + p] * half / a.denom;
+  if (a.tt[p]) {      // a stored teacher is a constant: stream 0's rows of this pair's gradient are +0.0, for `fused` too
+    const int rps = p == 1 ? SDUMC_NQ : 1;
+    const TeacherChunk tc = teacher_chunk(a, p, bx, n, toff);
+    for (int r = bx * rpb + wave; r < r1; r += 4) {
+      const size_t o = (size_t)r * W;
+      const int b = __builtin_amdgcn_readfirstlane(r / rps);
+      const float* t = teacher_row(a, p, tc, b);
+      if (t)
+        crit_row<true>(a.crit, s1 + o, t + (r - b * rps) * W, W, lane, scale, g + n + o, nullptr);
+      for (int c = lane; c < W; c += 64) {
+        if (!t) g[n + o + c] = NAN;      // the student's gradient against a NaN target row
+        g[o + c] = 0.f;
+      }
+    }
+    return;
+  }
   for (int r = bx * rpb + wave; r < r1; r += 4) {
     const size_t o = (size_t)r * W;
     crit_row<true>(a.crit, s1 + o, s0 + o, W, lane, scale, g + n + o, p == 2 ? g + o : nullptr);
@@ -867,11 +925,21 @@ __device__ __forceinline__ void distill_rows_apply(const DistillArgs& a, const i
       for (int c = lane; c < W; c += 64) g[o + c] = 0.f;
   }
 }
+// RMSE against a stored teacher: element i of the pair is column i % per of sample i / per; the 256 threads walk the chunk as they
+// do without one (coalesced inside a row), the target comes from the teacher's row of that sample.
+__device__ __forceinline__ float teacher_elem(const DistillArgs& a, const int p, const int per, const TeacherChunk& tc, const int64_t i) {
+  // (shifts and one division by a constant, in 32 bits: the host refuses a teacher where B * 896 leaves int32)
+  const unsigned u = (unsigned)i;
+  const int b = __builtin_amdgcn_readfirstlane((int)(p == 0 ? u / (unsigned)SDUMC_D : (p == 1 ? u / (unsigned)(SDUMC_NQ * SDUMC_H) : u / (unsigned)SDUMC_H)));
+  const float* t = teacher_row(a, p, tc, b);
+  return t ? t[i - (int64_t)b * per] : NAN;
+}
 __device__ __forceinline__ void distill_partials_body(const DistillArgs a, const int bx, const int p) {
   __shared__ float red[4];
+  __shared__ long long toff[T_SLOTS];      // (a stored teacher's row offsets of this block's chunk: teacher_chunk)
   if (bx >= a.nblk[p]) return;
   if (a.crit != SDUMC_DISTILL_RMSE) {
-    distill_rows_partials(a, bx, p, red);
+    distill_rows_partials(a, bx, p, red, toff);
     return;
   }
   const float *s1, *s0;
@@ -880,9 +948,18 @@ __device__ __forceinline__ void distill_partials_body(const DistillArgs a, const
   distill_pair(a, p, s1, s0, g, n);
   const int64_t i0 = (int64_t)bx * DCH, i1 = min(n, i0 + DCH);
   float acc = 0.f;
-  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
-    const float d = s1[i] - s0[i];
-    acc += d * d;
+  if (a.tt[p]) {
+    const int per = p == 0 ? SDUMC_D : (p == 1 ? SDUMC_NQ * SDUMC_H : SDUMC_H);
+    const TeacherChunk tc = teacher_chunk(a, p, bx, n, toff);
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+      const float d = s1[i] - teacher_elem(a, p, per, tc, i);
+      acc += d * d;
+    }
+  } else {
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+      const float d = s1[i] - s0[i];
+      acc += d * d;
+    }
   }
   const float s = block_sum_256(acc, red);
   if (threadIdx.x == 0) a.part[p * a.nblk[1] + bx] = s;
@@ -890,6 +967,7 @@ __device__ __forceinline__ void distill_partials_body(const DistillArgs a, const
 __global__ __launch_bounds__(256) void distill_partials_kernel(const DistillArgs a) { distill_partials_body(a, blockIdx.x, blockIdx.y); }
 __device__ __forceinline__ void distill_apply_body(const DistillArgs a, const int bx, const int p) {
   __shared__ float red[4];
+  __shared__ long long toff[T_SLOTS];
   if (p == 3) {   // MSELoss on both streams (loss.py:19-33): value + gradient
     if (bx > 1) return;
     const int sidx = bx;
@@ -911,7 +989,7 @@ __device__ __forceinline__ void distill_apply_body(const DistillArgs a, const in
   }
   if (bx >= a.nblk[p]) return;
   if (a.crit != SDUMC_DISTILL_RMSE) {
-    distill_rows_apply(a, bx, p, red);
+    distill_rows_apply(a, bx, p, red, toff);
     return;
   }
   const float *s1, *s0;
@@ -932,6 +1010,14 @@ __device__ __forceinline__ void distill_apply_body(const DistillArgs a, const in
   if (bx == 0 && threadIdx.x == 0) a.losses[3 + p] = rmse;
   const float k = a.w[2 + p] * inv_numel / rmse;   // 0/0 -> NaN exactly like torch's sqrt backward
   const int64_t i0 = (int64_t)bx * DCH, i1 = min(n, i0 + DCH);
+  if (a.tt[p]) {
+    const TeacherChunk tc = teacher_chunk(a, p, bx, n, toff);
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+      g[n + i] = k * (s1[i] - teacher_elem(a, p, (int)per, tc, i));      // stream 1 (student)
+      g[i] = 0.f;                                                   // stream 0: no part in the pair
+    }
+    return;
+  }
   for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
     const float gr = k * (s1[i] - s0[i]);
     g[n + i] = gr;                        // stream 1 (student)
@@ -1176,10 +1262,23 @@ extern "C" size_t sdumc_distill_workspace_bytes(int32_t B) {
 // MSE x2 + the chosen criterion x3 of main :137-148 (value + gradients w.r.t. the network outputs) in two launches.
 // distill != RMSE: ssd_global is not read (the value is a sum over local rows / denom) and pass 1 always runs.
 // regress: the criterion of the two regression terms (SDUMC_REGRESS_*; the p == 3 workgroups of the second launch).
-extern "C" int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
-                                       const float* ct, const float* z, const float* weights5, const float* ssd_global,
-                                       float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
-                                       int32_t distill, int32_t regress, float regress_delta, void* stream) {
+namespace {
+// the teacher's part of the kernels' argument (checked by the caller: sdumc_teacher_check)
+void distill_teacher(DistillArgs& a, const sdumc_teacher* t) {
+  a.tt[0] = t ? t->text_hidden : nullptr;
+  a.tt[1] = t ? t->cross_text : nullptr;
+  a.tt[2] = t ? t->fused : nullptr;
+  a.tidx = t ? t->idx : nullptr;
+  a.tn_rows = t ? t->n_rows : 0;
+}
+}  // namespace
+extern "C" int sdumc_distill_crit_teacher_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                           const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                           float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                           int32_t distill, int32_t regress, float regress_delta, const sdumc_teacher* teacher,
+                                           void* stream) {
+  const int have_teacher = sdumc_teacher_check(teacher, B, ssd_global != nullptr || denom != (float)B);
+  if (have_teacher < 0) return SDUMC_EINVAL;
   if (B <= 0 || denom <= 0.f || !vals || !labels || !th || !ct || !z || !weights5 || !d_vals || !d_th || !d_ct || !d_z ||
       !losses || !workspace || distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL ||
       !sdumc_regress_valid(regress, regress_delta))
@@ -1197,6 +1296,7 @@ extern "C" int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals
   a.d_vals = d_vals; a.d_th = d_th; a.d_ct = d_ct; a.d_z = d_z;
   a.losses = losses;
   a.part = workspace;
+  distill_teacher(a, have_teacher ? teacher : nullptr);
   const int64_t per[3] = {SDUMC_D, SDUMC_NQ * SDUMC_H, SDUMC_H};
   int mx = 1;
   for (int p = 0; p < 3; ++p) {
@@ -1211,6 +1311,22 @@ extern "C" int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals
   hipLaunchKernelGGL(distill_apply_kernel, dim3(mx > 2 ? mx : 2, 4), dim3(256), 0, st, a);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
+}
+
+extern "C" int sdumc_distill_crit_reg_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                       const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                       float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                       int32_t distill, int32_t regress, float regress_delta, void* stream) {
+  return sdumc_distill_crit_teacher_(B, denom, vals, labels, th, ct, z, weights5, ssd_global, d_vals, d_th, d_ct, d_z, losses,
+                                     workspace, distill, regress, regress_delta, nullptr, stream);
+}
+
+extern "C" int sdumc_distill_teacher_fwd_bwd(int32_t B, float denom, const float* vals, const float* labels, const float* th,
+                                             const float* ct, const float* z, const float* weights5, const float* ssd_global,
+                                             float* d_vals, float* d_th, float* d_ct, float* d_z, float* losses, float* workspace,
+                                             int32_t distill, const sdumc_teacher* teacher, void* stream) {
+  return sdumc_distill_crit_teacher_(B, denom, vals, labels, th, ct, z, weights5, ssd_global, d_vals, d_th, d_ct, d_z, losses,
+                                     workspace, distill, SDUMC_REGRESS_MSE, 0.f, teacher, stream);
 }
 
 extern "C" int sdumc_distill_crit_(int32_t B, float denom, const float* vals, const float* labels, const float* th,
@@ -1256,12 +1372,15 @@ extern "C" int sdumc_ce_fwd_bwd(const float* a, const float* b, int32_t rows, in
 // MSE x2 + the distillation criterion x3 + RnC over cat(stream 0, stream 1) with the labels repeated (main :134-148): values and every gradient
 // w.r.t. the network outputs in two launches.  Returns 1 when the shape is not one it takes (n = 2B > 256: the sorted RnC form).
 // regress: the criterion of the two regression terms (SDUMC_REGRESS_*; the p == 3 workgroups of the second launch).
-extern "C" int sdumc_losses_fused_reg_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
-                                       const float* z, const float* rnc_feats, int32_t rd, float temperature,
-                                       const float* weights6, float* d_vals, float* d_th, float* d_ct, float* d_z, float* d_rnc,
-                                       float* losses, float* distill_ws, float* rnc_workspace, float* hyper, double beta1,
-                                       double beta2, int32_t distill, int32_t regress, float regress_delta, void* stream) {
+extern "C" int sdumc_losses_fused_teacher_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
+                                           const float* z, const float* rnc_feats, int32_t rd, float temperature,
+                                           const float* weights6, float* d_vals, float* d_th, float* d_ct, float* d_z,
+                                           float* d_rnc, float* losses, float* distill_ws, float* rnc_workspace, float* hyper,
+                                           double beta1, double beta2, int32_t distill, int32_t regress, float regress_delta,
+                                           const sdumc_teacher* teacher, void* stream) {
   const int n = 2 * B;
+  const int have_teacher = sdumc_teacher_check(teacher, B, false);
+  if (have_teacher < 0) return SDUMC_EINVAL;
   if (distill < SDUMC_DISTILL_RMSE || distill > SDUMC_DISTILL_KL || !sdumc_regress_valid(regress, regress_delta)) return SDUMC_EINVAL;
   if (B <= 0 || n > 256 || rd <= 0 || temperature <= 0.f) return 1;
   const size_t lds1 = (((size_t)rd + 3) & ~(size_t)3) * sizeof(float) + 5 * (size_t)n * sizeof(float);
@@ -1279,6 +1398,7 @@ extern "C" int sdumc_losses_fused_reg_(int32_t B, const float* vals, const float
   a.d_vals = d_vals; a.d_th = d_th; a.d_ct = d_ct; a.d_z = d_z;
   a.losses = losses;
   a.part = distill_ws;
+  distill_teacher(a, have_teacher ? teacher : nullptr);
   const int64_t per[3] = {SDUMC_D, SDUMC_NQ * SDUMC_H, SDUMC_H};
   int mx = 1;
   for (int p = 0; p < 3; ++p) {
@@ -1298,6 +1418,16 @@ extern "C" int sdumc_losses_fused_reg_(int32_t B, const float* vals, const float
   hipLaunchKernelGGL(loss_stage2_kernel, dim3(n + 4 * amx + 1), dim3(256), lds2, st, a, r, amx, hyper, beta1, beta2);
   SDUMC_CHECK_LAUNCH();
   return SDUMC_OK;
+}
+
+extern "C" int sdumc_losses_fused_reg_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,
+                                       const float* z, const float* rnc_feats, int32_t rd, float temperature,
+                                       const float* weights6, float* d_vals, float* d_th, float* d_ct, float* d_z, float* d_rnc,
+                                       float* losses, float* distill_ws, float* rnc_workspace, float* hyper, double beta1,
+                                       double beta2, int32_t distill, int32_t regress, float regress_delta, void* stream) {
+  return sdumc_losses_fused_teacher_(B, vals, labels, th, ct, z, rnc_feats, rd, temperature, weights6, d_vals, d_th, d_ct, d_z, d_rnc,
+                                     losses, distill_ws, rnc_workspace, hyper, beta1, beta2, distill, regress, regress_delta, nullptr,
+                                     stream);
 }
 
 extern "C" int sdumc_losses_fused_(int32_t B, const float* vals, const float* labels, const float* th, const float* ct,

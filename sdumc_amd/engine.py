@@ -507,12 +507,24 @@ class TrainStep(_OptStateMixin):
     launch() refuses until a batch is installed.  set_lengths copies into step-owned buffers, use_lengths points at the caller's: neither
     writes through the other's tensors."""
 
+    _teacher = _teacher_rows = _teacher_idx = None      # (teacher=: a stored teacher and the rows of the next launch)
+
     def __init__(self, flat_params, B, T, dims, weights=DEFAULT_WEIGHTS, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=1e-5, seed=0, train=True, sample0=0, bf16=False, share=None, arena=None, ctx=None, planes=None,
                  bits_next=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
                  skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, rates=None, ema_decay=None, ema_warmup=False,
-                 decoupled_decay=False, regress='mse', regress_delta=1.0):
-        """regress ('mse' = today's step, launch for launch and bit for bit): the criterion of the two regression terms (main :137-138;
+                 decoupled_decay=False, regress='mse', regress_delta=1.0, teacher=None):
+        """teacher (None = today's step, through the entry it always took): a teacher.TeacherTargets -- distillation targets from a
+        STORED teacher.  For every pair it holds a table of (text_hidden, cross_text, fused; losses[3:6]) the target of sample b is
+        table row idx[b] instead of stream 0's row b, a constant: stream 0 gets no gradient from that pair -- for `fused` too, the one
+        pair self-distillation does not detach.  The loss stage's kernels read the tables through the index vector (a workgroup reads its
+        chunk's indices, at most 32, once into LDS): no further launch, nothing on the host per step; tables that hold bit copies of stream 0's rows give the
+        default step's bits.  .teacher is settable between launches (a TeacherTargets or None); use_teacher_rows(idx) names the rows
+        of the NEXT launches (a device int64 [B] tensor, checked on the host against the tables and their `seen`; None: the tables
+        are [B, ...] in batch order).  Combines with distill / regress / contrast, clip_norm / skip_nonfinite (a NaN table row is a
+        NaN loss: the guard skips the step), freeze / lr_scale / decay_scale, ema_decay, decoupled_decay and bf16 storage.  A step with
+        a teacher is not captured (capture() raises: a graph would replay one index vector's address).
+        regress ('mse' = today's step, launch for launch and bit for bit): the criterion of the two regression terms (main :137-138;
         losses[1:3], the seed of the backward): 'l1' (torch.nn.L1Loss), 'huber' (torch.nn.HuberLoss(delta=regress_delta)), both under
         MSELoss's reduction (sum over rows / B), or 'ccc' (1 - the concordance correlation coefficient of the batch, moments in
         double).  Computed by the workgroups of the loss stage that held the MSE terms: no further launch, so it combines with
@@ -591,6 +603,9 @@ class TrainStep(_OptStateMixin):
         dev = flat_params.device
         _require_cuda(flat_params)
         self.params = flat_params
+        from .teacher import teacher_arg
+        self._teacher = teacher_arg(teacher, dev, "TrainStep")
+        self._teacher_rows = self._teacher_idx = None      # the index tensor (kept alive) / its device address; None: row b
         self.dims = make_dims(B, 2, Ta, Tv, (Tt, T4), dims, train, sample0, bf16=bf16)
         nbytes = lib.sdumc_step_workspace_bytes(C.byref(self.dims))
         if nbytes == 0:
@@ -796,6 +811,51 @@ class TrainStep(_OptStateMixin):
     def set_lr(self, lr):
         self.hyper[0] = lr
 
+    @property
+    def teacher(self):
+        """the teacher.TeacherTargets the next launch reads its distillation targets from; None: stream 0, as always"""
+        return self._teacher
+
+    @teacher.setter
+    def teacher(self, targets):
+        from .teacher import teacher_arg
+        targets = teacher_arg(targets, self.params.device, "TrainStep.teacher")
+        if self.graph is not None and targets is not None and targets.active:
+            raise _lib.SdumcError("teacher: the captured hipGraph was recorded without one")
+        self._teacher = targets
+        self._teacher_rows = self._teacher_idx = None      # (rows named for another table are not carried over)
+
+    def use_teacher_rows(self, idx):
+        """The rows of the teacher's tables the NEXT launches read: a device int64 [B] tensor (row idx[b] is the target of sample b),
+        or None (row b: the tables are [B, ...] in batch order).  Checked on the host -- range and the teacher's `seen` -- before
+        anything is enqueued; the step keeps the tensor alive."""
+        t = self._teacher
+        if idx is None or t is None or not t.active:
+            self._teacher_rows = self._teacher_idx = None
+            return self
+        if not (torch.is_tensor(idx) and idx.dtype == torch.int64 and idx.device == self.params.device and idx.is_contiguous()
+                and idx.numel() == self.B):
+            raise _lib.SdumcError(f"use_teacher_rows: a contiguous int64 [{self.B}] tensor on {self.params.device}, or None")
+        t.check_rows(idx, "use_teacher_rows")
+        self._teacher_rows, self._teacher_idx = idx, idx.data_ptr()
+        return self
+
+    def _use_teacher_ptr(self, targets, idx_ptr):
+        """FusedTrainer's launches: the run's teacher and the device address of this batch's index vector (both checked by the
+        trainer, once per epoch or batch, against the tables; the trainer keeps the indices alive)"""
+        self._teacher, self._teacher_rows, self._teacher_idx = targets, None, idx_ptr
+
+    def _step_entry(self):
+        """(entry, its arguments behind dims and io, its name): sdumc_train_step, or with a teacher that holds a table
+        sdumc_train_step_teacher and this launch's record"""
+        t = self._teacher
+        if t is None or not t.active:
+            return lib.sdumc_train_step, (C.byref(self.cfg),), "sdumc_train_step"
+        if self._teacher_idx is None:
+            t.check_batch(self.B, "launch")
+        self._teacher_rec = t.record(self._teacher_idx)      # (host memory, read during the call)
+        return lib.sdumc_train_step_teacher, (C.byref(self.cfg), C.byref(self._teacher_rec)), "sdumc_train_step_teacher"
+
     def launch(self, stream=None, next_step=None, prefetch=None, pregen=True):
         """Enqueues the step.  next_step: the TrainStep that runs NEXT in this arena (its dims decide how this step's middle lays out
         the next keep-bits set); prefetch: the sdumc_gather_batch descriptor of the next batch, issued by the step beside its middle
@@ -803,6 +863,7 @@ class TrainStep(_OptStateMixin):
         if self._src is None:
             raise _lib.SdumcError("launch: no batch is installed (set_batch, use_set, use_store or use_batch first)")
         st = _lib.current_stream() if stream is None else stream
+        entry, args, name = self._step_entry()      # (what a teacher's host checks refuse: before any field of io is touched)
         io = self.io
         a = self._arena
         shared = a is not None and a.bits is not None and io.bits_next
@@ -814,8 +875,7 @@ class TrainStep(_OptStateMixin):
         io.bits_next_dims = C.addressof(next_step.dims) if next_step is not None else None
         io.prefetch_workgroups = a.prefetch_workgroups if a is not None else 0
         try:
-            check(epoch.with_prefetch(io, prefetch, lib.sdumc_train_step, C.byref(self.dims), C.byref(io), C.byref(self.cfg), st),
-                  "sdumc_train_step")
+            check(epoch.with_prefetch(io, prefetch, entry, C.byref(self.dims), C.byref(io), *args, st), name)
         finally:
             io.bits_next, io.bits_next_dims = saved, None
         if pregen or self.graph is not None:
@@ -836,6 +896,8 @@ class TrainStep(_OptStateMixin):
             raise _lib.SdumcError("capture: a step with ema_decay is not captured (not built)")
         if self.decoupled_decay:
             raise _lib.SdumcError("capture: a step with decoupled_decay is not captured (not built)")
+        if self._teacher is not None and self._teacher.active:
+            raise _lib.SdumcError("capture: a step with a teacher is not captured (not built)")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
@@ -970,12 +1032,18 @@ class FusedTrainer:
     (sdumc_net_io.prefetch) -- and every step tells the engine the next batch's shape, so that the next keep-bits are laid out for it."""
 
     guard = None      # with clip_norm / skip_nonfinite: the run's device float[4] every step writes (sdumc_grad_guard)
+    teacher = None    # a teacher.TeacherTargets: the stored teacher every step reads its distillation targets from (set_teacher)
 
     def __init__(self, flat_params, dims, max_cached=8, lr=1e-4, seed=0, capacity=None, planes=None, sets=2, prefetch_workgroups=0,
                  inplace=True, distill='rmse', contrast='rnc', contrast_temperature=None, contrast_classes='eq', clip_norm=None,
                  skip_nonfinite=False, freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False,
-                 decoupled_decay=False, regress='mse', regress_delta=1.0, **step_kwargs):
-        """distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
+                 decoupled_decay=False, regress='mse', regress_delta=1.0, teacher=None, **step_kwargs):
+        """teacher: a teacher.TeacherTargets (or None; set_teacher changes it between launches, refresh_teacher installs the eval-mode
+        embeddings of the run's own parameters or averaged weights) -- distillation targets from a stored teacher in every step
+        (TrainStep has the semantics).  The tables are in STORE order: step_from_store / run_epoch / train_epoch hand step i the index
+        vector of batch i; step(..., teacher_rows=) takes the rows of a batch the caller brings.  Read at every launch: a cached
+        step never runs with a table that is no longer the trainer's.
+        distill: 'rmse' | 'cosine' | 'kl', the distillation criterion of every step of this trainer (TrainStep).
         regress: 'mse' | 'l1' | 'huber' | 'ccc' with regress_delta, the regression criterion of every step (TrainStep); columns 1-2 of
         train_epoch's record hold its values.
         decoupled_decay (a bool): torch.optim.AdamW's decoupled weight decay in every step of the run (TrainStep has the rule).
@@ -1007,6 +1075,9 @@ class FusedTrainer:
         self.contrast = (contrast, contrast_temperature, contrast_classes)
         _require_cuda(flat_params)
         self.params, self.dims, self.max_cached = flat_params, tuple(dims), max(1, int(max_cached))
+        self.teacher = None
+        self.set_teacher(teacher)
+        self._teacher_res = None      # refresh_teacher's result, kept and reused
         self.kw = dict(step_kwargs, lr=lr, seed=seed, distill=distill, contrast=contrast, contrast_temperature=contrast_temperature,
                        contrast_classes=contrast_classes, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
         if ema_on:      # (off: the steps are built with the keywords they always were)
@@ -1095,8 +1166,36 @@ class FusedTrainer:
             raise _lib.SdumcError(f"{what}: weights='ema' on a trainer without averaged weights (ema_decay=)")
         return self.ema_params
 
-    def _launch(self, ts, next_step=None, prefetch=None):
+    def set_teacher(self, targets):
+        """The stored teacher of every step from now on (a teacher.TeacherTargets), or None: self-distillation"""
+        from .teacher import teacher_arg
+        self.teacher = teacher_arg(targets, self.params.device, "FusedTrainer")
+
+    def _teacher_on(self):
+        return self.teacher is not None and self.teacher.active
+
+    def _check_teacher_epoch(self, store, indices):
+        """an epoch's indices against the teacher's tables, on the host, before anything is enqueued"""
+        self.teacher.check_store(len(store), "epoch")
+        self.teacher.check_rows(indices, "epoch")
+
+    def refresh_teacher(self, store, batches, weights="params", key_padding=False, stream="full", pairs=("text_hidden", "cross_text", "fused")):
+        """One evaluation pass (eval_epoch(embeddings=True), into a result the trainer keeps and reuses) over `batches` of `store`
+        with the trainer's parameters, or with weights='ema' its averaged weights, whose embeddings of `stream` ('full' | 'missing')
+        become the teacher's tables for `pairs` -> the EvalResult.  Between epochs with weights='ema': a mean teacher at epoch
+        granularity.  Utterances the pass did not visit hold NaN: an epoch that names one is refused on the host."""
+        from .teacher import TeacherTargets
+        out = self._teacher_res
+        if out is not None and not out.fits(len(store), self.params.device, True):
+            out = None
+        res = self.eval_epoch(store, batches, key_padding=key_padding, embeddings=True, out=out, weights=weights)
+        self._teacher_res = res
+        self.set_teacher(TeacherTargets.from_eval(res, stream, pairs))
+        return res
+
+    def _launch(self, ts, next_step=None, prefetch=None, teacher_idx=None):
         # keep-bits for a next step only when its shape is known (run_epoch) or has been repeating (a static-shape loader)
+        ts._use_teacher_ptr(self.teacher, teacher_idx)
         key = (ts.B,) + ts.T
         pregen = next_step is not None or key == self._last_shape
         self._last_shape = key
@@ -1119,10 +1218,16 @@ class FusedTrainer:
         if self.arena is None:
             raise _lib.SdumcError("step_from_store needs FusedTrainer(capacity=...)")
         B, T = store.batch_shape(indices)
+        teacher_idx = None
+        if self._teacher_on():      # (refused here, before the batch's assembly is enqueued)
+            self.teacher.check_store(len(store), "step_from_store")
+            self._keep_rows = self.teacher.check_rows(indices, "step_from_store").to(self.params.device)
+            teacher_idx = self._keep_rows.data_ptr()
         ts = self._get(B, T)
         st = self.arena.sets[0]
         if self._in_place(store):
-            idx_d = store._checked(indices).to(store.device, non_blocking=True)
+            # (one upload of the batch's indices: the row maps' gather and the teacher read the same vector)
+            idx_d = self._keep_rows if teacher_idx is not None else store._checked(indices).to(store.device, non_blocking=True)
             g = epoch.gather_desc(store, idx_d.data_ptr(), B, T, st, key_padding, True, True)
             check(lib.sdumc_gather_batch(C.byref(g), 0, _lib.current_stream()), "sdumc_gather_batch")
             self._keep_idx = idx_d
@@ -1133,7 +1238,7 @@ class FusedTrainer:
             store.batch_into(indices, (ts.audio, ts.text, ts.video, ts.feat4), ts.labels, st.lengths if key_padding else None,
                              st.planes if planes else None)
         ts.use_lengths(st.lengths if key_padding else None)
-        return self._launch(ts)
+        return self._launch(ts, teacher_idx=teacher_idx)
 
     def run_epoch(self, store, batches, key_padding=False, on_step=None):
         """Every batch of `batches` (index vectors into `store`, or a data.EpochPlan), in order: main :89-150's loop.  The first batch
@@ -1148,10 +1253,20 @@ class FusedTrainer:
         if self.arena is None or len(self.arena.sets) < 2:
             raise _lib.SdumcError(f"{what} needs FusedTrainer(capacity=..., sets=2)")
 
-    def _epoch(self, store, plan, key_padding, on_step, record=None):
+    def _epoch(self, store, plan, key_padding, on_step, record=None, teacher_checked=False):
         """The loop of run_epoch and train_epoch over a data.EpochPlan.  record(i, ts) is called right after step i has been enqueued
-        (ts = the step that ran it), before on_step."""
+        (ts = the step that ran it), before on_step.  teacher_checked: the caller has held the epoch's indices against the teacher."""
         # the arena must hold the epoch's largest batch BEFORE the first descriptor is built (growing it invalidates every cached step)
+        launch = self._launch
+        if self._teacher_on():
+            # the epoch's indices against the tables, once, on the host; then step i reads ITS batch's index vector (the same step
+            # prefetches batch i + 1 through another pointer)
+            if not teacher_checked:
+                self._check_teacher_epoch(store, plan.idx_h if getattr(plan, "idx_h", None) is not None else plan.idx_d)
+            batch_no = iter(range(len(plan)))
+
+            def launch(ts, nxt, pf):
+                return self._launch(ts, nxt, pf, plan.idx_ptr(next(batch_no)))
         self._fit_arena(max(B for B, _ in plan.shapes), tuple(max(T[i] for _, T in plan.shapes) for i in range(4)))
         sets, inplace = self.arena.sets, self._in_place(store)
         planes = inplace or self._store_planes(store)
@@ -1166,7 +1281,7 @@ class FusedTrainer:
                 record(i, ts)
             on_step(i, ts.losses)
 
-        return epoch.run(self, store, plan, sets, key_padding, planes, inplace, self._get, bind, self._launch,
+        return epoch.run(self, store, plan, sets, key_padding, planes, inplace, self._get, bind, launch,
                          record if on_step is None else both)
 
     def train_epoch(self, store, batches, key_padding=False, on_step=None, embeddings=False, grad_norm=False, out=None, by_tensor=False):
@@ -1190,6 +1305,9 @@ class FusedTrainer:
         by_tensor = by_tensor_mode(by_tensor)
         dev, n_store = self.params.device, len(store)
         plan, batches = epoch.checked_plan(batches, n_store)
+        if self._teacher_on():      # (before the record is made or reset)
+            host = torch.cat(batches) if plan is None else (plan.idx_h if getattr(plan, "idx_h", None) is not None else plan.idx_d)
+            self._check_teacher_epoch(store, host)
         n = len(plan if plan is not None else batches)
         lay = ParamLayout.get(*self.dims[:3])
         n_grads = lay.live if grad_norm else 0
@@ -1233,7 +1351,7 @@ class FusedTrainer:
             if guard:
                 rec.guard[i].copy_(self.guard, non_blocking=True)
 
-        rec.steps = self._epoch(store, plan, key_padding, on_step, record)
+        rec.steps = self._epoch(store, plan, key_padding, on_step, record, teacher_checked=True)
         return rec
 
     def _record_desc(self, rec, ts, embeddings, grad_norm):
@@ -1279,9 +1397,21 @@ class FusedTrainer:
                                          prefetch_workgroups=kw["prefetch_workgroups"]))
         return getattr(self, attr).saliency_epoch(store, batches, key_padding=key_padding, streams=streams, out=out)
 
-    def step(self, audio, text, video, feat4, labels, lengths=None):
+    def step(self, audio, text, video, feat4, labels, lengths=None, teacher_rows=None):
         """One optimisation step on one batch of any shape; returns the device loss vector
-        [total, mse_full, mse_missing, rmse_text, rmse_query, rmse_fused, rnc, 0]."""
+        [total, mse_full, mse_missing, rmse_text, rmse_query, rmse_fused, rnc, 0].
+        teacher_rows (a trainer with a teacher): the [B] rows of the teacher's tables this batch's samples have (indices, on the host
+        or the device; checked on the host), or None: the tables are [B, ...] in this batch's order."""
+        teacher_idx = None
+        if self._teacher_on():
+            if teacher_rows is None:
+                self.teacher.check_batch(audio.shape[0], "step")
+            else:
+                rows = self.teacher.check_rows(teacher_rows, "step")
+                if rows.numel() != audio.shape[0]:
+                    raise _lib.SdumcError(f"step: teacher_rows has {rows.numel()} entries for a batch of {audio.shape[0]}")
+                self._keep_rows = rows.to(self.params.device)
+                teacher_idx = self._keep_rows.data_ptr()
         ts = self._get(audio.shape[0], (audio.shape[1], text.shape[1], video.shape[1], feat4.shape[1]))
         if self.arena is not None:
             ts.use_set(0, planes=False)      # (fresh tensors: a split for one use costs more than the planes save)
@@ -1290,6 +1420,6 @@ class FusedTrainer:
         batch = (audio, text, video, feat4, labels.reshape(-1) if torch.is_tensor(labels) else labels)
         self._batch = batch if ts.use_batch(*batch) else None
         ts.set_lengths(lengths)
-        losses = self._launch(ts)
+        losses = self._launch(ts, teacher_idx=teacher_idx)
         ts._bind(None)
         return losses

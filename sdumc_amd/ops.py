@@ -585,6 +585,33 @@ def kl_fwd_bwd(a, b, weight=1.0, denom=None, need_da=True, need_db=True):
     return _row_crit(lib.sdumc_kl_fwd_bwd, "sdumc_kl_fwd_bwd", a, b, weight, denom, need_da, need_db)
 
 
+def distill_teacher_fwd_bwd(vals, labels, th, ct, z, weights5, teacher=None, rows=None, distill="rmse"):
+    """sdumc_distill_teacher_fwd_bwd on the [2B, ...] stream-major outputs vals [2B], th [2B, 256], ct [2B, 7, 128], z [2B, 128] and
+    labels [B]: the two regression terms and the three distillation pairs, the pairs `teacher` (a teacher.TeacherTargets, or None)
+    holds a table of against table row rows[b] (a device int64 [B] tensor checked on the host; None: row b) -> losses [8] (entries
+    1..5 written), d_vals, d_th, d_ct, d_z."""
+    from .teacher import teacher_arg
+    teacher = teacher_arg(teacher, vals.device, "distill_teacher_fwd_bwd")
+    B = labels.numel()
+    rec = None
+    if teacher is not None and teacher.active:
+        if rows is None:
+            teacher.check_batch(B, "distill_teacher_fwd_bwd")
+        else:
+            if rows.dtype != torch.int64 or rows.device != vals.device or not rows.is_contiguous() or rows.numel() != B:
+                raise _lib.SdumcError(f"distill_teacher_fwd_bwd: rows must be a contiguous int64 [{B}] tensor on {vals.device}")
+            teacher.check_rows(rows, "distill_teacher_fwd_bwd")
+        rec = teacher.record(ptr(rows))
+    losses = torch.zeros(8, device=vals.device)
+    outs = tuple(torch.empty_like(t) for t in (vals, th, ct, z))
+    ws = torch.empty(max(lib.sdumc_distill_workspace_bytes(B), 16), dtype=torch.uint8, device=vals.device)
+    w5 = (C.c_float * 5)(*weights5)
+    check(lib.sdumc_distill_teacher_fwd_bwd(B, float(B), ptr(vals), ptr(labels), ptr(th), ptr(ct), ptr(z), w5, None,
+                                            *(ptr(o) for o in outs), ptr(losses), ptr(ws), _lib.distill_code(distill),
+                                            C.byref(rec) if rec is not None else None, _st()), "sdumc_distill_teacher_fwd_bwd")
+    return (losses,) + outs
+
+
 def ce_fwd_bwd(logits, target, weight=1.0, denom=None):
     """CELoss (loss.py:6-16): logits [N, C] fp32, target [N] class indices held as fp32: loss [1], dlogits."""
     if logits.dim() != 2 or target.numel() != logits.shape[0]:

@@ -34,7 +34,7 @@ class HipBackend:
     """Per-rank compute on one MI355X through the C ABI."""
 
     def __init__(self, flat_params, B, T, dims, weights, lr, betas, eps, weight_decay, seed, sample0, B_global,
-                 bf16=False, share=None, planes=False, distill='rmse', regress='mse', regress_delta=1.0):
+                 bf16=False, share=None, planes=False, distill='rmse', regress='mse', regress_delta=1.0, teacher=None):
         """distill: 'rmse' | 'cosine' | 'kl', the criterion of the three distillation pairs (engine.TrainStep).  Cosine and KL
         are sums over rows / B_global: the rank's loss entries 3..5 are then LOCAL shares like the MSE entries, and the
         sums of squares of the exchange record are carried but not read.
@@ -50,6 +50,8 @@ class HipBackend:
         from . import _lib, engine
         self._lib, self._engine = _lib, engine
         lib = _lib.lib
+        if teacher is not None:      # the rank exchange carries no teacher (sdumc_teacher is refused beside global sums)
+            raise _lib.SdumcError("HipBackend: teacher= is not built under data parallelism (single-GPU steps only)")
         regress_code, regress_d = _lib.regress_args(regress, regress_delta)
         if regress == 'ccc':
             raise _lib.SdumcError("HipBackend: regress='ccc' is not built under data parallelism (single-GPU steps only)")
@@ -222,10 +224,13 @@ class DataParallelStep:
     def __init__(self, flat_params, B, T, dims, weights=(0.5, 0.5, 0.1, 0.7, 0.1, 0.8), lr=1e-4, betas=(0.9, 0.999),
                  eps=1e-8, weight_decay=1e-5, seed=0, exact=True, backend_factory=None, bf16=False,
                  force_collectives=False, planes=False, distill='rmse', contrast='rnc', clip_norm=None, skip_nonfinite=False,
-                 freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False, regress='mse', regress_delta=1.0):
+                 freeze=None, lr_scale=None, decay_scale=None, ema_decay=None, ema_warmup=False, regress='mse', regress_delta=1.0,
+                 teacher=None):
         import collections
         import inspect
         from ._lib import SdumcError, contrast_code, regress_args
+        if teacher is not None:      # the fused single-GPU step's (engine.TrainStep): the rank exchange carries no teacher
+            raise SdumcError("DataParallelStep: teacher= is not built under data parallelism (single-GPU steps only)")
         regress_args(regress, regress_delta)
         if regress == 'ccc':      # the moments of the whole batch would need an exchange of their own: no local-only CCC
             raise SdumcError("DataParallelStep: regress='ccc' is not built under data parallelism (single-GPU steps only)")
