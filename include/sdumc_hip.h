@@ -1396,6 +1396,15 @@ int sdumc_debug_marks_read(float* ms, int n);
  * sdumc_net_io.workspace); returns the text length, or minus the buffer size needed.  For probes that compare intermediate
  * tensors of two runs (tools/fwd_determinism_probe.py); not part of the data path. */
 int32_t sdumc_debug_plan_table(const sdumc_net_dims* d, char* buf, size_t buflen);
+/* Debug: the schedule the backward pass of a call with these dims and io (its context's options, its feature pointers) would take,
+ * as text lines "name value": rc, chain, cluster, fra_fold, utterance, frame, dw_grouped, pool_grouped, early_one_launch,
+ * flush1_after_pool, flush2_after_query, flush3_after_utt, then per modality (suffix _a / _t / _v) early, early_lane, ca_dw_grouped,
+ * fra_dw_grouped, ca_dw_late, dw_on_lane3, dx_sum, frame_dw_grouped, frame_dw_skip, k1.  phases: 3 = sdumc_net_backward and
+ * sdumc_train_step, 1 / 2 = sdumc_net_backward_phase 0 / 1; frozen_frame_dw: bit m = frame_dim_reshape_m frozen (the fused step).
+ * Returns the text length, minus the buffer size needed, or 0 for arguments the call itself would refuse.  Launches nothing and
+ * records no event; for tests that hold every route to the reference (tests/test_gpu_backward_routes.py). */
+int32_t sdumc_debug_backward_schedule(const sdumc_net_dims* d, const sdumc_net_io* io, int32_t phases, uint32_t frozen_frame_dw,
+                                      void* stream, char* buf, size_t buflen);
 size_t sdumc_net_workspace_bytes(const sdumc_net_dims* d);
 int sdumc_net_forward(const sdumc_net_dims* d, const sdumc_net_io* io, void* stream);
 

@@ -644,6 +644,8 @@ _SIGS = {
     "sdumc_debug_marks_read": (C.c_int, [C.POINTER(C.c_float), C.c_int]),
     "sdumc_attnpool_set_v2_": (C.c_int, [C.c_int]),
     "sdumc_debug_plan_table": (C.c_int32, [C.POINTER(NetDims), C.c_char_p, C.c_size_t]),
+    "sdumc_debug_backward_schedule": (C.c_int32, [C.POINTER(NetDims), C.POINTER(NetIO), C.c_int32, C.c_uint32, C.c_void_p,
+                                                  C.c_char_p, C.c_size_t]),
     "sdumc_net_workspace_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_net_bits_next_bytes": (C.c_size_t, [C.POINTER(NetDims)]),
     "sdumc_net_forward": (C.c_int, [C.POINTER(NetDims), C.POINTER(NetIO), C.c_void_p]),

@@ -2198,7 +2198,7 @@ int keys_gemm_bwd(const Ctx& c, int m, int k0, int k1, int parts = 3, int rows_c
     g.b_drop = in_drop(c, k0, m, sg.T, sg.s0, sg.row0);
     g.ab_drop_group_stride = SITE_IN[1][m] - SITE_IN[0][m];
     g.accumulate = first ? 0 : 1;
-    g.bf16 = c.d.bf16 ? 1 : 0;
+    g.bf16 = c.d.bf16 && (rows % 4 == 0) ? 1 : 0;      // (the bf16-operand TN kernel takes K in whole fours: an odd run multiplies in fp32)
     RET(run(c, g));
     first = false;
   }
@@ -2614,7 +2614,7 @@ int frame_dw_per_layer(const Ctx& c, int m, int s) {
   sdumc_gemm g = G_(SDUMC_TN, D, din, rows);
   g.A[0] = c.p(c.pl.dx[m][s]);
   fill(g);
-  g.bf16 = c.d.bf16 && (din % 4 == 0) ? 1 : 0;
+  g.bf16 = c.d.bf16 && (din % 4 == 0) && (rows % 4 == 0) ? 1 : 0;      // (K = rows: B * T of a text stream need not be a multiple of 4)
   return run(c, g);
 }
 
@@ -3285,6 +3285,36 @@ extern "C" int32_t sdumc_debug_plan_table(const sdumc_net_dims* d, char* buf, si
     put(std::string("dx_") + mod[m], p.dx[m][0], p.rows[m] / (m == 1 ? 1 : p.S) * D / HS);
   }
   put("d_hpre", p.d_hpre, 3 * V * D); put("d_ca_out", p.d_ca_out, 3 * V * NQ * D);
+  if (!buf || s.size() + 1 > buflen) return -(int32_t)(s.size() + 1);
+  memcpy(buf, s.c_str(), s.size() + 1);
+  return (int32_t)s.size();
+}
+
+// debug / tests (tests/test_gpu_backward_routes.py): the record plan_backward() decides for a call of these dims, io (its context's
+// options), phases (3 = the single call, 1 / 2 = phase 0 / phase 1) and frozen frame projections, as text lines "name value";
+// per-modality fields carry the suffix _a / _t / _v.  Built as net_backward_impl builds it; launches nothing, records no event.
+extern "C" int32_t sdumc_debug_backward_schedule(const sdumc_net_dims* d, const sdumc_net_io* io, int32_t phases,
+                                                 uint32_t frozen_frame_dw, void* stream, char* buf, size_t buflen) {
+  if (check_io(d, io) != SDUMC_OK || phases < 1 || phases > 3) return 0;
+  const SplitScope split_scope(io);
+  Ctx c{*d, *io, as_stream(stream), build_params(d->da, d->dt, d->dv), Plan(), nullptr, nullptr, nullptr};
+  if (ctx_init(c) != SDUMC_OK) return 0;
+  const BwdSchedule sch = plan_backward(c, plan_utterance(c), phases, frozen_frame_dw);
+  std::string s;
+  auto put = [&](const std::string& name, int v) { s += name + " " + std::to_string(v) + "\n"; };
+  put("rc", sch.rc); put("chain", sch.chain); put("cluster", sch.cluster); put("fra_fold", sch.fra_fold);
+  put("utterance", sch.utterance); put("frame", sch.frame); put("dw_grouped", sch.dw_grouped); put("pool_grouped", sch.pool_grouped);
+  put("early_one_launch", sch.early_one_launch); put("flush1_after_pool", sch.flush1_after_pool);
+  put("flush2_after_query", sch.flush2_after_query); put("flush3_after_utt", sch.flush3_after_utt);
+  const char* mod[3] = {"_a", "_t", "_v"};
+  for (int m = 0; m < 3; ++m) {
+    const BwdSchedule::Mod& M = sch.mod[m];
+    put(std::string("early") + mod[m], M.early); put(std::string("early_lane") + mod[m], M.early_lane);
+    put(std::string("ca_dw_grouped") + mod[m], M.ca_dw_grouped); put(std::string("fra_dw_grouped") + mod[m], M.fra_dw_grouped);
+    put(std::string("ca_dw_late") + mod[m], M.ca_dw_late); put(std::string("dw_on_lane3") + mod[m], M.dw_on_lane3);
+    put(std::string("dx_sum") + mod[m], M.dx_sum); put(std::string("frame_dw_grouped") + mod[m], M.frame_dw_grouped);
+    put(std::string("frame_dw_skip") + mod[m], M.frame_dw_skip); put(std::string("k1") + mod[m], M.k1);
+  }
   if (!buf || s.size() + 1 > buflen) return -(int32_t)(s.size() + 1);
   memcpy(buf, s.c_str(), s.size() + 1);
   return (int32_t)s.size();

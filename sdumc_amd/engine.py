@@ -232,6 +232,28 @@ class ExecContext:
             pass
 
 
+def backward_schedule(call, phases=3):
+    """Debug: the record the backward pass of `call` (a NetCall or TrainStep: its .dims and .io, the context's options included) would
+    take -- {field: int} of sdumc_debug_backward_schedule; phases 3 = the single call (NetCall.backward, the fused step), 1 / 2 =
+    sdumc_net_backward_phase 0 / 1.  A TrainStep's frozen frame projections (freeze=: weight AND bias) are passed as the step passes
+    them.  Launches nothing."""
+    frozen = 0
+    rates = getattr(call, "rates", None)
+    if rates is not None:
+        is_frozen = dict(zip(rates.names, rates.frozen))
+        for m in range(3):
+            if is_frozen.get(f"frame_dim_reshape_{m}.weight") and is_frozen.get(f"frame_dim_reshape_{m}.bias"):
+                frozen |= 1 << m
+    args = (C.byref(call.dims), C.byref(call.io), int(phases), frozen, _lib.current_stream())
+    need = -lib.sdumc_debug_backward_schedule(*args, None, 0)
+    if need <= 0:
+        raise _lib.SdumcError("sdumc_debug_backward_schedule: arguments the call itself would refuse")
+    buf = C.create_string_buffer(need)
+    if lib.sdumc_debug_backward_schedule(*args, buf, need) <= 0:
+        raise _lib.SdumcError("sdumc_debug_backward_schedule failed")
+    return {k: int(v) for k, v in (line.split() for line in buf.value.decode().splitlines())}
+
+
 class RngState:
     """Device-resident {seed_lo, seed_hi, call}: lets captured graphs draw fresh masks per replay."""
 

@@ -34,8 +34,9 @@ class HipBackend:
     """Per-rank compute on one MI355X through the C ABI."""
 
     def __init__(self, flat_params, B, T, dims, weights, lr, betas, eps, weight_decay, seed, sample0, B_global,
-                 bf16=False, share=None, planes=False, distill='rmse', regress='mse', regress_delta=1.0, teacher=None):
-        """distill: 'rmse' | 'cosine' | 'kl', the criterion of the three distillation pairs (engine.TrainStep).  Cosine and KL
+                 bf16=False, share=None, planes=False, distill='rmse', regress='mse', regress_delta=1.0, teacher=None, ctx=None):
+        """ctx: an engine.ExecContext whose lanes and schedule options every call of this backend takes (None: the device's default).
+        distill: 'rmse' | 'cosine' | 'kl', the criterion of the three distillation pairs (engine.TrainStep).  Cosine and KL
         are sums over rows / B_global: the rank's loss entries 3..5 are then LOCAL shares like the MSE entries, and the
         sums of squares of the exchange record are carried but not read.
         regress: 'mse' | 'l1' | 'huber' (with regress_delta), the criterion of the two regression terms (engine.TrainStep).  L1 and
@@ -72,7 +73,7 @@ class HipBackend:
         self.state = st
         self.rng = st.rng
         self.call = engine.NetCall(flat_params, self.audio, [self.text, self.feat4], self.video, True, self.rng,
-                                   sample0=sample0, bf16=bf16, planes=planes, bits_next=True)
+                                   sample0=sample0, bf16=bf16, planes=planes, bits_next=True, ctx=ctx)
         V = 2 * B
         self.d_vals = torch.empty(V, 1, device=dev)
         self.d_fused = torch.empty(V, engine.H, device=dev)
